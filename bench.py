@@ -6,10 +6,16 @@ every one of the S resident streams by T blocks (S*T frames).  Inputs are synthe
 generated on the device and resident in HBM before the timed region; state stays on the device between
 steps.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--blocks T] [--fs 16000|8000]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams S] [--blocks T] [--fs 16000|8000] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what needs work outside the timed
+steps: the CPU re-run of the timed workload (`parity`, `content` shares), the CPU baseline, the rocprofv3 counter passes
+(`roofline.live_counters`) and the profile record of the timed kernel (`roofline.traffic`, `issue_bound`).
+--dump-outputs DIR writes the output rows of the last timed step as DIR/out.npy (float32 [R, L]): rank 0's streams, a
+fixed seeded choice of R rows when all S would exceed 60 MiB.  The inputs depend only on the arguments (seeded).
 
 N > 1: one rank per GPU.  Started by hand (`python bench.py --gpus N`, no WORLD_SIZE in the environment) the
-script re-executes itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N`; started by
+script starts itself under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` in a child process; started by
 torch.distributed.run it reads RANK / LOCAL_RANK / WORLD_SIZE.  Every rank owns S streams (weak scaling, no
 data-path collective); RCCL only lines the ranks up and gathers the counters.  Prints ONE JSON line on rank 0.
 """
@@ -85,6 +91,21 @@ def synth_on_device(torch, S, L, seed, device, chunk=8192, profile="recipe"):
         near[s0:s0 + n] = y.clamp_(-32768, 32767).round_().to(torch.int16)
         del env, x, echo, tenv, y
     return far, near
+
+
+DUMP_BYTES = 60 << 20                 # --dump-outputs: below the 64 MB a dump may hold
+
+
+def dump_outputs(dir_, out):
+    """out: the int16 [S, L] output rows on the device.  Writes DIR/out.npy: float32 rows of `out`, all of them when they fit
+    in DUMP_BYTES, else a seeded (fixed) choice of rows in ascending order; a row longer than the budget keeps its last samples."""
+    S, L = out.shape
+    cols = min(L, DUMP_BYTES // 4)
+    rows = min(S, DUMP_BYTES // (4 * cols))
+    idx = np.arange(S) if rows == S else np.sort(np.random.default_rng(0).choice(S, rows, replace=False))
+    sample = out[idx.tolist()][:, L - cols:].cpu().numpy().astype(np.float32)
+    Path(dir_).mkdir(parents=True, exist_ok=True)
+    np.save(Path(dir_) / "out.npy", sample)
 
 
 def usable_cores() -> int:
@@ -333,9 +354,9 @@ def main():
     ap.add_argument("--fs", type=int, default=16000)
     ap.add_argument("--variant", choices=["fast", "safe"], default="fast")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true", help="skip the CPU re-run of the timed workload (A/B timing loops only)")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: skip the CPU re-run of the timed workload")
     ap.add_argument("--no-live-counters", action="store_true",
-                    help="skip the rocprofv3 counter passes that measure roofline.traffic in this very run (N = 1 only; ~40 s)")
+                    help="with --full: skip the rocprofv3 counter passes that measure roofline.traffic in this very run (N = 1 only; ~40 s)")
     ap.add_argument("--dist-backend", default="nccl", help="torch.distributed backend for the counter gather (nccl = RCCL)")
     ap.add_argument("--share-devices", action="store_true",
                     help="map rank r to HIP device r %% device_count (exercises the N-rank path on a box with fewer GPUs; "
@@ -352,6 +373,10 @@ def main():
     ap.add_argument("--fixed-delay", type=int, default=-1,
                     help="WebRtcAecm_Control fixed delay (>= 0 disables the estimator's choice; 0 = no far-history reads; "
                          "used to calibrate the FETCH_SIZE counter on a known byte count)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the parity check, the CPU baseline, the counter passes and the profile record (off: only the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's output rows (a fixed seeded sample of at most 60 MiB) as DIR/out.npy, float32")
     args = ap.parse_args()
 
     from webrtc_aecm_amd import dist as adist
@@ -428,6 +453,8 @@ def main():
     kernel_ms_total, launches = batch.timers()      # HIP events recorded by the library around every launch, on its stream
     assert launches == K * len(chunks), (launches, K, len(chunks))
     launches = K                            # per step from here on (a step is len(chunks) launches only under --launch-blocks)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     cdev = device if args.dist_backend == "nccl" else torch.device("cpu")
     _form, _detail = batch.describe_launch(C, bool(args.clean))
@@ -435,7 +462,7 @@ def main():
                                                        aecm.device_pci_bus_id(local_rank), _form, _detail)      # (64 bytes travel per rank)
     c = adist.gather_counters(S * T * K, wall, kernel_ms_total, cdev, dev_name)
     parity = None
-    if not args.no_parity:                  # every rank checks streams of its own shard; rank 0 reports, all must agree
+    if args.full and not args.no_parity:    # every rank checks streams of its own shard; rank 0 reports, all must agree
         parity = verify_timed_workload(batch, far, near, clean, out, S, T, W + K, args.fs, args.fixed_delay, timed_passes=K, world=world)
         parity["ranks_ok"] = adist.all_ok(parity["ok"], cdev)
     if rank == 0:
@@ -448,7 +475,7 @@ def main():
         form, chunk = batch.describe_launch(C, bool(args.clean))              # which block kernel a launch of this shape takes
         if args.variant == "fast":
             kernel_substr, kernel_name = isa_census.block_kernel(form, bool(args.clean), chunk)
-            traffic, issue = load_profile_record(aecm.library_path(), workload_key, kernel_substr)
+            traffic, issue = load_profile_record(aecm.library_path(), workload_key, kernel_substr) if args.full else (None, None)
         else:
             kernel_name, traffic, issue = f"aecm_process_kernel<safe,{'clean' if args.clean else 'noclean'}>", None, None
         if args.clean or len(chunks) > 1:                      # the profile record is of the default workload's launch
@@ -493,7 +520,7 @@ def main():
         }
         # roofline.traffic measured in THIS run (N = 1): counter passes over child runs of the same command; the quoted profile record
         # stays beside it (issue_bound: the port-busy fractions need the SQ cycle counters of the full profile)
-        if world == 1 and not args.no_live_counters and not args.no_cpu_baseline and args.variant == "fast":
+        if args.full and world == 1 and not args.no_live_counters and not args.no_cpu_baseline and args.variant == "fast":
             child = ["--streams", str(S), "--blocks", str(T), "--fs", str(args.fs), "--profile", args.profile]
             if args.clean:
                 child.append("--clean")
@@ -519,7 +546,7 @@ def main():
                           "measured_on": None if shares is None else f"{len(parity['streams'])} streams of the timed batch x the {K} timed passes"}
         if parity is not None:
             res["parity"] = parity
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             n_pairs = min(usable_cores(), S, 32)
             pairs = [(far[i].cpu().numpy(), near[i].cpu().numpy()) for i in range(n_pairs)]
             res["cpu_baseline"] = cpu_baseline(args.fs, pairs)

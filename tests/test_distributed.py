@@ -63,7 +63,7 @@ def test_two_rank_gloo_sharded_run_matches_single_process(tmp_path):
 
 
 def test_bench_self_launches_its_ranks(tmp_path):
-    """`python bench.py --gpus 2` without WORLD_SIZE re-executes itself under torch.distributed.run with two ranks
+    """`python bench.py --gpus 2` without WORLD_SIZE starts itself under torch.distributed.run with two ranks
     (the driver's command shape for N = 1 must also work for N > 1).  Without a GPU both ranks get as far as the
     device check (made before the rendezvous, so a bad launch dies in seconds) and say so."""
     import torch

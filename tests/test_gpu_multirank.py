@@ -74,10 +74,10 @@ def test_two_ranks_shard_8192_streams_on_the_hip_library(tmp_path):
 
 
 def test_bench_self_launch_two_ranks_share_one_gpu():
-    """`python bench.py --gpus 2 --share-devices`: started by hand it must re-execute under torch.distributed.run,
+    """`python bench.py --gpus 2 --share-devices`: started by hand it must start itself under torch.distributed.run,
     both ranks must run the HIP engine and the JSON must show ranks_seen == 2 with per-rank rates."""
     r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--share-devices", "--streams", "4096", "--blocks", "64",
-                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], env=_clean_env(), capture_output=True, text=True, timeout=900)
+                        "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--full"], env=_clean_env(), capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
     d = json.loads(line)
@@ -101,7 +101,7 @@ def test_bench_counter_collectives_over_rccl():
     the parity flag travel as device tensors through all-reduce / all-gather -- exactly the calls the 8-GPU run makes."""
     env = dict(_clean_env(), AECM_FORCE_DIST="1", MASTER_PORT="29641")
     d = _bench_json(["--gpus", "1", "--dist-backend", "nccl", "--streams", "4096", "--blocks", "64", "--steps", "3", "--warmup", "1",
-                     "--no-cpu-baseline"], env=env)
+                     "--no-cpu-baseline", "--full"], env=env)
     assert d["ranks"]["collective_backend"] == "nccl" and d["ranks"]["ranks_seen"] == 1 and d["n_gpus"] == 1
     assert len(d["ranks"]["per_rank_device"]) == 1 and "gfx950" in d["ranks"]["per_rank_device"][0]
     assert d["parity"]["ok"] is True and d["parity"]["ranks_ok"] == 1 and d["parity"]["blocks"] == 4 * 64
@@ -112,7 +112,7 @@ def test_bench_strong_scaling_shards_sum_to_the_total():
     """--total-streams splits a fixed total over the ranks (strong scaling): two ranks sharing the GPU own 4096 + 4095 of
     8191 streams, the frames counted are total x blocks x steps, and every rank's timed workload passes its own parity check."""
     d = _bench_json(["--gpus", "2", "--share-devices", "--total-streams", "8191", "--blocks", "64", "--steps", "3", "--warmup", "1",
-                     "--no-cpu-baseline"])
+                     "--no-cpu-baseline", "--full"])
     assert d["scaling"] == "strong" and d["n_gpus"] == 2 and d["ranks"]["ranks_seen"] == 2
     assert d["ranks"]["per_rank_streams"] == [4096, 4095] and sum(d["ranks"]["per_rank_streams"]) == 8191
     assert abs(d["value"] * d["config"]["timed_region_s"] - 8191 * 64 * 3) < 1.0
@@ -123,15 +123,36 @@ def test_bench_eight_ranks_preflight_on_one_gpu():
     """The shape of the driver's 8-GPU run (configs[4]) with the ranks mapped onto the one device present: eight processes
     under torch.distributed.run, eight HIP engines, the counter collectives over eight ranks, every rank's own parity check
     (on its share of the host's cores), weak and strong sharding.  tools/scale_preflight.sh runs the same for N = 2, 4, 8."""
-    d = _bench_json(["--gpus", "8", "--share-devices", "--streams", "1024", "--blocks", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    d = _bench_json(["--gpus", "8", "--share-devices", "--streams", "1024", "--blocks", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                     "--full"],
                     timeout=1500)
     assert d["n_gpus"] == 8 and d["ranks"]["ranks_seen"] == 8 and d["ranks"]["world_size"] == 8
     assert d["ranks"]["per_rank_streams"] == [1024] * 8 and len(set(d["ranks"]["per_rank_device"])) >= 1
     assert d["parity"]["ok"] is True and d["parity"]["ranks_ok"] == 8 and d["parity"]["checker_threads"] >= 1
     assert abs(d["value"] * d["config"]["timed_region_s"] - 8 * 1024 * 64 * 2) < 1.0 and d["scaling"] == "weak"
-    d = _bench_json(["--gpus", "8", "--share-devices", "--total-streams", "8191", "--blocks", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+    d = _bench_json(["--gpus", "8", "--share-devices", "--total-streams", "8191", "--blocks", "64", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
+                     "--full"],
                     timeout=1500)
     assert d["scaling"] == "strong" and d["ranks"]["per_rank_streams"] == [1024] * 7 + [1023] and d["parity"]["ranks_ok"] == 8
+
+
+def test_bench_plain_run_and_output_dump(tmp_path):
+    """A plain run times its steps and adds no parity, CPU-baseline or counter legs; --dump-outputs writes the last step's
+    output rows (4096 x 4096 samples exceed the budget: a seeded choice of 3840 rows), the same from run to run and the same
+    as in a --full run whose parity check passed."""
+    argv = ["--gpus", "1", "--streams", "4096", "--blocks", "64", "--steps", "3", "--warmup", "1"]
+    full = _bench_json(argv + ["--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")])
+    assert full["parity"]["ok"] is True
+    dumps = [np.load(tmp_path / "full" / "out.npy")]
+    for k in range(2):
+        d = _bench_json(argv + ["--dump-outputs", str(tmp_path / f"plain{k}")])
+        assert d["steps"] == 3 and d["value"] > 0 and abs(d["ms_per_step"] * 3 - d["config"]["timed_region_s"] * 1e3) < 1e-6
+        assert not {"parity", "cpu_baseline"} & d.keys() and "live_counters" not in d["roofline"]
+        dumps.append(np.load(tmp_path / f"plain{k}" / "out.npy"))
+    a = dumps[0]
+    assert a.dtype == np.float32 and a.shape == (3840, 64 * 64) and a.nbytes <= 64 << 20
+    assert np.array_equal(a, np.round(a)) and a.min() >= -32768 and a.max() <= 32767 and np.count_nonzero(a)
+    assert all(np.array_equal(a, b) for b in dumps[1:])
 
 
 def test_bench_refuses_more_ranks_than_devices_quickly():

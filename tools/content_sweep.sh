@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R"
 for args in "" "--streams 4096 --blocks 2048" ${CONTENT_SWEEP_EXTRA:+"$CONTENT_SWEEP_EXTRA"} "--streams 1024 --blocks 2048"; do
   for p in recipe always_active double_talk full_scale silent; do
-    timeout 600 python bench.py --no-cpu-baseline --profile $p $args 2>&1 | tail -1 | python -c "
+    timeout 600 python bench.py --full --no-cpu-baseline --profile $p $args 2>&1 | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read())
 c, p = d['content'], d['parity']

@@ -11,7 +11,7 @@ O=gpurun_out
 mkdir -p $O
 ( time AECM_SANITIZER_LOG=$PWD/$O/${T}_ubsan_gpu.log python -m pytest tests -m gpu -x -q --durations=6 ) > $O/${T}_pytest.log 2>&1
 echo "pytest rc=$?" >> $O/${T}_pytest.log
-python bench.py --steps 20 --warmup 5 > $O/${T}_bench.log 2>&1
+python bench.py --full --steps 20 --warmup 5 > $O/${T}_bench.log 2>&1
 PARTS="stats hbm sq cal tick" bash tools/profile_gpu.sh > $O/${T}_profile.log 2>&1
 kernel_of() { python - "$@" <<'PY'
 import sys
@@ -31,7 +31,7 @@ echo "# between the multiples of the CU count (the static placement's sawtooth) 
 python tools/sweep_streams.py --sizes 1025,1100,1152,2049,2100,2176,3073,3150,3200,4097,4200 --blocks 2048 --tolerance 1.0 2>&1 | grep -v "amdgpu.ids\|monotone"
 for a in "--streams 4 --blocks 2048" "--streams 64 --blocks 2048" "--streams 1024 --blocks 2048" "--streams 1536 --blocks 2048" "--streams 2560 --blocks 2048" \
          "--streams 4096 --blocks 2048" "--streams 16384" "--fs 8000 --streams 32768" "--streams 131072 --blocks 512" "--clean" "--variant safe"; do
-  python bench.py --no-cpu-baseline $a | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$a', round(d['value']/1e6,1), 'M frames/s; parity', d['parity']['ok'], ';', d['roofline']['kernel'], ';', d['config']['workload'][:70])"
+  python bench.py --full --no-cpu-baseline $a | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$a', round(d['value']/1e6,1), 'M frames/s; parity', d['parity']['ok'], ';', d['roofline']['kernel'], ';', d['config']['workload'][:70])"
 done
 python bench.py --no-cpu-baseline --no-parity --policy "queue_chunk_blocks=0" | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('one wave per stream (policy queue_chunk_blocks=0)', round(d['value']/1e6,1), 'M frames/s;', d['roofline']['kernel'])"
 python bench.py --no-cpu-baseline --no-parity --streams 4096 --blocks 2048 --policy "pipelined_min_streams=0" | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('4096 streams, one wave per stream (policy pipelined_min_streams=0)', round(d['value']/1e6,1), 'M frames/s;', d['roofline']['kernel'])"

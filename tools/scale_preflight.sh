@@ -1,6 +1,6 @@
 #!/bin/bash
 # Run ON A GPU BOX with fewer GPUs than the scaling run will use: the exact command shape of the driver's N = 2 / 4 / 8 runs
-# (python bench.py --gpus N re-executes itself under torch.distributed.run), with the ranks mapped onto the devices present
+# (python bench.py --gpus N starts itself under torch.distributed.run), with the ranks mapped onto the devices present
 # (--share-devices: gloo for the counter collectives, RCCL refuses two ranks on one device).  Checks per N: every rank took part
 # (ranks_seen), every rank owns its own shard, every rank's timed workload is bit-exact against the CPU checker.
 #   gpurun -- 'bash tools/scale_preflight.sh'
@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 cd "$R"
 rc=0
 for n in ${GPUS:-2 4 8}; do
-  line=$(timeout 900 python bench.py --gpus $n --share-devices --streams ${STREAMS:-2048} --blocks ${BLOCKS:-128} --steps 3 --warmup 1 --no-cpu-baseline 2>&1 | grep '^{' | tail -1)
+  line=$(timeout 900 python bench.py --gpus $n --share-devices --streams ${STREAMS:-2048} --blocks ${BLOCKS:-128} --steps 3 --warmup 1 --no-cpu-baseline --full 2>&1 | grep '^{' | tail -1)
   python - "$n" "$line" <<'PY' || rc=1
 import json, sys
 n, d = int(sys.argv[1]), json.loads(sys.argv[2])

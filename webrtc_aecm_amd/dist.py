@@ -30,9 +30,12 @@ def free_port() -> int:
 
 
 def self_launch(script: str, argv, n_ranks: int):
-    """`python script --gpus N` started by hand (no WORLD_SIZE in the environment): replace this process by
-    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... script argv` -- one rank per GPU of
-    this node, rendezvous on 127.0.0.1.  Does not return."""
+    """`python script --gpus N` started by hand (no WORLD_SIZE in the environment): run
+    `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... script argv` as a child -- one rank per GPU of
+    this node, rendezvous on 127.0.0.1 -- and exit with its status.  Does not return.  A child, not exec: the caller
+    may already have initialised the GPU (device count), and a process holding the device must not replace itself."""
+    import signal
+    import subprocess
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC only on this driver (RCCL needs it)
     env.setdefault("OMP_NUM_THREADS", "1")
@@ -40,7 +43,14 @@ def self_launch(script: str, argv, n_ranks: int):
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), script, *argv]
     sys.stdout.flush()
     sys.stderr.flush()
-    os.execvpe(sys.executable, cmd, env)
+    child = subprocess.Popen(cmd, env=env)
+    signal.signal(signal.SIGTERM, lambda *_: child.terminate())     # torch.distributed.run stops its ranks on SIGTERM
+    try:
+        rc = child.wait()
+    except KeyboardInterrupt:
+        child.send_signal(signal.SIGINT)
+        rc = child.wait()
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def init(backend: str, device_index=None, timeout_s: int = 300):
