@@ -79,6 +79,33 @@ int32_t WebRtcAecmBatch_ProcessRecordings(AecmBatch *b, const int16_t *far_dev, 
 int32_t WebRtcAecmBatch_ProcessRecordingsHost(AecmBatch *b, const int16_t *far_host, const int16_t *near_host,
                                               const int16_t *near_clean_host, int16_t *out_host, int64_t stream_stride,
                                               int32_t samples_per_call, int32_t num_calls, int16_t msInSndCardBuf);
+/* Ragged batches: a corpus of recordings never has one length.
+ * As WebRtcAecmBatch_ProcessBlocks, but stream s runs its first blocks_per_stream_host[s] blocks only (host array, S entries
+ * in [0, num_blocks], read before the call returns; AECM_BAD_PARAMETER_ERROR and nothing changed otherwise).  Its state
+ * afterwards is the state after exactly that many WebRtcAecm_ProcessBlock calls; its out blocks beyond that are not written,
+ * a stream of length 0 is not touched at all.  The device's work is proportional to the SUM of the lengths: large launches are
+ * cut into (chunk, stream) items over the streams still live in each chunk (the chunk queue, below).  Every length equal to
+ * num_blocks is exactly WebRtcAecmBatch_ProcessBlocks.  Asynchronous like it.  The Host form is a convenience for tests and small
+ * batches: it stages S x num_blocks dense rows through pageable copies (a short stream's unused blocks as zeros), runs, copies only
+ * the blocks that were written back into out_host and synchronises; a corpus is fed through device pointers or a registered host buffer. */
+int32_t WebRtcAecmBatch_ProcessBlocksRagged(AecmBatch *b, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                            int16_t *out_dev, int64_t stream_stride, int64_t block_stride, int32_t num_blocks,
+                                            const int32_t *blocks_per_stream_host);
+int32_t WebRtcAecmBatch_ProcessBlocksRaggedHost(AecmBatch *b, const int16_t *far_host, const int16_t *near_host, const int16_t *near_clean_host,
+                                                int16_t *out_host, int64_t stream_stride, int64_t block_stride, int32_t num_blocks,
+                                                const int32_t *blocks_per_stream_host);
+/* As WebRtcAecmBatch_ProcessRecordings(Host): session s makes calls_per_stream_host[s] <= num_calls call pairs (host array, S entries
+ * in [0, num_calls]).  codes_host (S entries, may be NULL): what each session's calls returned (the first non-zero code; 0 for a
+ * session without calls); the function returns 0 or the first non-zero of them.  out rows are 0 from calls * samples_per_call to
+ * num_calls * samples_per_call; a session's state afterwards is the state after its own last call.  A session one of whose calls
+ * returns an error (not the AECM_BAD_PARAMETER_WARNING of an out-of-range msInSndCardBuf) is not run: its row is all zeros, its state
+ * untouched, its code reported; the other sessions run. */
+int32_t WebRtcAecmBatch_ProcessRecordingsRagged(AecmBatch *b, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                                int16_t *out_dev, int64_t stream_stride, int32_t samples_per_call, int32_t num_calls,
+                                                const int32_t *calls_per_stream_host, int16_t msInSndCardBuf, int32_t *codes_host);
+int32_t WebRtcAecmBatch_ProcessRecordingsRaggedHost(AecmBatch *b, const int16_t *far_host, const int16_t *near_host, const int16_t *near_clean_host,
+                                                    int16_t *out_host, int64_t stream_stride, int32_t samples_per_call, int32_t num_calls,
+                                                    const int32_t *calls_per_stream_host, int16_t msInSndCardBuf, int32_t *codes_host);
 int32_t WebRtcAecmBatch_Synchronize(AecmBatch *b);
 
 /* Duration of the most recent timed ProcessBlocks kernel, from HIP events recorded around the launch on
@@ -350,6 +377,20 @@ typedef struct AecmLaunchDescription {
 } AecmLaunchDescription;
 int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
                                              int32_t has_clean_input, AecmLaunchDescription *out);
+/* The same for a ragged launch (WebRtcAecmBatch_ProcessBlocksRagged) of num_streams streams with these lengths, no device needed: form,
+ * chunk and grid as above -- the chunk queue when more streams than the queue's threshold have blocks to run and the longest has at
+ * least two chunks, else one wavefront per stream; never pipelined; every length equal: exactly DescribeLaunchDetail of that length --
+ * plus the queue's item count (*items = sum of ceil(length / chunk); 0 for the other forms), and the sum and the maximum of the
+ * lengths in blocks: the useful work and the critical path.  items / sum_blocks / max_blocks may be NULL. */
+int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                             const int32_t *blocks_per_stream_host, int32_t has_clean_input, AecmLaunchDescription *out,
+                                             int64_t *items, int64_t *sum_blocks, int32_t *max_blocks);
+/* Diagnostics: the plan a ragged chunk-queue launch with chunks of chunk_blocks blocks runs by.  order[num_streams]: the streams by
+ * length, longest first (equal lengths in stream order); *num_chunks = ceil(longest / chunk_blocks); first_item[*num_chunks + 1]
+ * (first_item_capacity entries available): the items of chunk c are the numbers first_item[c] .. first_item[c + 1], item
+ * first_item[c] + r being (chunk c, stream order[r]) -- the streams with more than c * chunk_blocks blocks. */
+int32_t WebRtcAecmBatch_RaggedPlan(int32_t num_streams, const int32_t *blocks_per_stream_host, int32_t chunk_blocks, int32_t *order,
+                                   int32_t *first_item, int32_t first_item_capacity, int32_t *num_chunks);
 int32_t WebRtcAecmSessions_DescribeTick(int32_t num_sessions, int32_t compute_units, AecmLaunchDescription *out);
 /* The HIP device WebRtcAecm_Create (which has no device argument) puts its sessions on from now on; process-wide, default 0. */
 int32_t WebRtcAecm_SetDefaultDevice(int32_t device_id);

@@ -43,6 +43,11 @@ SESSJIT_CASES = [
 ]
 # Far-end bursts (k = 0..3 and 30 WebRtcAecm_BufferFarend calls per WebRtcAecm_Process) + mid-session set_config / InitEchoPath /
 # re-Init at the other rate (tests/helpers.py: call_pattern(bursts=True), reconfiguration_events): (seed, seconds, fs, frame)
+# Ragged batches (WebRtcAecmBatch_ProcessBlocksRagged): (name, streams, n_blocks, fs, first seed) -- stream s runs its first lens[s]
+# blocks (random in [0, n_blocks]; 0, n_blocks and 1 among them) with the configuration tests/helpers.py: stream_config(s) gives it
+RAGGED_CASES = [
+    ("ragged_16k", 48, 200, 16000, 7000),
+]
 SESSBURST_CASES = [
     (15, 3, 16000, 160),
     (16, 3, 8000, 80),
@@ -123,6 +128,24 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, n_calls=n_calls, fs=fs, frame=frame, ms_seq=ms_seq, far_calls=far_calls, out=out,
                             codes=codes, paths=np.stack(r.event_log), sha256=hashlib.sha256(out.tobytes()).hexdigest())
         print("sessburst", seed, fs, frame, sorted(set(codes.tolist())), int(far_calls.sum()), "far calls for", n_calls, "near calls")
+    from helpers import stream_config
+    for name, S, nb, fs, seed0 in RAGGED_CASES:
+        if only and only not in name:
+            continue
+        lens = np.random.RandomState(seed0).randint(0, nb + 1, size=S).astype(np.int32)
+        lens[:3] = (0, nb, 1)
+        seeds = np.arange(seed0, seed0 + S)
+        cfgs = [stream_config(s) for s in range(S)]
+        hashes, digs = [], []
+        for s in range(S):
+            far, near = synth_pair(int(seeds[s]), nb, fs)
+            r = pyoracle.RefCoreStream(fs, *cfgs[s])
+            out = r.process(far[:lens[s] * 64], near[:lens[s] * 64]) if lens[s] else np.zeros(0, np.int16)
+            hashes.append(hashlib.sha256(out.tobytes()).hexdigest())
+            digs.append(r.digest())
+        np.savez_compressed(GOLD / f"{name}.npz", fs=fs, n_blocks=nb, lens=lens, seeds=seeds, cng=np.array([c[0] for c in cfgs]),
+                            echo_mode=np.array([c[1] for c in cfgs]), sha256=np.array(hashes), digests=np.stack(digs))
+        print("ragged", name, S, nb, fs, int(lens.sum()), "blocks")
     if only:
         return
     # 60 s reference-CLI-shaped run: hash only

@@ -32,6 +32,8 @@ def main():
     ap.add_argument("--variant", choices=["fast", "safe"], default="fast")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--chunk", type=int, default=4096, help="streams checked per host round trip")
+    ap.add_argument("--ragged", action="store_true", help="every stream its own length, uniform in [blocks / 4, blocks]: each pass is one "
+                    "WebRtcAecmBatch_ProcessBlocksRagged launch, every stream is checked over its own first blocks (forces --passes 1)")
     a = ap.parse_args()
 
     import torch
@@ -47,7 +49,14 @@ def main():
     batch = aecm.AecmBatch(S, a.fs, cng_mode=a.cng, echo_mode=a.echo_mode, device=0,
                            variant=aecm.KERNEL_FAST if a.variant == "fast" else aecm.KERNEL_SAFE)
     out = torch.empty_like(near)
-    for _ in range(a.passes):
+    lens = None
+    if a.ragged:
+        a.passes = 1
+        lens = np.random.RandomState(a.seed).randint(T // 4, T + 1, size=S).astype(np.int32)
+        lens[0] = T
+        batch.process_ragged_device(far.data_ptr(), near.data_ptr(), out.data_ptr(), far.shape[1], 64, T, lens,
+                                    clean.data_ptr() if clean is not None else None)
+    for _ in range(0 if a.ragged else a.passes):
         batch.process_device(far.data_ptr(), near.data_ptr(), out.data_ptr(), far.shape[1], 64, T,
                              clean.data_ptr() if clean is not None else None)
     batch.synchronize()
@@ -65,13 +74,14 @@ def main():
         def one(k):
             chk = pyoracle.RefCoreStream(a.fs, a.cng, a.echo_mode) if use_ref else pyoracle.OracleStream(a.fs, a.cng, a.echo_mode)
             exp = None
+            n = T if lens is None else int(lens[c0 + k])          # ragged: the stream's own first blocks
             for _ in range(a.passes):
                 if cl is None:
-                    exp = chk.process(f[k], d[k])
+                    exp = chk.process(f[k][:n * 64], d[k][:n * 64])
                 else:
                     exp = np.concatenate([chk.process_block_clean(f[k][b * 64:(b + 1) * 64], d[k][b * 64:(b + 1) * 64],
-                                                                  cl[k][b * 64:(b + 1) * 64]) for b in range(T)])
-            return int(np.count_nonzero(exp != got[k])), bool(np.array_equal(chk.digest(), digests[k]))
+                                                                  cl[k][b * 64:(b + 1) * 64]) for b in range(n)])
+            return int(np.count_nonzero(exp != got[k][:n * 64])), bool(np.array_equal(chk.digest(), digests[k]))
         with ThreadPoolExecutor(max_workers=cores) as ex:
             for k, (nbad, dig_ok) in enumerate(ex.map(one, range(c1 - c0))):
                 if nbad or not dig_ok:
@@ -82,10 +92,12 @@ def main():
                     "digests compared bit for bit",
             "checker": "reference" if use_ref else "port", "streams": S, "blocks_per_pass": T, "passes": a.passes, "fs": a.fs,
             "cng": a.cng, "echo_mode": a.echo_mode, "clean_input": bool(a.clean), "variant": a.variant, "seed": a.seed,
-            "frames_processed_per_side": S * T * a.passes, "samples_compared": S * T * 64, "digests_compared": S,
+            "ragged": bool(a.ragged), "frames_processed_per_side": S * T * a.passes if lens is None else int(lens.sum()),
+            "samples_compared": (S * T if lens is None else int(lens.sum())) * 64, "digests_compared": S,
             "ok": not bad_streams, "mismatching_streams": bad_streams[:32], "mismatching_samples": bad_samples,
             "mismatching_digests": bad_digests, "cpu_cores": cores, "cpu_seconds_wall": round(time.perf_counter() - t0, 1),
-            "launch_form": dict(zip(("form", "chunk_blocks"), batch.describe_launch(T, bool(a.clean)))),      # 2 = chunk queue (include/aecm_batch.h)
+            "launch_form": dict(zip(("form", "chunk_blocks"), batch.describe_launch(T, bool(a.clean)))) if lens is None else
+                           {k: v for k, v in batch.describe_ragged_launch(lens, bool(a.clean)).items() if k in ("form", "chunk_blocks", "items")},      # 2 = chunk queue (include/aecm_batch.h)
             "library": str(aecm.library_path()), "build": _build.build_info()}
     print(json.dumps(line))
     return 0 if not bad_streams else 1

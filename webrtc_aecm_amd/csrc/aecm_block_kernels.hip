@@ -1,6 +1,7 @@
 // The block kernels of the MI355X AECM engine.  One block DSP (BlockEngine, aecm_wave.h) under three launch forms:
 //   aecm_process_kernel            one wavefront per stream for the whole launch (described next)
 //   aecm_process_queue_kernel      launches larger than the chip: (chunk, stream) items claimed in order by a resident grid
+//   aecm_process_ragged_queue_kernel  the same queue for streams of different lengths: items by a host-made plan, longest streams first
 //   aecm_process_pipelined_kernel  launches the chip holds at once: six waves per four streams, transforms one block ahead
 // (aecm_engine.cpp: LaunchBlocks picks by the size of the launch; the forms give identical results.)
 //
@@ -170,6 +171,76 @@ void aecm_process_queue_kernel(StatePtrs st, IoView io, int n_streams, int n_blo
         const int nb = n_blocks - first < chunk_blocks ? n_blocks - first : chunk_blocks;
         typename E::StridedIo sio{io, (int64_t)stream * io.stream_stride + (int64_t)first * io.block_stride};
         E::run_stream_io(st, sio, (int64_t)stream, nb);
+        // every store of the chunk (state, history rows: sc1, written through) has completed before the flag is raised
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __hip_atomic_store(done + stream, chunk + 1u, kQueueRelease, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// ---- the ragged chunk queue: every stream its own number of blocks ---------------------------------------------------
+// A corpus of recordings never has one length.  The work of this launch is the SUM of the streams' lengths, not S x the
+// longest: the host sorts the streams by length, longest first (BuildRaggedPlan, aecm_engine.cpp), so that the streams
+// live in chunk c -- those with more than c x chunk_blocks blocks -- are the ranks [0, live[c]) of that order, and the
+// queue's items are, chunk-major, first_item[c] .. first_item[c] + live[c] (first_item = prefix sums of live).  Behind
+// done[] the control buffer carries the plan (RaggedPlanOffsetWords): len[S], order[S], first_item[n_chunks + 1].
+// A wave claims items from the one counter as above.  Its claims are monotone, so it finds an item's chunk with a cursor
+// that only moves forward (amortised one load per item, no division), takes stream = order[item - first_item[chunk]] and
+// runs min(chunk_blocks, len[stream] - chunk x chunk_blocks) >= 1 blocks.  Streams of length 0 have no item: nothing of
+// theirs is read or written.
+// The hand-over between chunks is the one described above, unchanged (sc1 payload, s_waitcnt, one relaxed flag store;
+// relaxed polls, sc1 loads; AECM_QUEUE_FENCES), and so is the no-deadlock argument: the items are chunk-major and a stream
+// live in chunk c is live in chunk c - 1, so item (c, s) has a larger number than item (c - 1, s) and is claimed after it
+// (one counter).  A wave that finds done[s] < c therefore waits for a wave that HOLDS (c - 1, s): one that is running it,
+// or is itself waiting for (c - 2, s) -- a chain that ends at a chunk 0, which waits for nobody.  Late chunks of a
+// long-tailed batch have fewer live streams than the grid has waves: the surplus waves find the counter exhausted and
+// leave, the tail runs as serially as a stream's chunks depend on each other.  The wait stays bounded and raises *err.
+// (A kernel of its own with the equal-length kernel's item body restated, not a template parameter of that kernel: the
+// headline kernels' instruction streams stay exactly what they were.)
+template <bool kHasClean>
+__global__ __launch_bounds__(64 * kWavesPerWorkgroup)
+__attribute__((amdgpu_waves_per_eu(AECM_WAVES_PER_EU, AECM_MAX_WAVES_PER_EU)))
+void aecm_process_ragged_queue_kernel(StatePtrs st, IoView io, int n_streams, uint32_t n_items, int chunk_blocks, uint32_t *ctl, uint32_t *err) {
+    FillLdsTables<64 * kWavesPerWorkgroup>(st.consts);
+    using E = BlockEngine<Gfx950Wave<true, true, false, true>, kHasClean>;
+    uint32_t *done = ctl + kQueueCtlWords;
+    const uint32_t *len = done + n_streams, *order = len + n_streams, *first_item = order + n_streams;      // written by the host before the launch
+    const uint32_t one_in_lane0 = (threadIdx.x & 63u) == 0 ? 1u : 0u;
+    uint32_t chunk = 0, chunk_first = 0;                                      // the cursor: first_item[chunk] <= every later claim of this wave
+    uint32_t chunk_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)first_item[1]);
+    for (;;) {
+        const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane(
+            (int)__hip_atomic_fetch_add(ctl, one_in_lane0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (item >= n_items) break;
+        if (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) break;
+        while (item >= chunk_end) {                                           // item < n_items = first_item[n_chunks]: stops at a chunk < n_chunks
+            ++chunk;
+            chunk_first = chunk_end;
+            chunk_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)first_item[chunk + 1]);
+        }
+        const uint32_t stream = (uint32_t)__builtin_amdgcn_readfirstlane((int)order[item - chunk_first]);
+        if (stream >= (uint32_t)n_streams) {                                  // not a plan BuildRaggedPlan made: touch nothing
+            __hip_atomic_store(err, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+        if (chunk != 0) {
+            uint32_t polls = 0;
+            while ((uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(done + stream, kQueueAcquire, __HIP_MEMORY_SCOPE_AGENT)) < chunk) {
+                __builtin_amdgcn_s_sleep(16);
+                if (++polls > QueueMaxPolls(chunk_blocks) ||
+                    ((polls & 1023u) == 0 && __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)) {
+                    __hip_atomic_store(err, 1u + stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // every wave leaves at its next claim
+                    return;
+                }
+            }
+        }
+        asm volatile("" ::: "memory");                       // the state loads stay behind the flag
+        const int first = (int)chunk * chunk_blocks;
+        const int left = __builtin_amdgcn_readfirstlane((int)len[stream]) - first;
+        const int nb = left < chunk_blocks ? left : chunk_blocks;
+        if (nb > 0) {
+            typename E::StridedIo sio{io, (int64_t)stream * io.stream_stride + (int64_t)first * io.block_stride};
+            E::run_stream_io(st, sio, (int64_t)stream, nb);
+        }
         // every store of the chunk (state, history rows: sc1, written through) has completed before the flag is raised
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __hip_atomic_store(done + stream, chunk + 1u, kQueueRelease, __HIP_MEMORY_SCOPE_AGENT);
@@ -1033,6 +1104,31 @@ hipError_t LaunchProcessBlocksQueued(const StatePtrs &st, const IoView &io, int 
         hipLaunchKernelGGL((aecm_process_queue_kernel<true>), grid, block, lds, stream, st, io, n_streams, n_blocks, chunk_blocks, n_chunks, ctl, err);
     else
         hipLaunchKernelGGL((aecm_process_queue_kernel<false>), grid, block, lds, stream, st, io, n_streams, n_blocks, chunk_blocks, n_chunks, ctl, err);
+    return hipGetLastError();
+}
+
+// The ragged form's control buffer: the equal-length form's words, then the plan -- len[S], order[S], first_item[n_chunks + 1].
+size_t RaggedPlanOffsetWords(int n_streams) { return (size_t)kQueueCtlWords + (size_t)n_streams; }
+size_t RaggedQueueControlBytes(int n_streams, int n_chunks) {
+    return QueueControlBytes(n_streams) + (2 * (size_t)n_streams + (size_t)n_chunks + 1) * sizeof(uint32_t);
+}
+
+// ctl: RaggedQueueControlBytes of device memory whose plan part the caller has uploaded on `stream` (or will, ahead of this
+// launch); live_streams = streams of non-zero length (the grid never needs more waves than that).
+hipError_t LaunchProcessBlocksRaggedQueued(const StatePtrs &st, const IoView &io, int n_streams, int live_streams, uint32_t n_items, int chunk_blocks,
+                                           int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream) {
+    if (n_streams <= 0 || live_streams <= 0 || n_items == 0 || chunk_blocks <= 0) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(ctl, 0, QueueControlBytes(n_streams), stream);
+    if (e != hipSuccess) return e;
+    const int resident_groups = resident_waves / kWavesPerWorkgroup;
+    const int needed = (live_streams + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup;
+    const dim3 grid(needed < resident_groups ? needed : resident_groups);
+    const dim3 block(64 * kWavesPerWorkgroup);
+    const size_t lds = sizeof(LdsTables);
+    if (io.near_clean != nullptr)
+        hipLaunchKernelGGL((aecm_process_ragged_queue_kernel<true>), grid, block, lds, stream, st, io, n_streams, n_items, chunk_blocks, ctl, err);
+    else
+        hipLaunchKernelGGL((aecm_process_ragged_queue_kernel<false>), grid, block, lds, stream, st, io, n_streams, n_items, chunk_blocks, ctl, err);
     return hipGetLastError();
 }
 

@@ -171,6 +171,65 @@ int32_t WebRtcAecmBatch_ProcessRecordingsHost(AecmBatch *b, const int16_t *far_h
                              msInSndCardBuf, true);
 }
 
+// ---- ragged batches: one length per stream ---------------------------------------------------------------
+static int32_t CheckLengths(const AecmBatch *b, const int32_t *lens, int32_t limit) {
+    if (!lens) return AECM_NULL_POINTER_ERROR;
+    for (int32_t s = 0; s < b->engine->num_streams(); ++s)
+        if (lens[s] < 0 || lens[s] > limit) return AECM_BAD_PARAMETER_ERROR;
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_ProcessBlocksRagged(AecmBatch *b, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                            int16_t *out_dev, int64_t stream_stride, int64_t block_stride, int32_t num_blocks,
+                                            const int32_t *blocks_per_stream_host) {
+    if (int32_t rc = CheckIo(b, far_dev, near_dev, out_dev, num_blocks)) return rc;
+    if (int32_t rc = CheckLengths(b, blocks_per_stream_host, num_blocks)) return rc;
+    if (num_blocks == 0) return 0;
+    aecm::IoView io{far_dev, near_dev, near_clean_dev, out_dev, stream_stride, block_stride};
+    return b->engine->ProcessBlocksRagged(io, num_blocks, blocks_per_stream_host);
+}
+
+int32_t WebRtcAecmBatch_ProcessBlocksRaggedHost(AecmBatch *b, const int16_t *far_host, const int16_t *near_host, const int16_t *near_clean_host,
+                                                int16_t *out_host, int64_t stream_stride, int64_t block_stride, int32_t num_blocks,
+                                                const int32_t *blocks_per_stream_host) {
+    if (int32_t rc = CheckIo(b, far_host, near_host, out_host, num_blocks)) return rc;
+    if (int32_t rc = CheckLengths(b, blocks_per_stream_host, num_blocks)) return rc;
+    if (num_blocks == 0) return 0;
+    aecm::IoView io{far_host, near_host, near_clean_host, out_host, stream_stride, block_stride};
+    return b->engine->ProcessBlocksRaggedHost(io, num_blocks, blocks_per_stream_host);
+}
+
+static int32_t ProcessRecordingsRagged(AecmBatch *b, const int16_t *far_p, const int16_t *near_p, const int16_t *clean_p, int16_t *out_p,
+                                       int64_t stream_stride, int32_t samples_per_call, int32_t num_calls, const int32_t *calls, int16_t ms,
+                                       int32_t *codes, bool host) {
+    if (int32_t rc = CheckIo(b, far_p, near_p, out_p, num_calls)) return rc;
+    if (samples_per_call != 80 && samples_per_call != 160) return AECM_BAD_PARAMETER_ERROR;
+    if (stream_stride < (int64_t)samples_per_call * num_calls) return AECM_BAD_PARAMETER_ERROR;
+    if (int32_t rc = CheckLengths(b, calls, num_calls)) return rc;
+    if (num_calls == 0) {
+        for (int32_t s = 0; codes && s < b->engine->num_streams(); ++s) codes[s] = 0;
+        return 0;
+    }
+    int32_t rc = 0;
+    if (!b->engine->ProcessRecordingsRagged(far_p, near_p, clean_p, out_p, stream_stride, samples_per_call, num_calls, calls, ms, host, &rc, codes))
+        return AECM_UNSPECIFIED_ERROR;
+    return rc;
+}
+
+int32_t WebRtcAecmBatch_ProcessRecordingsRagged(AecmBatch *b, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                                int16_t *out_dev, int64_t stream_stride, int32_t samples_per_call, int32_t num_calls,
+                                                const int32_t *calls_per_stream_host, int16_t msInSndCardBuf, int32_t *codes_host) {
+    return ProcessRecordingsRagged(b, far_dev, near_dev, near_clean_dev, out_dev, stream_stride, samples_per_call, num_calls,
+                                   calls_per_stream_host, msInSndCardBuf, codes_host, false);
+}
+
+int32_t WebRtcAecmBatch_ProcessRecordingsRaggedHost(AecmBatch *b, const int16_t *far_host, const int16_t *near_host, const int16_t *near_clean_host,
+                                                    int16_t *out_host, int64_t stream_stride, int32_t samples_per_call, int32_t num_calls,
+                                                    const int32_t *calls_per_stream_host, int16_t msInSndCardBuf, int32_t *codes_host) {
+    return ProcessRecordingsRagged(b, far_host, near_host, near_clean_host, out_host, stream_stride, samples_per_call, num_calls,
+                                   calls_per_stream_host, msInSndCardBuf, codes_host, true);
+}
+
 int32_t WebRtcAecmBatch_Synchronize(AecmBatch *b) {
     if (!b) return -1;
     return b->engine->Synchronize() ? 0 : AECM_UNSPECIFIED_ERROR;
@@ -378,6 +437,54 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int
         p = aecm::DefaultLaunchPolicy(compute_units);
     }
     DescriptionToAbi(aecm::DescribeLaunchWith(p, aecm::kVariantFast, num_streams, num_blocks, has_clean_input != 0), out);
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                             const int32_t *blocks_per_stream_host, int32_t has_clean_input, AecmLaunchDescription *out,
+                                             int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
+    if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
+    if (num_streams <= 0) return AECM_BAD_PARAMETER_ERROR;
+    aecm::LaunchPolicy p;
+    if (policy) {
+        if (policy->struct_size != (int32_t)sizeof(AecmLaunchPolicy)) return AECM_BAD_PARAMETER_ERROR;
+        p = PolicyFromAbi(*policy);
+        if (!aecm::LaunchPolicyValid(p) || p.compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
+    } else {
+        if (compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
+        p = aecm::DefaultLaunchPolicy(compute_units);
+    }
+    int32_t longest = 0;
+    for (int32_t s = 0; s < num_streams; ++s) {
+        if (blocks_per_stream_host[s] < 0) return AECM_BAD_PARAMETER_ERROR;
+        if (blocks_per_stream_host[s] > longest) longest = blocks_per_stream_host[s];
+    }
+    aecm::RaggedPlan plan;
+    const aecm::LaunchDescription d = aecm::DescribeRaggedLaunchWith(p, aecm::kVariantFast, num_streams, longest, blocks_per_stream_host,
+                                                                     has_clean_input != 0, &plan);
+    if (d.form < 0) return AECM_BAD_PARAMETER_ERROR;
+    DescriptionToAbi(d, out);
+    if (items) *items = d.form == 2 ? plan.items : 0;
+    if (sum_blocks) *sum_blocks = plan.sum_blocks;
+    if (max_blocks) *max_blocks = plan.max_blocks;
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_RaggedPlan(int32_t num_streams, const int32_t *blocks_per_stream_host, int32_t chunk_blocks, int32_t *order,
+                                   int32_t *first_item, int32_t first_item_capacity, int32_t *num_chunks) {
+    if (!blocks_per_stream_host || !order || !first_item || !num_chunks) return AECM_NULL_POINTER_ERROR;
+    if (num_streams <= 0 || chunk_blocks <= 0) return AECM_BAD_PARAMETER_ERROR;
+    int32_t longest = 0;
+    for (int32_t s = 0; s < num_streams; ++s) {
+        if (blocks_per_stream_host[s] < 0) return AECM_BAD_PARAMETER_ERROR;
+        if (blocks_per_stream_host[s] > longest) longest = blocks_per_stream_host[s];
+    }
+    aecm::RaggedPlan plan;
+    if (!aecm::BuildRaggedPlan(blocks_per_stream_host, num_streams, longest, chunk_blocks, &plan)) return AECM_BAD_PARAMETER_ERROR;
+    if (plan.items >= (int64_t(1) << 31) || first_item_capacity < plan.n_chunks + 1) return AECM_BAD_PARAMETER_ERROR;
+    *num_chunks = plan.n_chunks;
+    for (int32_t s = 0; s < num_streams; ++s) order[s] = (int32_t)plan.order()[s];
+    for (int32_t c = 0; c <= plan.n_chunks; ++c) first_item[c] = (int32_t)plan.first_item()[c];
     return 0;
 }
 

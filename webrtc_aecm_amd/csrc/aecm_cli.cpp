@@ -6,7 +6,7 @@
 //                                        result in <near>_out<ext>, tail beyond the last full call untouched
 //   aecm_run --batch list.txt            many pairs at once (one "far.wav near.wav" per line): all
 //                                        recordings of one sample rate are processed as one device batch
-//                                        (WebRtcAecmBatch_ProcessRecordingsHost), one wavefront per file
+//                                        (WebRtcAecmBatch_ProcessRecordingsRaggedHost: every file its own length)
 //   aecm_run --decode in.wav out.wav     read in.wav the way the pair modes do and write it back as 16-bit PCM
 //                                        (which sample formats are read, and how they become int16: ReadWav)
 // RIFF/WAVE reader for the sample formats the reference CLI accepts, 16-bit PCM writer (the reference uses dr_wav.h for
@@ -249,7 +249,10 @@ int RunBatch(const char *list_path, const std::vector<int> &devices) {
         const size_t n_dev = devices.size();
         std::vector<int32_t> shard_rc(n_dev, 0);
         std::vector<double> shard_s(n_dev, 0.0);              // per device: seconds in the library, recordings, WebRtcAecm_ProcessBlock-equivalents
-        std::vector<size_t> shard_n(n_dev, 0);
+        std::vector<size_t> shard_n(n_dev, 0), shard_frames(n_dev, 0);
+        // every recording its own call count: the padding behind a short recording is not processed (WebRtcAecmBatch_ProcessRecordingsRaggedHost)
+        std::vector<int32_t> calls(ids.size());
+        for (size_t k = 0; k < ids.size(); ++k) calls[k] = (int32_t)(jobs[ids[k]].near_w.samples.size() / frame);
         std::vector<std::thread> workers;
         for (size_t d = 0; d < n_dev; ++d) {
             const size_t base = ids.size() / n_dev, rem = ids.size() % n_dev;
@@ -265,9 +268,10 @@ int RunBatch(const char *list_path, const std::vector<int> &devices) {
                 int32_t rc = WebRtcAecmBatch_Init(batch, (int32_t)rate);
                 if (rc == 0) rc = WebRtcAecmBatch_set_config(batch, cfg, 0, -1);
                 if (rc == 0)
-                    rc = WebRtcAecmBatch_ProcessRecordingsHost(batch, &far_all[first * stride], &near_all[first * stride], /*nearendClean*/ nullptr,
-                                                               &out_all[first * stride], (int64_t)stride, frame, (int32_t)max_calls,
-                                                               kMsInSndCardBuf);
+                    rc = WebRtcAecmBatch_ProcessRecordingsRaggedHost(batch, &far_all[first * stride], &near_all[first * stride], /*nearendClean*/ nullptr,
+                                                                     &out_all[first * stride], (int64_t)stride, frame, (int32_t)max_calls,
+                                                                     &calls[first], kMsInSndCardBuf, /*codes*/ nullptr);
+                for (size_t k = first; k < first + count; ++k) shard_frames[d] += (size_t)calls[k] * frame / 64;
                 shard_s[d] = std::chrono::duration<double>(std::chrono::steady_clock::now() - s0).count();
                 shard_n[d] = count;
                 WebRtcAecmBatch_Free(batch);
@@ -282,8 +286,8 @@ int RunBatch(const char *list_path, const std::vector<int> &devices) {
         // the counters of the shards, gathered where the threads join (no collective needed inside one process)
         for (size_t d = 0; d < n_dev; ++d)
             if (shard_n[d] != 0)
-                printf("device %d: %zu recordings at %u Hz, %zu frames of 64 samples each, %.3f s in the library (%.2f M frames/s)\n", devices[d], shard_n[d], rate,
-                       stride / 64, shard_s[d], shard_s[d] > 0 ? (double)shard_n[d] * (double)(stride / 64) / shard_s[d] / 1e6 : 0.0);
+                printf("device %d: %zu recordings at %u Hz, %zu frames of 64 samples processed (the longest recording: %zu), %.3f s in the library (%.2f M frames/s)\n",
+                       devices[d], shard_n[d], rate, shard_frames[d], stride / 64, shard_s[d], shard_s[d] > 0 ? (double)shard_frames[d] / shard_s[d] / 1e6 : 0.0);
         for (size_t k = 0; k < ids.size(); ++k) {
             Job &j = jobs[ids[k]];
             const size_t n = (j.near_w.samples.size() / frame) * frame;      // tail stays untouched (main.cc:111)

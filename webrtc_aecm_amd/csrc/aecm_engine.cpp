@@ -120,6 +120,8 @@ BatchEngine::~BatchEngine() {
     (void)hipFree(consts_dev_);
     (void)hipFree(queue_ctl_);
     (void)hipFree(queue_err_);
+    if (plan_host_) (void)hipHostFree(plan_host_);
+    if (plan_uploaded_) (void)hipEventDestroy(plan_uploaded_);
     (void)hipFree(stage_dev_);
     if (mapped_host_) (void)hipHostFree(mapped_host_);
     (void)hipFree(rec_maps_);
@@ -308,6 +310,86 @@ LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int cou
     return d;
 }
 
+// The plan of a ragged launch (aecm_engine.h: RaggedPlan; read by aecm_process_ragged_queue_kernel).  A counting sort by length --
+// O(S + num_blocks), stable, longest first -- so that a plan for 65 536 streams costs well under a millisecond of host time.
+bool BuildRaggedPlan(const int32_t *lens, int S, int num_blocks, int chunk_blocks, RaggedPlan *plan) {
+    RaggedPlan &p = *plan;
+    p = RaggedPlan();
+    if (S < 0 || num_blocks < 0) return false;
+    p.num_streams = S;
+    p.chunk_blocks = chunk_blocks > 0 ? chunk_blocks : 0;
+    std::vector<uint32_t> at((size_t)num_blocks + 2, 0u);       // at[l]: streams longer than l, i.e. the rank of the first stream of length l
+    for (int s = 0; s < S; ++s) {
+        const int32_t l = lens[s];
+        if (l < 0 || l > num_blocks) return false;
+        at[l] += 1;
+        p.sum_blocks += l;
+        p.max_blocks = std::max(p.max_blocks, (int)l);
+        if (l > 0) {
+            p.live_streams += 1;
+            if (p.chunk_blocks) p.items += (l + p.chunk_blocks - 1) / p.chunk_blocks;
+        }
+    }
+    p.n_chunks = p.chunk_blocks ? (p.max_blocks + p.chunk_blocks - 1) / p.chunk_blocks : 0;
+    const bool with_items = p.items < (int64_t(1) << 31);
+    p.words.assign(2 * (size_t)S + (with_items ? (size_t)p.n_chunks + 1 : 1), 0u);
+    uint32_t longer = 0;                                          // counts -> ranks: exclusive suffix sums
+    for (int l = num_blocks; l >= 0; --l) {
+        const uint32_t n = at[l];
+        at[l] = longer;
+        longer += n;
+    }
+    uint32_t *len = p.words.data(), *order = len + S, *first_item = order + S;
+    if (with_items)                                               // live[c] = streams longer than c x chunk = the rank of the first stream of that length or less
+        for (int c = 0; c < p.n_chunks; ++c) first_item[c + 1] = first_item[c] + at[(size_t)c * p.chunk_blocks];
+    for (int s = 0; s < S; ++s) {
+        len[s] = (uint32_t)lens[s];
+        order[at[lens[s]]++] = (uint32_t)s;
+    }
+    return true;
+}
+
+LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, const int32_t *lens, bool has_clean,
+                                           RaggedPlan *plan_out) {
+    RaggedPlan local;
+    RaggedPlan &plan = plan_out ? *plan_out : local;
+    LaunchDescription d;
+    // one pass over the lengths decides the form; the plan is then built once, with the chunk that form runs by
+    int live = 0, longest = 0;
+    int64_t sum = 0;
+    bool valid = count >= 0 && num_blocks >= 0 && (lens || count == 0);
+    for (int s = 0; valid && s < count; ++s) {
+        valid = lens[s] >= 0 && lens[s] <= num_blocks;
+        live += lens[s] > 0;
+        longest = std::max(longest, (int)lens[s]);
+        sum += lens[s];
+    }
+    if (!valid) { d.form = -1; return d; }
+    int chunk = 0;
+    if (longest == 0) {
+        // nothing to launch
+    } else if (sum == (int64_t)count * longest) {                 // every stream the same length: the equal-length launch, whatever its form
+        d = DescribeLaunchWith(p, variant, count, longest, has_clean);
+        chunk = d.form == 2 ? d.chunk_blocks : 0;                 // (the plan then tells the caller the queue's item count)
+    } else {
+        chunk = QueueChunkFor(p, live);
+        int64_t items = 0;
+        if (chunk > 0 && variant == kVariantFast && live > QueueMinStreams(p) && longest >= 2 * chunk)
+            for (int s = 0; s < count; ++s) items += (lens[s] + chunk - 1) / chunk;
+        if (items == 0 || items >= (int64_t(1) << 31)) chunk = 0;
+        // the queue over the live streams, or one wavefront per stream of the whole range, each with its own count (a wave of a
+        // zero-length stream leaves at once): the grid arithmetic is the equal-length launch's with the queue's threshold taken or refused
+        LaunchPolicy q = p;
+        q.pipelined_min_streams = 0x7fffffff;
+        q.queue_chunk_blocks = chunk;
+        q.queue_chunk_explicit = true;
+        q.queue_min_streams = 0;
+        d = DescribeLaunchWith(q, variant, chunk ? live : count, longest, has_clean);
+    }
+    BuildRaggedPlan(lens, count, num_blocks, chunk, &plan);
+    return d;
+}
+
 // A tick of a session batch (aecm_kernels.hip: aecm_tick_flow_kernel): one wavefront per session, four per workgroup, seven such
 // workgroups per CU -- 65 536 sessions on 256 CUs are 16 384 workgroups on 1 792 places: 9.14 rounds, the last one 14 % full.
 LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units) {
@@ -321,8 +403,57 @@ LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units) {
     return d;
 }
 
-bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev) {
+// The plan travels through a pinned buffer of the engine's, so the copy is asynchronous and the caller's (and the plan's) memory is
+// free when this returns; the buffer is reused once the previous upload has run.
+// (Grown, and the event created, on first use -- by ProcessBlocksRaggedRange ahead of the launch's timing events, so that no
+// allocation falls between them.  Growing waits for the previous upload: the old buffer may still be read.)
+bool BatchEngine::EnsurePlanStaging(size_t words) {
+    if (words > plan_host_words_) {
+        if (plan_upload_pending_) {
+            if (!AECM_HIP_OK(hipEventSynchronize(plan_uploaded_))) return false;
+            plan_upload_pending_ = false;
+        }
+        if (plan_host_) (void)hipHostFree(plan_host_);
+        plan_host_ = nullptr;
+        plan_host_words_ = 0;
+        if (!AECM_HIP_OK(hipHostMalloc((void **)&plan_host_, words * sizeof(uint32_t), hipHostMallocDefault))) return false;
+        plan_host_words_ = words;
+    }
+    return plan_uploaded_ || AECM_HIP_OK(hipEventCreateWithFlags(&plan_uploaded_, hipEventDisableTiming));
+}
+
+bool BatchEngine::UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev) {
+    const size_t words = plan.words.size();
+    if (plan_upload_pending_) {
+        if (!AECM_HIP_OK(hipEventSynchronize(plan_uploaded_))) return false;
+        plan_upload_pending_ = false;
+    }
+    if (!EnsurePlanStaging(words)) return false;
+    memcpy(plan_host_, plan.words.data(), words * sizeof(uint32_t));
+    if (!AECM_HIP_OK(hipMemcpyAsync(dst_dev, plan_host_, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream_))) return false;
+    if (!AECM_HIP_OK(hipEventRecord(plan_uploaded_, stream_))) return false;
+    plan_upload_pending_ = true;
+    return true;
+}
+
+bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev,
+                               const RaggedPlan *ragged, int ragged_form) {
     if (launch_failed_) return false;                 // streams half processed by an abandoned launch: nothing runs until Init
+    if (ragged) {
+        // one upload per launch, on the engine's stream, behind the control words the queue form clears: the whole plan for the queue,
+        // for one wavefront per stream its first part (the lengths) is what aecm_process_kernel reads
+        if (!EnsureLaunchControl(RaggedQueueControlBytes(count, ragged->n_chunks))) return false;
+        uint32_t *plan_dev = queue_ctl_ + RaggedPlanOffsetWords(count);
+        if (!UploadRaggedPlan(*ragged, plan_dev)) return false;
+        if (ragged_form == 2) {
+            if (!EnsureLaunchErrorWord()) return false;
+            queue_unchecked_ = true;
+            return AECM_HIP_OK(LaunchProcessBlocksRaggedQueued(st, io, count, ragged->live_streams, (uint32_t)ragged->items, ragged->chunk_blocks,
+                                                               policy_.resident_waves, queue_ctl_, queue_err_, stream_));
+        }
+        return AECM_HIP_OK(LaunchProcessBlocks(st, io, count, num_blocks, variant_, policy_.rotation_stream_limit, stream_,
+                                               reinterpret_cast<const int32_t *>(plan_dev)));
+    }
     const int chunk = QueueChunkFor(policy_, count);
     if (QueueLaunchApplies(count, num_blocks, variant_, chunk, QueueMinStreams(policy_), blocks_per_stream_dev != nullptr)) {
         if (!EnsureLaunchControl(QueueControlBytes(count))) return false;
@@ -386,6 +517,70 @@ bool BatchEngine::ProcessBlocks(const IoView &io, int num_blocks, const int32_t 
 
 // Streams [first, first + count); io (and blocks_per_stream_dev) are indexed from `first`.
 bool BatchEngine::ProcessBlocksRange(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev) {
+    return TimedLaunch(io, num_blocks, first, count, blocks_per_stream_dev, nullptr, 0);
+}
+
+int32_t BatchEngine::ProcessBlocksRagged(const IoView &io, int num_blocks, const int32_t *blocks_per_stream_host) {
+    return ProcessBlocksRaggedRange(io, num_blocks, 0, num_streams_, blocks_per_stream_host);
+}
+
+int32_t BatchEngine::ProcessBlocksRaggedRange(const IoView &io, int num_blocks, int first, int count, const int32_t *lens) {
+    if (first < 0 || count < 0 || first + count > num_streams_ || num_blocks < 0 || !lens) return kErrBadParameter;
+    RaggedPlan plan;
+    const LaunchDescription d = DescribeRaggedLaunchWith(policy_, variant_, count, num_blocks, lens, io.near_clean != nullptr, &plan);
+    if (d.form < 0) return kErrBadParameter;
+    if (plan.max_blocks == 0) return 0;
+    if (plan.sum_blocks == (int64_t)count * plan.max_blocks)          // every stream the same length: today's launch, whatever its form
+        return TimedLaunch(io, plan.max_blocks, first, count, nullptr, nullptr, 0) ? 0 : kErrUnspecified;
+    if (!AECM_HIP_OK(hipSetDevice(device_)) || !EnsureLaunchControl(RaggedQueueControlBytes(count, plan.n_chunks)) ||
+        !EnsurePlanStaging(plan.words.size()))
+        return kErrUnspecified;
+    return TimedLaunch(io, plan.max_blocks, first, count, nullptr, &plan, d.form) ? 0 : kErrUnspecified;
+}
+
+// Host audio: the live blocks are packed into dense device rows, run, and the blocks that were written are copied back.
+int32_t BatchEngine::ProcessBlocksRaggedHost(const IoView &io, int num_blocks, const int32_t *lens) {
+    if (num_blocks < 0 || !lens) return kErrBadParameter;
+    for (int s = 0; s < num_streams_; ++s)
+        if (lens[s] < 0 || lens[s] > num_blocks) return kErrBadParameter;
+    if (num_blocks == 0) return 0;
+    if (!AECM_HIP_OK(hipSetDevice(device_))) return kErrUnspecified;
+    const size_t row = (size_t)num_blocks * kBlock, per = (size_t)num_streams_ * row;
+    const int n_in = io.near_clean ? 3 : 2;
+    const size_t need = per * (n_in + 1);
+    if (need > stage_elems_) {
+        if (!AECM_HIP_OK(hipStreamSynchronize(stream_))) return kErrUnspecified;
+        (void)hipFree(stage_dev_);
+        stage_dev_ = nullptr;
+        stage_elems_ = 0;
+        if (!AECM_HIP_OK(hipMalloc((void **)&stage_dev_, need * sizeof(int16_t)))) return kErrUnspecified;
+        stage_elems_ = need;
+    }
+    std::vector<int16_t> tmp(per, 0);
+    auto upload = [&](const int16_t *src, int16_t *dst) -> bool {
+        for (int s = 0; s < num_streams_; ++s)
+            for (int b = 0; b < lens[s]; ++b)
+                memcpy(&tmp[(size_t)s * row + (size_t)b * kBlock], src + s * io.stream_stride + b * io.block_stride, kBlock * sizeof(int16_t));
+        return AECM_HIP_OK(hipMemcpy(dst, tmp.data(), per * sizeof(int16_t), hipMemcpyHostToDevice));
+    };
+    IoView dev{stage_dev_, stage_dev_ + per, io.near_clean ? stage_dev_ + 2 * per : nullptr, stage_dev_ + (size_t)n_in * per, (int64_t)row, kBlock};
+    if (!upload(io.far, const_cast<int16_t *>(dev.far)) || !upload(io.near, const_cast<int16_t *>(dev.near)) ||
+        (io.near_clean && !upload(io.near_clean, const_cast<int16_t *>(dev.near_clean))))
+        return kErrUnspecified;
+    if (const int32_t rc = ProcessBlocksRagged(dev, num_blocks, lens)) return rc;
+    if (!AECM_HIP_OK(hipMemcpyAsync(tmp.data(), dev.out, per * sizeof(int16_t), hipMemcpyDeviceToHost, stream_))) {
+        (void)Drain();                                                // tmp goes out of scope
+        return kErrUnspecified;
+    }
+    if (!Drain()) return kErrUnspecified;
+    for (int s = 0; s < num_streams_; ++s)
+        for (int b = 0; b < lens[s]; ++b)
+            memcpy(io.out + s * io.stream_stride + b * io.block_stride, &tmp[(size_t)s * row + (size_t)b * kBlock], kBlock * sizeof(int16_t));
+    return 0;
+}
+
+bool BatchEngine::TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged,
+                              int ragged_form) {
     if (first < 0 || count < 0 || first + count > num_streams_) return false;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
     if (!HarvestTimers(false)) return false;
@@ -399,7 +594,7 @@ bool BatchEngine::ProcessBlocksRange(const IoView &io, int num_blocks, int first
     st.vec += (size_t)first * kVecWordsPerStream;
     st.scal += (size_t)first * kNumScal;
     st.hist += (size_t)first * kHistWordsPerStream;
-    if (!LaunchBlocks(st, io, count, num_blocks, blocks_per_stream_dev)) return false;
+    if (!LaunchBlocks(st, io, count, num_blocks, blocks_per_stream_dev, ragged, ragged_form)) return false;
     if (!AECM_HIP_OK(hipEventRecord(ev_stop_[slot], stream_))) return false;
     ++timer_pending_;
     return true;
@@ -580,11 +775,43 @@ bool BatchEngine::EnsureRecordingScratch(size_t map_elems, size_t sample_elems) 
 
 bool BatchEngine::ProcessRecordings(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out,
                                     int64_t stream_stride, int frame, int n_calls, int16_t ms, bool host_pointers, int32_t *rc) {
+    return ProcessRecordingsRagged(far, near, clean, out, stream_stride, frame, n_calls, nullptr, ms, host_pointers, rc, nullptr);
+}
+
+// calls (may be null: every stream makes n_calls calls): the schedule of a session of k calls is the prefix of the schedule of n_calls
+// calls, so stream s runs the first blocks_after_call[calls[s] - 1] blocks of the common schedule (a ragged launch) and its
+// output is assembled up to calls[s] * frame samples, zeros behind.  The gathers stay full-width.
+bool BatchEngine::ProcessRecordingsRagged(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride,
+                                          int frame, int n_calls, const int32_t *calls, int16_t ms, bool host_pointers, int32_t *rc,
+                                          int32_t *codes) {
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
     if (mixed_rates_) { *rc = kErrUnsupported; return true; }        // an imported stream runs at another rate than fs_
     const RecordingSchedule sch = BuildRecordingSchedule(fs_, frame, n_calls, ms);
-    if (sch.first_error) { *rc = sch.first_error; return true; }
-    *rc = sch.warned ? kWarnBadParameter : 0;
+    std::vector<int32_t> lens, limits;                                // per stream: blocks to run, output samples to assemble
+    if (calls) {
+        if ((int)sch.blocks_after_call.size() != n_calls) {           // the session could not even be initialised: every call returns that
+            *rc = sch.first_error;
+            for (int s = 0; codes && s < num_streams_; ++s) codes[s] = calls[s] > 0 ? sch.first_error : 0;
+            return true;
+        }
+        *rc = 0;
+        lens.resize(num_streams_);
+        limits.resize(num_streams_);
+        for (int s = 0; s < num_streams_; ++s) {
+            const int k = calls[s];
+            lens[s] = k > 0 ? sch.blocks_after_call[k - 1] : 0;
+            limits[s] = k * frame;
+            const int32_t code = k > 0 ? sch.code_after_call[k - 1] : 0;
+            if (codes) codes[s] = code;
+            if (*rc == 0) *rc = code;
+            // a session one of whose calls failed (not the 12100 warning) is not run at all: its row is written as zeros and its
+            // state stays as it was; the sessions that end before the failing call run as usual
+            if (code != 0 && code != kWarnBadParameter) lens[s] = limits[s] = 0;
+        }
+    } else {
+        if (sch.first_error) { *rc = sch.first_error; return true; }
+        *rc = sch.warned ? kWarnBadParameter : 0;
+    }
     const int64_t n_in = (int64_t)n_calls * frame, n_blk = (int64_t)sch.n_blocks * kBlock;
     const int n_near = clean ? 2 : 1;      // the clean near-end follows the near-end's schedule sample for sample
     // Device scratch per stream: gathered far/near(/clean) blocks + block outputs (+ staged I/O for host pointers).
@@ -598,10 +825,12 @@ bool BatchEngine::ProcessRecordings(const int16_t *far, const int16_t *near, con
     chunk = std::min<int64_t>(chunk, 0x7fffffffll / tiles);
     chunk = std::min<int64_t>(chunk, num_streams_);
     const size_t map_elems = std::max<size_t>((size_t)(2 * n_blk + n_in), 1);
-    if (!EnsureRecordingScratch(map_elems, (size_t)chunk * per_stream)) return false;
+    if (!EnsureRecordingScratch(map_elems + (calls ? (size_t)num_streams_ : 0), (size_t)chunk * per_stream)) return false;
     int32_t *maps = rec_maps_;
+    int32_t *limits_dev = calls ? rec_maps_ + map_elems : nullptr;
     bool ok = true;
-    if (n_blk > 0) {
+    if (calls) ok = AECM_HIP_OK(hipMemcpyAsync(limits_dev, limits.data(), limits.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    if (ok && n_blk > 0) {
         ok = AECM_HIP_OK(hipMemcpyAsync(maps, sch.far_map.data(), n_blk * sizeof(int32_t), hipMemcpyHostToDevice, stream_)) &&
              AECM_HIP_OK(hipMemcpyAsync(maps + n_blk, sch.near_map.data(), n_blk * sizeof(int32_t), hipMemcpyHostToDevice, stream_));
     }
@@ -631,13 +860,14 @@ bool BatchEngine::ProcessRecordings(const int16_t *far, const int16_t *near, con
                  (!clean || AECM_HIP_OK(LaunchGatherByMap(dclean, dstride, maps + n_blk, n_blk, bclean, n_blk, (int)C, stream_)));
             if (ok) {
                 IoView io{bfar, bnear, clean ? bclean : nullptr, bout, n_blk, kBlock};
-                ok = ProcessBlocksRange(io, sch.n_blocks, (int)s0, (int)C, nullptr);
+                ok = calls ? ProcessBlocksRaggedRange(io, sch.n_blocks, (int)s0, (int)C, lens.data() + s0) == 0
+                           : ProcessBlocksRange(io, sch.n_blocks, (int)s0, (int)C, nullptr);
             }
         }
         // pass-through samples of the start-up phase come from the clean near-end when there is one
         // (reference echo_control_mobile.cc:285-291)
         if (ok) ok = AECM_HIP_OK(LaunchAssembleOutput(bout, n_blk, clean ? dclean : dnear, dstride, maps + 2 * n_blk, n_in, dout, dstride,
-                                                      (int)C, stream_));
+                                                      (int)C, stream_, calls ? limits_dev + s0 : nullptr));
         if (ok && host_pointers)
             ok = AECM_HIP_OK(hipMemcpy2DAsync(out + s0 * stream_stride, stream_stride * 2, dout, n_in * 2, n_in * 2, C,
                                               hipMemcpyDeviceToHost, stream_));

@@ -5,6 +5,8 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "aecm_host_state.h"
 #include "aecm_kernels.h"
 #include "aecm_state.h"
@@ -46,6 +48,32 @@ struct LaunchDescription {
 LaunchDescription DescribeLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, bool has_clean);
 LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units);
 
+// A ragged launch: stream s runs len[s] blocks.  Pure host logic (no device), so that it can be tested and used for planning.
+// The streams sorted by length, longest first (stable: equal lengths keep their stream order), make the streams live in chunk c --
+// those with more than c x chunk_blocks blocks -- the ranks [0, live[c]); the queue's items are chunk-major, those of chunk c the
+// numbers first_item[c] .. first_item[c] + live[c], item first_item[c] + r = (chunk c, stream order[r]).
+struct RaggedPlan {
+    int num_streams = 0, chunk_blocks = 0, n_chunks = 0;
+    int live_streams = 0;             // streams of non-zero length (live[0])
+    int max_blocks = 0;               // the longest stream: the launch's critical path
+    int64_t sum_blocks = 0;           // the useful work
+    int64_t items = 0;                // sum over the streams of ceil(len / chunk_blocks)
+    // what the kernel reads (aecm_kernels.h: RaggedPlanOffsetWords): len[S], order[S], first_item[n_chunks + 1]
+    // (first_item only when the items fit 31 bits; without a chunk -- chunk_blocks <= 0 -- n_chunks = 0 and first_item = {0})
+    std::vector<uint32_t> words;
+    const uint32_t *len() const { return words.data(); }
+    const uint32_t *order() const { return words.data() + num_streams; }
+    const uint32_t *first_item() const { return words.data() + 2 * (size_t)num_streams; }
+};
+// false: a length outside [0, num_blocks] (the plan is then not usable).
+bool BuildRaggedPlan(const int32_t *blocks_per_stream, int num_streams, int num_blocks, int chunk_blocks, RaggedPlan *plan);
+// Which form a ragged launch takes under a policy; *plan_out (may be null) receives the plan it would run with.  Every length equal:
+// exactly DescribeLaunchWith of that length.  Otherwise the chunk queue when the fast variant is selected, more than queue_min_streams
+// streams are live, the longest stream has at least two chunks and the items fit 31 bits; else one wavefront per stream, each with its
+// own block count.  Never pipelined.  form < 0: a length outside [0, num_blocks].
+LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, const int32_t *blocks_per_stream,
+                                           bool has_clean, RaggedPlan *plan_out);
+
 class BatchEngine {
 public:
     // Returns nullptr if the device cannot be used or memory cannot be allocated.
@@ -68,6 +96,21 @@ public:
     bool ProcessBlocks(const IoView &io_dev, int num_blocks, const int32_t *blocks_per_stream_dev = nullptr);
     bool ProcessBlocksRange(const IoView &io_dev, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev);
     bool ProcessBlocksHost(const IoView &io_host, int num_blocks);     // sync
+    // Ragged launches: stream s runs its first blocks_per_stream_host[s] blocks only (host array, read before the call returns;
+    // the Range form's array and io are indexed from `first`).  Its state afterwards is the state after exactly that many blocks,
+    // its out blocks beyond that are not written.  Every length equal to num_blocks: exactly ProcessBlocks.  async like ProcessBlocks.
+    // Returns 0, kErrBadParameter (a length outside [0, num_blocks] or a bad range: nothing changed) or kErrUnspecified (HIP).
+    int32_t ProcessBlocksRagged(const IoView &io_dev, int num_blocks, const int32_t *blocks_per_stream_host);
+    int32_t ProcessBlocksRaggedRange(const IoView &io_dev, int num_blocks, int first, int count, const int32_t *blocks_per_stream_host);
+    int32_t ProcessBlocksRaggedHost(const IoView &io_host, int num_blocks, const int32_t *blocks_per_stream_host);     // sync; stages the live blocks
+    // ProcessRecordings with one call count per stream (host array, entries in [0, n_calls]): stream s is a session of
+    // calls_per_stream_host[s] call pairs; its out samples from calls x frame to n_calls x frame are written as 0.
+    // codes_host (may be null): what each session's calls returned (first non-zero); *rc = the first non-zero of them.
+    bool ProcessRecordingsRagged(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, int frame,
+                                 int n_calls, const int32_t *calls_per_stream_host, int16_t ms, bool host_pointers, int32_t *rc, int32_t *codes_host);
+    LaunchDescription DescribeRaggedLaunch(int num_blocks, const int32_t *blocks_per_stream_host, bool has_clean, RaggedPlan *plan_out) const {
+        return DescribeRaggedLaunchWith(policy_, variant_, num_streams_, num_blocks, blocks_per_stream_host, has_clean, plan_out);
+    }
     // Whole recordings as sessions: every stream is driven like a fresh WebRtcAecm_* session by
     // n_calls x (BufferFarend, Process) of `frame` samples with a constant msInSndCardBuf
     // (aecm_session_flow.h).  far/near/clean/out: [S][>= n_calls*frame], device (or host) pointers; clean
@@ -123,7 +166,18 @@ private:
     size_t queue_ctl_bytes_ = 0;
     bool queue_unchecked_ = false;       // a queue launch has been enqueued since the error word was last read
     bool launch_failed_ = false;         // a wave of a queue launch gave up: sticky until Init (CheckQueueError)
-    bool LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev);
+    // ragged (may be null): the plan of a ragged launch and the form DescribeRaggedLaunchWith gave it; num_blocks is then its longest stream
+    bool LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev,
+                      const RaggedPlan *ragged = nullptr, int ragged_form = 0);
+    bool TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged, int ragged_form);
+    // The plan's way to the device: a pinned staging buffer (grown on first use) and the event behind its last upload -- the
+    // buffer is rewritten only when that copy has run, so ragged launches queue back to back like the others.
+    uint32_t *plan_host_ = nullptr;
+    size_t plan_host_words_ = 0;
+    hipEvent_t plan_uploaded_ = nullptr;
+    bool plan_upload_pending_ = false;
+    bool EnsurePlanStaging(size_t words);
+    bool UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev);
     bool CheckQueueError();
     bool Drain();
     bool EnsureLaunchErrorWord();

@@ -37,6 +37,13 @@ bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_bloc
 hipError_t LaunchProcessBlocksQueued(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, int chunk_blocks,
                                      int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
 int ResidentWaves(int compute_units);
+// The ragged queue (aecm_process_ragged_queue_kernel): stream s runs len[s] blocks.  Behind the equal-length form's control words
+// (RaggedPlanOffsetWords(n_streams) words into ctl) lies the plan the host uploads before the launch, on the same stream: len[S],
+// order[S] (streams by length, longest first), first_item[n_chunks + 1] (aecm_engine.h: RaggedPlan).  n_items = first_item[n_chunks].
+size_t RaggedPlanOffsetWords(int n_streams);
+size_t RaggedQueueControlBytes(int n_streams, int n_chunks);
+hipError_t LaunchProcessBlocksRaggedQueued(const StatePtrs &st, const IoView &io, int n_streams, int live_streams, uint32_t n_items, int chunk_blocks,
+                                           int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
 
 // The pipelined form of a launch the chip holds at once (aecm_block_kernels.hip): a workgroup serves four streams with one
 // "back" wave per stream and, in waves of their own, the state-independent forward transforms one block ahead (front waves)
@@ -103,9 +110,10 @@ hipError_t LaunchScatterStates(const StatePtrs &st, int first, int count, const 
 hipError_t LaunchGatherByMap(const int16_t *src, int64_t src_stride, const int32_t *map_dev, int64_t n, int16_t *dst,
                              int64_t dst_stride, int n_streams, hipStream_t stream);
 //   out[s][j] = v >= 0 ? blocks[s][v] : (v == -1 ? 0 : near[s][-(v+2)])  with v = map[j]
+//   sample_limit_dev (may be null; S entries): out[s][j] = 0 for j >= sample_limit_dev[s] (the stream's recording ended there)
 hipError_t LaunchAssembleOutput(const int16_t *blocks, int64_t blocks_stride, const int16_t *near, int64_t near_stride,
                                 const int32_t *map_dev, int64_t n, int16_t *out, int64_t out_stride, int n_streams,
-                                hipStream_t stream);
+                                hipStream_t stream, const int32_t *sample_limit_dev = nullptr);
 
 // Streaming sessions (aecm_sessions.cpp): per-session sample rings of `ring_len` (power of two) int16 in HBM, indexed by
 // wrapping stream positions.

@@ -162,25 +162,26 @@ hipError_t LaunchGatherByMap(const int16_t *src, int64_t src_stride, const int32
 
 __global__ void aecm_assemble_output_kernel(const int16_t *blocks, int64_t blocks_stride, const int16_t *near,
                                             int64_t near_stride, const int32_t *map, int64_t n, int16_t *out,
-                                            int64_t out_stride, unsigned tiles) {
+                                            int64_t out_stride, unsigned tiles, const int32_t *sample_limit) {
     const int64_t s = blockIdx.x / tiles;
     const int64_t j = (int64_t)(blockIdx.x % tiles) * blockDim.x + threadIdx.x;
     if (j >= n) return;
     const int32_t v = map[j];
     int16_t r = 0;
-    if (v >= 0) r = blocks[s * blocks_stride + v];
+    if (sample_limit && j >= sample_limit[s]) r = 0;       // behind this stream's last call (ragged recordings): nothing was processed
+    else if (v >= 0) r = blocks[s * blocks_stride + v];
     else if (v <= -2) r = near[s * near_stride + (-(int64_t)v - 2)];
     out[s * out_stride + j] = r;
 }
 
 hipError_t LaunchAssembleOutput(const int16_t *blocks, int64_t blocks_stride, const int16_t *near, int64_t near_stride,
                                 const int32_t *map_dev, int64_t n, int16_t *out, int64_t out_stride, int n_streams,
-                                hipStream_t stream) {
+                                hipStream_t stream, const int32_t *sample_limit_dev) {
     if (n <= 0 || n_streams <= 0) return hipSuccess;
     const int64_t tiles = (n + 255) / 256;
     if (tiles * n_streams > 0x7fffffffll) return hipErrorInvalidValue;
     hipLaunchKernelGGL(aecm_assemble_output_kernel, dim3((unsigned)(tiles * n_streams)), dim3(256), 0, stream,
-                       blocks, blocks_stride, near, near_stride, map_dev, n, out, out_stride, (unsigned)tiles);
+                       blocks, blocks_stride, near, near_stride, map_dev, n, out, out_stride, (unsigned)tiles, sample_limit_dev);
     return hipGetLastError();
 }
 

@@ -28,6 +28,8 @@ RecordingSchedule BuildRecordingSchedule(int fs, int frame, int n_calls, int16_t
         }
         if (rc == kWarnBadParameter) s.warned = true;
         else if (rc != 0 && s.first_error == 0) s.first_error = rc;
+        s.blocks_after_call.push_back(s.n_blocks);
+        s.code_after_call.push_back(c > 0 && s.code_after_call[c - 1] != 0 ? s.code_after_call[c - 1] : rc);
         for (int i = 0; i < frame; ++i) {
             const int32_t v = out[i];
             // start-up calls copy the near input through: re-tag into the "near sample" range

@@ -300,6 +300,10 @@ struct RecordingSchedule {
     std::vector<int32_t> out_map;     // [n_calls*frame]: >= 0 block-output sample, -1 zero, <= -2 near sample -(v+2)
     int32_t first_error = 0;          // first non-zero return code other than the 12100 warning
     bool warned = false;              // some call returned AECM_BAD_PARAMETER_WARNING
+    // The session machinery is causal: the schedule of a recording of k <= n_calls calls is the prefix of this one that ends with
+    // call k - 1 -- its first blocks_after_call[k - 1] blocks and k * frame output entries (tests/test_ragged.py shows it).
+    std::vector<int32_t> blocks_after_call;   // [n_calls] blocks processed by the end of call c
+    std::vector<int32_t> code_after_call;     // [n_calls] first non-zero return code up to and including call c (0: none)
 };
 RecordingSchedule BuildRecordingSchedule(int fs, int frame, int n_calls, int16_t ms_in_snd_card_buf);
 

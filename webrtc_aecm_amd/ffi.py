@@ -45,6 +45,8 @@ BATCH_SYMBOLS = [
     "WebRtcAecmBatch_RegisterHostBuffer", "WebRtcAecmBatch_UnregisterHostBuffer",
     "WebRtcAecmBatch_DefaultLaunchPolicy", "WebRtcAecmBatch_GetLaunchPolicy", "WebRtcAecmBatch_SetLaunchPolicy", "WebRtcAecmBatch_DescribeLaunchDetail",
     "WebRtcAecm_SetDefaultDevice", "WebRtcAecmBatch_DevicePciBusId",
+    "WebRtcAecmBatch_ProcessBlocksRagged", "WebRtcAecmBatch_ProcessBlocksRaggedHost", "WebRtcAecmBatch_ProcessRecordingsRagged",
+    "WebRtcAecmBatch_ProcessRecordingsRaggedHost", "WebRtcAecmBatch_DescribeRaggedLaunch", "WebRtcAecmBatch_RaggedPlan",
 ]
 SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_Create", "WebRtcAecmSessions_Free", "WebRtcAecmSessions_Init", "WebRtcAecmSessions_set_config",
@@ -130,6 +132,14 @@ def load():
     lib.WebRtcAecmBatch_ProcessBlocksHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32]
     lib.WebRtcAecmBatch_ProcessRecordings.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int16]
     lib.WebRtcAecmBatch_ProcessRecordingsHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, C.c_int16]
+    lib.WebRtcAecmBatch_ProcessBlocksRagged.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp]
+    lib.WebRtcAecmBatch_ProcessBlocksRaggedHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int32, vp]
+    lib.WebRtcAecmBatch_ProcessRecordingsRagged.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int16, vp]
+    lib.WebRtcAecmBatch_ProcessRecordingsRaggedHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, C.c_int16, vp]
+    lib.WebRtcAecmBatch_DescribeRaggedLaunch.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, vp, C.c_int32,
+                                                         C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                         C.POINTER(C.c_int32)]
+    lib.WebRtcAecmBatch_RaggedPlan.argtypes = [C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.WebRtcAecmBatch_Synchronize.argtypes = [vp]
     lib.WebRtcAecmBatch_GetLastLaunchMs.argtypes = [vp, C.POINTER(C.c_float)]
     lib.WebRtcAecmBatch_GetTimers.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -375,6 +385,63 @@ class AecmBatch:
         """Device pointers (e.g. torch .data_ptr()); asynchronous on the engine's stream."""
         self._check(self.lib.WebRtcAecmBatch_ProcessBlocks(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride,
                                                            block_stride, num_blocks), "ProcessBlocks")
+
+    def _lengths(self, lengths):
+        lengths = np.ascontiguousarray(lengths, dtype=np.int32)
+        if lengths.shape != (self.num_streams,):
+            raise ValueError("one length per stream")
+        return lengths
+
+    def process_ragged_device(self, far_ptr, near_ptr, out_ptr, stream_stride, block_stride, num_blocks, blocks_per_stream, clean_ptr=None):
+        """process_device with one block count per stream (host array, entries in [0, num_blocks]): stream s runs its first
+        blocks_per_stream[s] blocks, its out blocks beyond that are not written.  Asynchronous on the engine's stream."""
+        lens = self._lengths(blocks_per_stream)
+        self._check(self.lib.WebRtcAecmBatch_ProcessBlocksRagged(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, block_stride,
+                                                                 num_blocks, lens.ctypes.data), "ProcessBlocksRagged")
+
+    def process_ragged_host(self, far, near, blocks_per_stream, clean=None, out=None):
+        """process_host with one block count per stream: far/near(/clean) [S, T*64] int16; stream s runs its first
+        blocks_per_stream[s] <= T blocks.  Returns out [S, T*64]: `out` if given (blocks beyond a stream's length keep what
+        they held), else a fresh array with zeros there."""
+        far = np.ascontiguousarray(far, dtype=np.int16)
+        near = np.ascontiguousarray(near, dtype=np.int16)
+        assert far.shape == near.shape and far.shape[0] == self.num_streams and far.shape[1] % BLOCK == 0
+        lens = self._lengths(blocks_per_stream)
+        if out is None:
+            out = np.zeros_like(near)
+        assert out.shape == near.shape and out.dtype == np.int16 and out.flags.c_contiguous
+        cp = None
+        if clean is not None:
+            clean = np.ascontiguousarray(clean, dtype=np.int16)
+            assert clean.shape == near.shape, "clean must have the shape of near"
+            cp = clean.ctypes.data
+        self._check(self.lib.WebRtcAecmBatch_ProcessBlocksRaggedHost(self.h, far.ctypes.data, near.ctypes.data, cp, out.ctypes.data, far.shape[1],
+                                                                     BLOCK, far.shape[1] // BLOCK, lens.ctypes.data), "ProcessBlocksRaggedHost")
+        return out
+
+    def process_recordings_ragged_host(self, far, near, frame: int, calls_per_stream, ms: int = 40, clean=None):
+        """process_recordings_host with one call count per stream (entries in [0, N // frame]): stream s is a session of
+        calls_per_stream[s] call pairs; its out row is 0 behind them.  Returns (code, out, codes[S])."""
+        far = np.ascontiguousarray(far, dtype=np.int16)
+        near = np.ascontiguousarray(near, dtype=np.int16)
+        assert far.shape == near.shape and far.shape[0] == self.num_streams
+        calls = self._lengths(calls_per_stream)
+        cptr = None
+        if clean is not None:
+            clean = np.ascontiguousarray(clean, dtype=np.int16)
+            assert clean.shape == near.shape
+            cptr = clean.ctypes.data
+        out = near.copy()
+        codes = np.zeros(self.num_streams, dtype=np.int32)
+        rc = self.lib.WebRtcAecmBatch_ProcessRecordingsRaggedHost(self.h, far.ctypes.data, near.ctypes.data, cptr, out.ctypes.data, far.shape[1],
+                                                                  frame, far.shape[1] // frame, calls.ctypes.data, ms, codes.ctypes.data)
+        if rc in (-1, AECM_UNSPECIFIED_ERROR, AECM_UNINITIALIZED_ERROR, AECM_NULL_POINTER_ERROR):      # the library's failure, not a session's code
+            raise AecmError(rc, "WebRtcAecmBatch_ProcessRecordingsRaggedHost")
+        return rc, out, codes
+
+    def describe_ragged_launch(self, blocks_per_stream, clean=False) -> dict:
+        """describe_ragged_launch (module level) under this batch's launch policy."""
+        return describe_ragged_launch(self._lengths(blocks_per_stream), clean=clean, policy=self.launch_policy())
 
     def synchronize(self):
         self._check(self.lib.WebRtcAecmBatch_Synchronize(self.h), "Synchronize")
@@ -699,6 +766,33 @@ def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int
     if rc != 0:
         raise AecmError(rc, "WebRtcAecmBatch_DescribeLaunchDetail")
     return d.as_dict()
+
+
+def describe_ragged_launch(blocks_per_stream, compute_units: int = 0, clean: bool = False, policy=None) -> dict:
+    """describe_launch_detail for a ragged launch (one block count per stream), without a device: the AecmLaunchDescription
+    fields plus items (the chunk queue's (chunk, stream) items; 0 for the other forms), sum_blocks (the useful work) and
+    max_blocks (the critical path)."""
+    lens = np.ascontiguousarray(blocks_per_stream, dtype=np.int32)
+    d = AecmLaunchDescription()
+    items, total, longest = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+    rc = load().WebRtcAecmBatch_DescribeRaggedLaunch(C.byref(policy) if policy is not None else None, compute_units, lens.size, lens.ctypes.data,
+                                                     1 if clean else 0, C.byref(d), C.byref(items), C.byref(total), C.byref(longest))
+    if rc != 0:
+        raise AecmError(rc, "WebRtcAecmBatch_DescribeRaggedLaunch")
+    return dict(d.as_dict(), items=items.value, sum_blocks=total.value, max_blocks=longest.value)
+
+
+def ragged_plan(blocks_per_stream, chunk_blocks: int):
+    """(order, first_item) of the plan a ragged chunk-queue launch runs by (include/aecm_batch.h: WebRtcAecmBatch_RaggedPlan)."""
+    lens = np.ascontiguousarray(blocks_per_stream, dtype=np.int32)
+    order = np.zeros(lens.size, dtype=np.int32)
+    cap = (int(lens.max(initial=0)) + chunk_blocks - 1) // max(chunk_blocks, 1) + 1 if chunk_blocks > 0 else 1
+    first_item = np.zeros(cap, dtype=np.int32)
+    n_chunks = C.c_int32(0)
+    rc = load().WebRtcAecmBatch_RaggedPlan(lens.size, lens.ctypes.data, chunk_blocks, order.ctypes.data, first_item.ctypes.data, cap, C.byref(n_chunks))
+    if rc != 0:
+        raise AecmError(rc, "WebRtcAecmBatch_RaggedPlan")
+    return order, first_item[:n_chunks.value + 1]
 
 
 def describe_tick(num_sessions: int, compute_units: int) -> dict:
