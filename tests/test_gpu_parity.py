@@ -802,17 +802,20 @@ def test_random_launch_policies_never_change_results(seed):
     for s_ in range(S):
         b.set_config(*stream_config(int(idx[s_])), s_, 1)
     outs, pos, forms = [], 0, set()
-    for t in parts:
+    all_resident = b.launch_policy().resident_waves
+    starved = next(i for i, t in enumerate(parts) if t >= 16)     # one launch on the chunk queue under resident_waves=1: fewer waves than a workgroup has
+    for i, t in enumerate(parts):
         wishes = dict(pipe_tail_waves=int(rs.choice([-1, 0, 2])), pipe_front_waves=int(rs.choice([-1, 2, 4])), pipe_raw=int(rs.choice([-1, 0, 1])),
                       pipe_delay_waves=int(rs.choice([-1, 0, 2, 4])), pipe_gain_waves=int(rs.choice([-1, 0, 4])), pipe_spread=int(rs.randint(0, 2)),
                       pipe_rot=int(rs.choice([-1, rs.randint(0, 1024)])), pipe_prio=int(rs.choice([-1, rs.randint(0, 256)])),
                       pipelined_min_streams=int(rs.choice([2, 2, 2, 0])), pipelined_min_blocks=int(rs.choice([1, 3])))
-        if rs.rand() < 0.25:                                  # the chunk queue on a batch this small: chunks of 8, at least two of them
+        if rs.rand() < 0.25 or i == starved:                  # the chunk queue on a batch this small: chunks of 8, at least two of them
             wishes.update(queue_min_streams=0, queue_chunk_blocks=8, queue_chunk_explicit=1, pipelined_min_streams=0)
         else:
             wishes.update(queue_min_streams=-1, queue_chunk_blocks=128, queue_chunk_explicit=0)
-        b.set_launch_policy(**wishes)
+        b.set_launch_policy(resident_waves=1 if i == starved else all_resident, **wishes)
         forms.add(b.describe_launch(t)[0])
+        assert i != starved or b.describe_launch(t)[0] == 2, (seed, t)
         outs.append(b.process_host(far[:, pos * 64:(pos + t) * 64], near[:, pos * 64:(pos + t) * 64]))
         pos += t
     out = np.concatenate(outs, axis=1)

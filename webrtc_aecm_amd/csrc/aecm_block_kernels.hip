@@ -136,6 +136,34 @@ __device__ __forceinline__ uint32_t QueueMaxPolls(int chunk_blocks) {
     return by_chunk > (1u << 20) ? by_chunk : (1u << 20);
 }
 
+// The three pieces both queue kernels are made of.  Every lane takes part in the queue's few memory operations with the same
+// address and, for the counter, an addend that is 1 in lane 0 only: no lane-divergent control flow anywhere in the item loop.
+__device__ __forceinline__ uint32_t QueueClaim(uint32_t *ctl) {
+    const uint32_t one_in_lane0 = (threadIdx.x & 63u) == 0 ? 1u : 0u;
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_fetch_add(ctl, one_in_lane0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+// Until the stream's chunks before `chunk` are done.  false: gave up -- *err is raised and every wave leaves at its next claim.
+__device__ __forceinline__ bool QueueWait(const uint32_t *done, uint32_t stream, uint32_t chunk, int chunk_blocks, uint32_t *err) {
+    if (chunk != 0) {
+        uint32_t polls = 0;
+        while ((uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(done + stream, kQueueAcquire, __HIP_MEMORY_SCOPE_AGENT)) < chunk) {
+            __builtin_amdgcn_s_sleep(16);
+            if (++polls > QueueMaxPolls(chunk_blocks) ||
+                ((polls & 1023u) == 0 && __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)) {
+                __hip_atomic_store(err, 1u + stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return false;
+            }
+        }
+    }
+    asm volatile("" ::: "memory");                       // the state loads stay behind the flag
+    return true;
+}
+__device__ __forceinline__ void QueuePublish(uint32_t *done, uint32_t stream, uint32_t chunk) {
+    // every store of the chunk (state, history rows: sc1, written through) has completed before the flag is raised
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __hip_atomic_store(done + stream, chunk + 1u, kQueueRelease, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <bool kHasClean>
 __global__ __launch_bounds__(64 * kWavesPerWorkgroup)
 __attribute__((amdgpu_waves_per_eu(AECM_WAVES_PER_EU, AECM_MAX_WAVES_PER_EU)))
@@ -145,35 +173,18 @@ void aecm_process_queue_kernel(StatePtrs st, IoView io, int n_streams, int n_blo
     using E = BlockEngine<Gfx950Wave<true, true, false, true>, kHasClean>;
     const uint32_t n_items = (uint32_t)n_streams * (uint32_t)n_chunks;
     uint32_t *done = ctl + kQueueCtlWords;
-    // Every lane takes part in the queue's few memory operations with the same address and, for the counter, an addend
-    // that is 1 in lane 0 only: no lane-divergent control flow anywhere in the item loop.
-    const uint32_t one_in_lane0 = (threadIdx.x & 63u) == 0 ? 1u : 0u;
     for (;;) {
-        const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane(
-            (int)__hip_atomic_fetch_add(ctl, one_in_lane0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        const uint32_t item = QueueClaim(ctl);
         if (item >= n_items) break;
         if (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) break;
         const uint32_t chunk = item / (uint32_t)n_streams;
         const uint32_t stream = item - chunk * (uint32_t)n_streams;
-        if (chunk != 0) {
-            uint32_t polls = 0;
-            while ((uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(done + stream, kQueueAcquire, __HIP_MEMORY_SCOPE_AGENT)) < chunk) {
-                __builtin_amdgcn_s_sleep(16);
-                if (++polls > QueueMaxPolls(chunk_blocks) ||
-                    ((polls & 1023u) == 0 && __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)) {
-                    __hip_atomic_store(err, 1u + stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // every wave leaves at its next claim
-                    return;
-                }
-            }
-        }
-        asm volatile("" ::: "memory");                       // the state loads stay behind the flag
+        if (!QueueWait(done, stream, chunk, chunk_blocks, err)) return;
         const int first = (int)chunk * chunk_blocks;
         const int nb = n_blocks - first < chunk_blocks ? n_blocks - first : chunk_blocks;
         typename E::StridedIo sio{io, (int64_t)stream * io.stream_stride + (int64_t)first * io.block_stride};
         E::run_stream_io(st, sio, (int64_t)stream, nb);
-        // every store of the chunk (state, history rows: sc1, written through) has completed before the flag is raised
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __hip_atomic_store(done + stream, chunk + 1u, kQueueRelease, __HIP_MEMORY_SCOPE_AGENT);
+        QueuePublish(done, stream, chunk);
     }
 }
 
@@ -194,7 +205,8 @@ void aecm_process_queue_kernel(StatePtrs st, IoView io, int n_streams, int n_blo
 // or is itself waiting for (c - 2, s) -- a chain that ends at a chunk 0, which waits for nobody.  Late chunks of a
 // long-tailed batch have fewer live streams than the grid has waves: the surplus waves find the counter exhausted and
 // leave, the tail runs as serially as a stream's chunks depend on each other.  The wait stays bounded and raises *err.
-// (A kernel of its own with the equal-length kernel's item body restated, not a template parameter of that kernel: the
+// (A kernel of its own with the equal-length kernel's item loop restated around the shared claim / wait / publish steps, not a
+// template parameter of that kernel: the
 // headline kernels' instruction streams stay exactly what they were.)
 template <bool kHasClean>
 __global__ __launch_bounds__(64 * kWavesPerWorkgroup)
@@ -204,12 +216,10 @@ void aecm_process_ragged_queue_kernel(StatePtrs st, IoView io, int n_streams, ui
     using E = BlockEngine<Gfx950Wave<true, true, false, true>, kHasClean>;
     uint32_t *done = ctl + kQueueCtlWords;
     const uint32_t *len = done + n_streams, *order = len + n_streams, *first_item = order + n_streams;      // written by the host before the launch
-    const uint32_t one_in_lane0 = (threadIdx.x & 63u) == 0 ? 1u : 0u;
     uint32_t chunk = 0, chunk_first = 0;                                      // the cursor: first_item[chunk] <= every later claim of this wave
     uint32_t chunk_end = (uint32_t)__builtin_amdgcn_readfirstlane((int)first_item[1]);
     for (;;) {
-        const uint32_t item = (uint32_t)__builtin_amdgcn_readfirstlane(
-            (int)__hip_atomic_fetch_add(ctl, one_in_lane0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        const uint32_t item = QueueClaim(ctl);
         if (item >= n_items) break;
         if (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0) break;
         while (item >= chunk_end) {                                           // item < n_items = first_item[n_chunks]: stops at a chunk < n_chunks
@@ -222,18 +232,7 @@ void aecm_process_ragged_queue_kernel(StatePtrs st, IoView io, int n_streams, ui
             __hip_atomic_store(err, 0x80000000u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
-        if (chunk != 0) {
-            uint32_t polls = 0;
-            while ((uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(done + stream, kQueueAcquire, __HIP_MEMORY_SCOPE_AGENT)) < chunk) {
-                __builtin_amdgcn_s_sleep(16);
-                if (++polls > QueueMaxPolls(chunk_blocks) ||
-                    ((polls & 1023u) == 0 && __builtin_amdgcn_readfirstlane((int)__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)) {
-                    __hip_atomic_store(err, 1u + stream, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // every wave leaves at its next claim
-                    return;
-                }
-            }
-        }
-        asm volatile("" ::: "memory");                       // the state loads stay behind the flag
+        if (!QueueWait(done, stream, chunk, chunk_blocks, err)) return;
         const int first = (int)chunk * chunk_blocks;
         const int left = __builtin_amdgcn_readfirstlane((int)len[stream]) - first;
         const int nb = left < chunk_blocks ? left : chunk_blocks;
@@ -241,9 +240,7 @@ void aecm_process_ragged_queue_kernel(StatePtrs st, IoView io, int n_streams, ui
             typename E::StridedIo sio{io, (int64_t)stream * io.stream_stride + (int64_t)first * io.block_stride};
             E::run_stream_io(st, sio, (int64_t)stream, nb);
         }
-        // every store of the chunk (state, history rows: sc1, written through) has completed before the flag is raised
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __hip_atomic_store(done + stream, chunk + 1u, kQueueRelease, __HIP_MEMORY_SCOPE_AGENT);
+        QueuePublish(done, stream, chunk);
     }
 }
 
@@ -272,9 +269,8 @@ constexpr int kPipeStreams = 4;
 // front wave with two streams' transforms is the longest link of the chain).
 // A third role (round 5): tail_block -- inverse transform, synthesis window, overlap-add, the output store: 19 % of a block's
 // vector instructions and a long chain of LDS table reads and lane exchanges -- in kTail "tail" waves of their own, one block
-// BEHIND the middle waves (which then run middle_block only).  kTail = 1: one wave for the workgroup's four streams, seven
-// waves per workgroup = 28 per CU with four workgroups, every wave slot of the SIMDs taken; kTail = 2: two waves of two
-// streams, eight waves per workgroup, three workgroups per CU (launches of up to 3 072 streams).  The stream's sequential part
+// BEHIND the middle waves (which then run middle_block only): two waves of two streams, eight waves per workgroup, three
+// workgroups per CU (launches of up to 3 072 streams).  The stream's sequential part
 // shrinks once more (what a small launch is bound by) and a SIMD gets one more wave of dense vector work to fill its port with.
 // A fourth role (round 5, small launches): delay_block -- both binary spectra, the bit histories, the 100 means; a chain of
 // reductions and scalar decisions on state of its own, a sixth of the middle wave's instructions -- in kDelay "delay" waves, one
@@ -319,30 +315,24 @@ struct PipeShared {
     PipeGainSlot gains[kGain ? 2 : 1][kGain ? kPipeStreams : 1];
     PipeGainState gain_state[kGain ? kPipeStreams : 1];
     int ahead;                            // this workgroup leads the launch's slowest one by more than the allowed lead (balance, below)
-    int level;                            // the front waves' base priority for the current group of blocks (balance modes 2, 3)
+    int level;                            // the front waves' base priority for the current group of blocks (balance)
 };
 #ifndef AECM_PIPE_TAIL_PRIO
 #define AECM_PIPE_TAIL_PRIO 1         // the tail waves' issue priority
-#endif
-// Which launches get delay waves when the caller does not say (workgroups of four streams the launch makes, CUs of the device): those the
-// sixteen-wave shape takes (below).
-#ifndef AECM_PIPE_DELAY_DEFAULT
-#define AECM_PIPE_DELAY_DEFAULT(n_wg, cus) ((n_wg) <= 2 * (cus) ? kPipeStreams : 0)
 #endif
 // Workgroups of the sixteen-wave shape a CU takes (experiments: two of them are 32 waves, eight per SIMD -- the kernel's 61 VGPRs allow it)
 #ifndef AECM_PIPE_GAIN_WGS_PER_CU
 #define AECM_PIPE_GAIN_WGS_PER_CU (PipeWorkgroupsPerCu<2, 4, 2, 4>())
 #endif
-// Which launches get gain waves when the caller does not say: up to two sixteen-wave workgroups per CU (eight streams per CU).
+// Which launches get delay and gain waves (the sixteen-wave shape) when the caller does not say, by the workgroups of four streams
+// the launch makes and the CUs of the device: up to two sixteen-wave workgroups per CU (eight streams per CU).
 // Round 5 gave this shape one workgroup per CU only (1 024 streams 492 -> 612 M frames/s with the gain waves, 256 streams 124 -> 155)
 // because two of them measured 620 M at 2 048 streams against the ten-wave shape's 740: with 81 SGPRs the two never shared a CU
-// (PipeWavesPerEu above), and with every one-stream role of a slot on the same SIMD a CU of five streams ran them at 0.43 instead of
+// (PipeWavesPerEu below), and with every one-stream role of a slot on the same SIMD a CU of five streams ran them at 0.43 instead of
 // 0.60 M frames/s each.  Built for eight waves per SIMD and with the roles staggered over the SIMDs (the kernel's slot_of) the shape
 // carries a CU's eight streams as well as the ten-wave shape and everything below better (profiles/r06_experiments.md):
 // 1 280 streams 482 -> 650, 1 536: 571 -> 688, 1 792: 647 -> 702, 2 048: 738 / 734.
-#ifndef AECM_PIPE_GAIN_DEFAULT
-#define AECM_PIPE_GAIN_DEFAULT(n_wg, cus) ((n_wg) <= 2 * (cus) ? kPipeStreams : 0)
-#endif
+constexpr bool PipeDeepShapeByDefault(int n_wg, int cus) { return n_wg <= 2 * cus; }
 #ifndef AECM_PIPE_GAIN_PRIO
 #define AECM_PIPE_GAIN_PRIO 3         // the gain waves' issue priority (1 / 2 / 3: 1 024 streams 594 / 607 / 613 M frames/s)
 #endif
@@ -357,10 +347,13 @@ struct PipeShared {
 // front wave of a workgroup (the "monitor": front waves finish their step early and would otherwise just park at the
 // barrier) publishes the workgroup's group count in its own word of progress[] (a write-through store, no atomic), reads
 // everybody's words (n_workgroups / 64 loads of 64 lanes, issued at the top of its step and looked at at the end of it) and
-// takes their minimum: a workgroup more than AECM_PIPE_BALANCE_LEAD groups ahead of the slowest one runs its back waves with
-// lowered phase priorities (Gfx950Wave<.., kDynamicPrio>) for the next group -- they still issue whenever the others leave a
-// slot free (a lowered priority is work-conserving, a sleeping wave is not), but no longer win ties.  The flag reaches the
-// other waves through LDS behind the barrier every wave executes anyway.  Stale words only make the verdict late.
+// takes their minimum: a workgroup more than AECM_PIPE_BALANCE_LEAD groups ahead of the slowest one runs its FRONT waves at
+// AECM_PIPE_FRONT_PRIO instead of kPipeFrontPrioBehind for the next group -- a workgroup advances at the pace of its front waves
+// (the back waves run at higher priorities and park at the barrier until the spectra of the next block are there: measured 30 %
+// of their time at 4 096 streams), so the front waves are the handle.  The level reaches them through LDS behind the barrier
+// every wave executes anyway.  Stale words only make the verdict late.  AECM_PIPE_BALANCE 0: no launch takes the balanced form.
+// (Tried and not built -- back-wave demotion, one level per group of lead, a sampled monitor, "behind the fastest" as the rule,
+// seven-wave workgroups with one tail wave: profiles/r05_experiments.md, profiles/r09_experiments.md.)
 #ifndef AECM_PIPE_BALANCE
 #define AECM_PIPE_BALANCE 2
 #endif
@@ -370,36 +363,10 @@ struct PipeShared {
 #ifndef AECM_PIPE_BALANCE_LEAD
 #define AECM_PIPE_BALANCE_LEAD 1
 #endif
-// AECM_PIPE_BALANCE: 0 off; 1 the back waves of a workgroup that is ahead run demoted (and its front waves at
-// AECM_PIPE_FRONT_PRIO instead of .._BEHIND, if those differ); 2 only the front waves' priority follows the flag -- a
-// workgroup advances at the pace of its front waves (the back waves run at higher priorities and park at the barrier until
-// the spectra of the next block are there: measured 30 % of their time at 4 096 streams), so the front waves are the handle.
-// AECM_PIPE_BALANCE_RULE: which workgroups take the LOW front priority: 0 those more than LEAD groups ahead of the slowest,
-// 1 those less than LEAD groups behind the fastest (i.e. only the stragglers are raised).  AECM_PIPE_BALANCE 3: like 2 with
-// one level per group of lead (proportional instead of on / off).
-#ifndef AECM_PIPE_FRONT_PRIO_BEHIND
-#if AECM_PIPE_BALANCE == 3
-#define AECM_PIPE_FRONT_PRIO_BEHIND 2
-#elif AECM_PIPE_BALANCE == 2
-#define AECM_PIPE_FRONT_PRIO_BEHIND 1
-#else
-#define AECM_PIPE_FRONT_PRIO_BEHIND AECM_PIPE_FRONT_PRIO     // the front waves' priority while their workgroup is NOT ahead
-#endif
-#endif
-#ifndef AECM_PIPE_MONITOR_SAMPLE
-#define AECM_PIPE_MONITOR_SAMPLE 0
-#endif
-#ifndef AECM_PIPE_BALANCE_RULE
-#define AECM_PIPE_BALANCE_RULE 0
-#endif
-// A front wave's priority rises by AECM_PIPE_FRONT_SECOND_BOOST while it works on its second stream (the rule of the back
-// waves' phase table -- the priority rises with the progress through the step -- applied to the front waves).
-#ifndef AECM_PIPE_FRONT_SECOND_BOOST
-#define AECM_PIPE_FRONT_SECOND_BOOST 1
-#endif
-#ifndef AECM_PIPE_FRONT_SECOND_BOOST_BALANCED
-#define AECM_PIPE_FRONT_SECOND_BOOST_BALANCED 0
-#endif
+constexpr int kPipeFrontPrioBehind = 1;                 // the front waves' priority while their workgroup is NOT ahead (balanced launches)
+// A front wave's priority rises by this while it works on its second stream (the rule of the back waves' phase table -- the
+// priority rises with the progress through the step).  Not on top of the balance: 4 096 streams 862 M frames/s without, 844 with.
+constexpr int kPipeFrontSecondBoost = 1, kPipeFrontSecondBoostBalanced = 0;
 __device__ __forceinline__ void SetPrioDynamic(int p) {      // s_setprio takes an immediate
     if (p <= 0) __builtin_amdgcn_s_setprio(0);
     else if (p == 1) __builtin_amdgcn_s_setprio(1);
@@ -420,13 +387,6 @@ constexpr int kPipeMonitorLoads = 10;     // x 64 lanes x 2 halves: launches of 
 // (Measured against rings with per-stream counters and no barrier -- pairs of waves that only wait for each other:
 // slower, 4 096 streams 783 vs 818 M frames/s.  A wave parked at a barrier costs nothing; a wave polling a counter costs
 // issue slots, and at the priority its last phase left it with it starves the wave it is waiting for.)
-// Seven-wave workgroups (kTail = 1) are built for EIGHT waves per SIMD: four of them per CU are 28 waves, exactly the 4 x 7 slots
-// the usual budget leaves -- and the dispatcher does not find that exact fit (a workgroup's seven waves go 2 + 2 + 2 + 1 over the
-// SIMDs): measured, the fourth workgroup of every CU only started when the first had finished.  At 8 slots per SIMD (<= 64
-// VGPRs, which the kernel needs anyway, and <= 80 SGPRs) there is room to spare.
-#ifndef AECM_PIPE_TAIL1_WAVES_PER_EU
-#define AECM_PIPE_TAIL1_WAVES_PER_EU 8
-#endif
 // kBalance: the progress feedback of the front waves' priority (above) is compiled in; launches that do not use it (fewer than
 // four workgroups per CU) take the instantiation without it -- the same kernel with its monitor and its run-time priority
 // levels switched off at run time measured 2 % slower there.
@@ -443,35 +403,20 @@ constexpr int kPipeMonitorLoads = 10;     // x 64 lanes x 2 halves: launches of 
 #ifndef AECM_PIPE16_WAVES_PER_EU
 #define AECM_PIPE16_WAVES_PER_EU 8
 #endif
-#ifndef AECM_PIPE10_WAVES_PER_EU
-#define AECM_PIPE10_WAVES_PER_EU AECM_WAVES_PER_EU
-#endif
-#ifndef AECM_PIPE8_WAVES_PER_EU
-#define AECM_PIPE8_WAVES_PER_EU AECM_WAVES_PER_EU
-#endif
-#ifndef AECM_PIPE6_WAVES_PER_EU
-#define AECM_PIPE6_WAVES_PER_EU AECM_WAVES_PER_EU
-#endif
-constexpr int PipeWavesPerEu(int tail_waves, int front_waves, int delay_waves, int gain_waves) {
+constexpr int PipeWavesPerEu(int gain_waves) {
 #if defined(AECM_CHECKED)
     return AECM_WAVES_PER_EU;
 #else
-    return PipeWaves(tail_waves, front_waves, delay_waves, gain_waves) == 7 ? AECM_PIPE_TAIL1_WAVES_PER_EU
-           : gain_waves != 0 ? AECM_PIPE16_WAVES_PER_EU
-           : delay_waves != 0 ? AECM_WAVES_PER_EU
-           : tail_waves == 0 ? AECM_PIPE6_WAVES_PER_EU
-           : front_waves == 4 ? AECM_PIPE10_WAVES_PER_EU : AECM_PIPE8_WAVES_PER_EU;
+    return gain_waves != 0 ? AECM_PIPE16_WAVES_PER_EU : AECM_WAVES_PER_EU;
 #endif
 }
 template <int kTail, bool kBalance, bool kRaw = false, int kFront = 2, int kDelay = 0, int kGain = 0>
 __global__ __launch_bounds__(64 * PipeWaves(kTail, kFront, kDelay, kGain))
-__attribute__((amdgpu_waves_per_eu(PipeWavesPerEu(kTail, kFront, kDelay, kGain), AECM_MAX_WAVES_PER_EU)))
+__attribute__((amdgpu_waves_per_eu(PipeWavesPerEu(kGain), AECM_MAX_WAVES_PER_EU)))
 void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, int streams_rem, int n_blocks, uint32_t *progress, int n_workgroups,
                                     int wgs_per_round, int rot, int prio) {
-    constexpr int kMode = kBalance ? AECM_PIPE_BALANCE : 0;               // AECM_PIPE_BALANCE's meaning, per instantiation
-    constexpr int kFrontBehind = kBalance ? AECM_PIPE_FRONT_PRIO_BEHIND : AECM_PIPE_FRONT_PRIO;
-    // the second-stream boost is for the launches without balance: on top of it, it costs (4 096 streams: 862 M frames/s without, 844 with)
-    constexpr int kBoost = kBalance ? AECM_PIPE_FRONT_SECOND_BOOST_BALANCED : AECM_PIPE_FRONT_SECOND_BOOST;
+    constexpr int kFrontBehind = kBalance ? kPipeFrontPrioBehind : AECM_PIPE_FRONT_PRIO;
+    constexpr int kBoost = kBalance ? kPipeFrontSecondBoostBalanced : kPipeFrontSecondBoost;
 #if defined(AECM_PIPE_TRACE)     // diagnostics build: per wave, when it started / ended (100 MHz wall clock) and how long it sat at barriers (shader clocks)
     const uint64_t trace_t0 = wall_clock64(), trace_c0 = clock64();
     uint64_t trace_wait = 0;
@@ -479,15 +424,16 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
 #else
 #define AECM_PIPE_BARRIER() __syncthreads()
 #endif
+    static_assert(kTail == 0 || kTail == 2, "tail waves: two, of two streams each");
     static_assert(kDelay == 0 || (kPipeStreams % kDelay == 0 && !kRaw), "delay waves: in the shapes with formed spectra");
     static_assert(kGain == 0 || (kGain == kPipeStreams && kDelay != 0), "gain waves: one per stream, with delay waves");
     constexpr int kWaves = PipeWaves(kTail, kFront, kDelay, kGain), kPipeFrontWaves = kFront, kPipeStreamsPerFront = kPipeStreams / kFront;
     constexpr int kLagD = kDelay ? 1 : 0, kLagG = kGain ? 1 : 0;           // steps the delay / gain waves put between the front waves and the rest
     constexpr int kSlots = 2 + kLagD + kLagG;
     PipeShared<kTail, kRaw, kDelay, kGain> &sh = *reinterpret_cast<PipeShared<kTail, kRaw, kDelay, kGain> *>(&g_lds[1]);        // behind the tables
-    if (kMode != 0 && threadIdx.x == 0) { sh.ahead = 0; sh.level = kFrontBehind; }
+    if (kBalance && threadIdx.x == 0) { sh.ahead = 0; sh.level = kFrontBehind; }
     FillLdsTables<64 * kWaves>(st.consts);                              // ends in a barrier
-    using W = Gfx950Wave<true, true, false, false, kMode == 1>;
+    using W = Gfx950Wave<true, true>;
     using E = BlockEngine<W, false>;
     using EF = BlockEngine<Gfx950Wave<true, false>, false>;               // the front and tail waves keep one priority (no per-phase s_setprio)
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -525,15 +471,11 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
         uint16_t *hist = st.hist + stream * (int64_t)kHistWordsPerStream;
         typename E::StridedIo sio{io, stream * io.stream_stride};
         if (live) E::load_state(r, vec, scal);
-        r.u.prio_drop = 0;
         W::begin_stream();
         AECM_PIPE_BARRIER();                                              // step 0: the spectra of block 0 are in slots[0]
         if (kDelay != 0) AECM_PIPE_BARRIER();                             // step 1: the delay waves' first
         int slot_idx = 0;                                                 // blk mod kSlots
         for (int blk = 0; blk < n_blocks; ++blk) {                        // step blk + 1 (+ 1 with delay waves)
-            // Balance, mode 1 (see above): the monitor wrote the flag at the end of its step blk, which ran next to this wave's
-            // block blk - 1 and ended in the barrier this wave has just passed.
-            if (kMode == 1 && (blk & kPipeGroupMask) == 0 && blk != 0) r.u.prio_drop = __builtin_amdgcn_readfirstlane(sh.ahead);
             if (live) {
                 const int lane = W::lane_id();
                 typename E::Spectrum xf, df;
@@ -567,7 +509,7 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
                 }
                 if constexpr (kTail != 0) {
                     if constexpr (kGain != 0) {
-                        W::template phase_priority<3>(r.u.prio_drop);
+                        W::template phase_priority<3>();
                         E::track_q(r.u, df, df);
                         const typename E::GainInput g = E::template channel_block<true>(r, hist, xf, df, delay_given, far_given);
                         PipeGainSlot &gs = sh.gains[blk & 1][slot];
@@ -632,7 +574,7 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
             // Balance: the monitor's step at a group boundary (see above).  pv[] is only ever read under the condition it is
             // loaded under (no initialisation: a register written by a move while a load of an earlier trip may still be
             // pending in the compiler's eyes costs a wait for everything in flight at the top of every trip).
-            const bool boundary = kMode != 0 && (blk & kPipeGroupMask) == 0 && blk != 0;
+            const bool boundary = kBalance && (blk & kPipeGroupMask) == 0 && blk != 0;
             const bool monitor = boundary && wave == kPipeStreams;
             int pv[kPipeMonitorLoads];
             if (monitor) {
@@ -642,22 +584,14 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
                 __hip_atomic_store(reinterpret_cast<uint16_t *>(progress) + blockIdx.x, (uint16_t)(0xffff - (g < 0xffff ? g : 0xffff)),
                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 const int lane = W::lane_id(), n_words = (n_workgroups + 1) >> 1;
-#if AECM_PIPE_MONITOR_SAMPLE
-                // a sample instead of everybody: 128 workgroups (one load), a different 128 at every boundary and in every workgroup.
-                // The slow workgroups are a quarter to a half of the launch (the ones dispatched last to each CU), so every sample has some.
-                const int n_chunks = (n_words + 63) >> 6, chunk = (int)((blockIdx.x + (unsigned)g * 7u) % (unsigned)n_chunks);
-                const int w = lane + 64 * chunk;
-                pv[0] = (int)__hip_atomic_load(progress + (w < n_words ? w : n_words - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
 #pragma unroll
                 for (int i = 0; i < kPipeMonitorLoads; ++i) {
                     const int w = lane + 64 * i;
                     if (64 * i < n_words)
                         pv[i] = (int)__hip_atomic_load(progress + (w < n_words ? w : n_words - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
-#endif
             }
-            if (kMode != 0 && kFrontBehind != AECM_PIPE_FRONT_PRIO && (blk & kPipeGroupMask) == 1 && blk > kPipeGroupMask) {
+            if (kBalance && kFrontBehind != AECM_PIPE_FRONT_PRIO && (blk & kPipeGroupMask) == 1 && blk > kPipeGroupMask) {
                 level = __builtin_amdgcn_readfirstlane(sh.level);
                 if (kBoost == 0) SetPrioDynamic(level);
             }
@@ -701,30 +635,14 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
             }
             if (monitor) {
                 const int n_words = (n_workgroups + 1) >> 1;
-                int m = AECM_PIPE_BALANCE_RULE == 0 ? pv[0] : pk_add_u16(pv[0], -1);
-#if !AECM_PIPE_MONITOR_SAMPLE
+                int m = pv[0];
 #pragma unroll
                 for (int i = 1; i < kPipeMonitorLoads; ++i)
-                    if (64 * i < n_words) m = AECM_PIPE_BALANCE_RULE == 0 ? pk_max_u16(m, pv[i]) : pk_min_u16(m, pk_add_u16(pv[i], -1));
-#endif
-#if AECM_PIPE_BALANCE_RULE == 0
+                    if (64 * i < n_words) m = pk_max_u16(m, pv[i]);
                 const int slowest = 0xffff - W::reduce_max(imax(zext16(m), lsr(m, 16)));      // group count of the slowest workgroup that has published
                 const int lead = (blk >> kPipeGroupLog2) - slowest;
-#if defined(AECM_PIPE_BALANCE_DRY)       // A/B: the monitor runs, nobody is ever demoted (what the mechanism itself costs)
-                sh.ahead = lead > 0x7ffffff ? 1 : 0;
-#else
                 sh.ahead = lead > AECM_PIPE_BALANCE_LEAD ? 1 : 0;
-#endif
-#else
-                // the fastest: the smallest published word (an unpublished or unused half reads 0: minus one it is the largest)
-                const int fastest = 0xfffe - W::reduce_min(imin(zext16(m), lsr(m, 16)));
-                const int lead = AECM_PIPE_BALANCE_LEAD + 1 - (fastest - (blk >> kPipeGroupLog2));     // (> LEAD <=> less than one group behind the fastest)
-                sh.ahead = lead > AECM_PIPE_BALANCE_LEAD ? 1 : 0;
-#endif
-                if (kMode == 3)      // proportional: one priority level per group of lead beyond the allowed one, from .._BEHIND down to AECM_PIPE_FRONT_PRIO
-                    sh.level = imax(kFrontBehind - imax(lead - AECM_PIPE_BALANCE_LEAD, 0), AECM_PIPE_FRONT_PRIO);
-                else
-                    sh.level = sh.ahead ? AECM_PIPE_FRONT_PRIO : kFrontBehind;
+                sh.level = sh.ahead ? AECM_PIPE_FRONT_PRIO : kFrontBehind;
             }
             slot_idx = slot_idx + 1 == kSlots ? 0 : slot_idx + 1;
             AECM_PIPE_BARRIER();
@@ -737,10 +655,9 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
             if (live[k]) EF::store_time_state(st.vec + slot_stream(ks(k)) * (int64_t)kVecWordsPerStream, r.lane, x_old[k], d_old[k]);
     } else if (wave < kPipeStreams + kPipeFrontWaves + kTail) {
         // ---- tail wave: kPipeStreams / kTail streams, inverse transform + synthesis + output of the block BEFORE the one the middle waves are at ----
-        constexpr int kPer = kTail ? kPipeStreams / kTail : 1;
+        constexpr int kPer = kPipeStreams / 2;
         typename EF::Regs r;
         EF::init_lane_constants(r, st.consts);
-        r.u.prio_drop = 0;
         SetPrioDynamic((prio >> 2) & 3);
         k0 = slot_of((wave - kPipeStreams - kPipeFrontWaves) * kPer, rot_tail);
         int ovl[kPer], c_old[kPer];
@@ -781,8 +698,7 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
             constexpr int kPer = kPipeStreams / kDelay;
             typename EF::Regs r;
             EF::init_lane_constants(r, st.consts);
-            r.u.prio_drop = 0;
-            SetPrioDynamic((prio >> 4) & 3);
+                SetPrioDynamic((prio >> 4) & 3);
             k0 = slot_of((wave - (kPipeStreams + kPipeFrontWaves + kTail)) * kPer, rot_delay);
             // the estimator's state per stream (BlockEngine::load_delay_state's fields), moved into r around each call
             int mean[kPer], bh0[kPer], bh1[kPer], m01[kPer], far_init[kPer], near_init[kPer], min_prob[kPer], last_prob[kPer], last_delay[kPer];
@@ -869,8 +785,7 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
             // ---- gain wave: one stream, gain_block of the block BEFORE the one its channel wave is at ----
             typename EF::Regs r;
             EF::init_lane_constants(r, st.consts);
-            r.u.prio_drop = 0;
-            SetPrioDynamic((prio >> 6) & 3);
+                SetPrioDynamic((prio >> 6) & 3);
             const int k = slot_of(wave - (kPipeStreams + kPipeFrontWaves + kTail + kDelay), rot_gain);
             const int64_t stream = slot_stream(k);
             const bool live = slot_live(k);
@@ -941,7 +856,7 @@ void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, in
 // Streams a pipelined launch keeps resident at once: workgroups per CU by wave slots (4 SIMDs x 7) and by LDS (160 KB).
 template <int kTail, int kFront = 2, int kDelay = 0, int kGain = 0>
 constexpr int PipeWorkgroupsPerCu() {
-    constexpr int by_waves = 4 * PipeWavesPerEu(kTail, kFront, kDelay, kGain) / PipeWaves(kTail, kFront, kDelay, kGain);
+    constexpr int by_waves = 4 * PipeWavesPerEu(kGain) / PipeWaves(kTail, kFront, kDelay, kGain);
     constexpr int by_lds = (int)((160 * 1024) / (sizeof(LdsTables) + (kDelay ? sizeof(PipeShared<kTail, false, kDelay, kGain>) : sizeof(PipeShared<kTail, true>))));
     return by_waves < by_lds ? by_waves : by_lds;
 }
@@ -977,7 +892,7 @@ PipeShape PipelinedShapeFor(int n_streams, int n_blocks, int compute_units, cons
     sh.raw = want_raw && (sh.balance || sh.tail_waves == 2);
     if (sh.balance && !want_raw) sh.balance = false;          // (no balanced instantiation without the raw hand-over)
     // delay waves: the two-tail shapes with formed spectra
-    const int want_delay = delay_waves < 0 ? AECM_PIPE_DELAY_DEFAULT(n_wg, cus) : delay_waves;
+    const int want_delay = delay_waves < 0 ? (PipeDeepShapeByDefault(n_wg, cus) ? kPipeStreams : 0) : delay_waves;
     // (Delay waves where the CU is short of issue slots rather than of independent work -- two delay waves next to four front waves
     // at two workgroups per CU, one for the workgroup's four streams at three and four per CU -- measured slower than the shapes
     // above: 2 048 streams 712 vs 740 M frames/s, 3 072 555 vs 796, 4 096 796 vs 859.  Not instantiated.)
@@ -986,7 +901,7 @@ PipeShape PipelinedShapeFor(int n_streams, int n_blocks, int compute_units, cons
         sh.delay_waves = kPipeStreams;
         sh.raw = false;
         // gain waves: the sixteen-wave shape (four front waves, two delay waves)
-        const int want_gain = gain_waves < 0 ? AECM_PIPE_GAIN_DEFAULT(n_wg, cus) : gain_waves;
+        const int want_gain = gain_waves < 0 ? (PipeDeepShapeByDefault(n_wg, cus) ? kPipeStreams : 0) : gain_waves;
         if (want_gain != 0 && (front_waves < 0 || front_waves == 4) && n_streams <= PipelinedStreamLimit(cus, 2, 4, 2, kPipeStreams, wgs)) {
             sh.gain_waves = kPipeStreams;
             sh.front_waves = 4;
@@ -1051,8 +966,7 @@ hipError_t LaunchProcessBlocksPipelined(const StatePtrs &st, const IoView &io, i
 #endif
 #define AECM_LAUNCH_PIPE(T, B, R, F, D, G) hipLaunchKernelGGL((aecm_process_pipelined_kernel<T, B, R, F, D, G>), grid, block, sizeof(LdsTables) + sizeof(PipeShared<T, R, D, G>), \
                                                               stream, st, io, streams_base, streams_rem, n_blocks, progress, (int)grid.x, shape.wgs_per_round, shape.rot, shape.prio)
-    // The instantiations the library carries (PipelinedShapeFor only ever asks for these).  One tail wave for four streams (kTail = 1,
-    // seven-wave workgroups) measured slower than its neighbours at every size and is not built.
+    // The instantiations the library carries (PipelinedShapeFor only ever asks for these).
     const int key = shape.gain_waves * 10000 + shape.delay_waves * 1000 + shape.tail_waves * 100 + shape.front_waves * 10 + (shape.raw ? 1 : 0);
     if (shape.balance) { if (key != 21) return hipErrorInvalidValue; AECM_LAUNCH_PIPE(0, true, true, 2, 0, 0); }
     else if (key == 20) AECM_LAUNCH_PIPE(0, false, false, 2, 0, 0);
@@ -1090,14 +1004,21 @@ bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_bloc
     return items < (int64_t(1) << 31);
 }
 
+// The grid of a queue launch: what the chip keeps resident (the launch policy's resident_waves), no more than the streams need,
+// never less than one workgroup (any grid drains the queue; a policy of fewer waves than a workgroup has gets one workgroup).
+int QueueGridWorkgroups(int n_streams, int resident_waves) {
+    const int resident_groups = resident_waves / kWavesPerWorkgroup;
+    const int needed = (n_streams + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup;
+    const int groups = needed < resident_groups ? needed : resident_groups;
+    return groups > 0 ? groups : 1;
+}
+
 hipError_t LaunchProcessBlocksQueued(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, int chunk_blocks,
                                      int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream) {
     hipError_t e = hipMemsetAsync(ctl, 0, QueueControlBytes(n_streams), stream);
     if (e != hipSuccess) return e;
     const int n_chunks = (n_blocks + chunk_blocks - 1) / chunk_blocks;
-    const int resident_groups = resident_waves / kWavesPerWorkgroup;
-    const int needed = (n_streams + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup;
-    const dim3 grid(needed < resident_groups ? needed : resident_groups);
+    const dim3 grid(QueueGridWorkgroups(n_streams, resident_waves));
     const dim3 block(64 * kWavesPerWorkgroup);
     const size_t lds = sizeof(LdsTables);
     if (io.near_clean != nullptr)
@@ -1120,9 +1041,7 @@ hipError_t LaunchProcessBlocksRaggedQueued(const StatePtrs &st, const IoView &io
     if (n_streams <= 0 || live_streams <= 0 || n_items == 0 || chunk_blocks <= 0) return hipErrorInvalidValue;
     hipError_t e = hipMemsetAsync(ctl, 0, QueueControlBytes(n_streams), stream);
     if (e != hipSuccess) return e;
-    const int resident_groups = resident_waves / kWavesPerWorkgroup;
-    const int needed = (live_streams + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup;
-    const dim3 grid(needed < resident_groups ? needed : resident_groups);
+    const dim3 grid(QueueGridWorkgroups(live_streams, resident_waves));
     const dim3 block(64 * kWavesPerWorkgroup);
     const size_t lds = sizeof(LdsTables);
     if (io.near_clean != nullptr)

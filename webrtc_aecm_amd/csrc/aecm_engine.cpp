@@ -276,8 +276,8 @@ LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int cou
         d.form = 2;
         d.chunk_blocks = chunk;
         d.waves_per_workgroup = kWavesPerWorkgroup;
-        d.workgroups_per_cu = p.resident_waves / (cus * kWavesPerWorkgroup);
-        d.workgroups = std::min((count + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup, p.resident_waves / kWavesPerWorkgroup);
+        d.workgroups = QueueGridWorkgroups(count, p.resident_waves);
+        d.workgroups_per_cu = std::max(p.resident_waves / (cus * kWavesPerWorkgroup), 1);
         rounds(d);
         return d;
     }

@@ -37,6 +37,8 @@ bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_bloc
 hipError_t LaunchProcessBlocksQueued(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, int chunk_blocks,
                                      int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
 int ResidentWaves(int compute_units);
+// Workgroups of a queue launch (equal-length and ragged) under a policy of resident_waves: never 0.
+int QueueGridWorkgroups(int n_streams, int resident_waves);
 // The ragged queue (aecm_process_ragged_queue_kernel): stream s runs len[s] blocks.  Behind the equal-length form's control words
 // (RaggedPlanOffsetWords(n_streams) words into ctl) lies the plan the host uploads before the launch, on the same stream: len[S],
 // order[S] (streams by length, longest first), first_item[n_chunks + 1] (aecm_engine.h: RaggedPlan).  n_items = first_item[n_chunks].

@@ -128,9 +128,10 @@ struct Uniform {
     // instead of a move + a whole-wave shift.  Entry k (0 = newest) is lane (log_pos + k) mod 20; load_state starts at 0
     // and store_state writes the canonical order back.
     int log_pos;
-    // Not persistent: set by kernels whose policy lowers the issue priority of a wave that has run ahead of the launch's
-    // other waves (wave_gfx950.h: kDynamicPrio; aecm_block_kernels.hip: the pipelined kernel).  0 everywhere else.
-    int prio_drop = 0;
+    // Not state and not read by anything: the place of a removed experiment's flag.  The compiler's register assignment in the
+    // block kernels follows this member list, and the recorded issue-port profiles (profiles/r07_rocprof_summary.json) are keyed
+    // on the kernels' instruction streams: delete it together with the next re-profile of those records, not before.
+    int reserved = 0;
 };
 
 template <class W, bool kHasClean>
@@ -1215,7 +1216,7 @@ struct BlockEngine {
     static AECM_HD void front_block(const Regs &r, vi x_old, vi far_new, vi d_old, vi near_new, vi c_old, vi clean_new,
                                     Spectrum &xf, Spectrum &df, Spectrum &cf) {
         AECM_PHASE_MARK(0, far_new, near_new);
-        W::template phase_priority<1>(r.u.prio_drop);
+        W::template phase_priority<1>();
         {
             constexpr int kSignals = kHasClean ? 3 : 2;
             int max_abs[3], q[3] = {0, 0, 0};
@@ -1231,7 +1232,7 @@ struct BlockEngine {
             fft128<false, true, kSignals, 1>(fa, fb, r.k_p);
             spectrum(r, fa[0], fb[0], q[0], xf);
             AECM_PHASE_MARK(1, xf.mag, xf.re);
-            W::template phase_priority<2>(r.u.prio_drop);
+            W::template phase_priority<2>();
             spectrum(r, fa[1], fb[1], q[1], df);
             if (kHasClean) spectrum(r, fa[kSignals - 1], fb[kSignals - 1], q[2], cf);
         }
@@ -1290,7 +1291,7 @@ struct BlockEngine {
             r.bh1 = W::shift_up1(r.bh1, carry);
         }
         AECM_PHASE_MARK(3, r.bh0, r.mean);
-        W::template phase_priority<4>(r.u.prio_drop);
+        W::template phase_priority<4>();
         // near binary spectrum -> delay (delay_estimator_wrapper.cc:447-476)
         return process_binary(r, near_word);
     }
@@ -1333,7 +1334,7 @@ struct BlockEngine {
     template <bool kDelayGiven = false>
     static AECM_HD TailInput middle_block(Regs &r, uint16_t *hist, const Spectrum &xf, const Spectrum &df, const Spectrum &cf, int delay_given = 0,
                                           vi far_given = vi(0)) {
-        W::template phase_priority<3>(r.u.prio_drop);
+        W::template phase_priority<3>();
         track_q(r.u, df, cf);
         const GainInput g = channel_block<kDelayGiven>(r, hist, xf, df, delay_given, far_given);
         return gain_block(r, df, cf, g);
@@ -1359,7 +1360,7 @@ struct BlockEngine {
         delay = effective_delay(u, delay);
 
         AECM_PHASE_MARK(4, r.m01, r.mean);
-        W::template phase_priority<5>(r.u.prio_drop);
+        W::template phase_priority<5>();
         // AlignedFarend (aecm_core.cc:157-172)
         const int pos = aligned_slot(u.hist_pos, delay);
         int side = pos < 64 ? W::readlane(r.hq0, pos) : W::readlane(r.hq1, pos - 64);
@@ -1371,12 +1372,12 @@ struct BlockEngine {
         vi echo_est;
         int echo_est64;
         AECM_PHASE_MARK(5, far, r.m01);
-        W::template phase_priority<6>(r.u.prio_drop);
+        W::template phase_priority<6>();
         calc_energies(r, far, far64, far_q, df.mag, df.mag64, echo_est, echo_est64);  // :498
         const int mu = calc_step_size(u);                                             // :503
         u.tot_count = add(u.tot_count, 1);                                            // :506
         AECM_PHASE_MARK(6, echo_est, r.near_log);
-        W::template phase_priority<7>(r.u.prio_drop);
+        W::template phase_priority<7>();
         update_channel(r, far, far64, far_q, df.mag, df.mag64, mu, echo_est, echo_est64);   // :511
         GainInput g;
         g.echo_est = echo_est; g.echo_est64 = echo_est64; g.far_q = far_q;
@@ -1392,7 +1393,7 @@ struct BlockEngine {
         const Spectrum &clean = kHasClean ? cf : df;   // "dfw"/"ptrDfaClean" of the reference (T30)
         const vi echo_est = g.echo_est;
         const int echo_est64 = g.echo_est64, far_q = g.far_q;
-        W::template phase_priority<8>(r.u.prio_drop);
+        W::template phase_priority<8>();
         const int sup_gain = calc_suppression_gain(u, g.cur_vad, g.near0, g.stored0);  // :514
 
         vi e;                            // the suppressed spectrum of bins 0..63, packed re | im << 16
@@ -1427,7 +1428,7 @@ struct BlockEngine {
         const int num_pos = (int)__builtin_popcountll(W::ballot(hnl != 0)) + (hnl64 != 0 ? 1 : 0);   // :612-614
 
         AECM_PHASE_MARK(8, hnl, r.b.near_filt);
-        W::template phase_priority<9>(r.u.prio_drop);
+        W::template phase_priority<9>();
         if (AECM_STEADY_ALWAYS(W::per_block(u.mult) == 2)) {                          // :618-648
             hnl = as_i16(sar(mul24(hnl, hnl), 14));
             hnl64 = sext16(sar(mul(hnl64, hnl64), 14));
@@ -1456,13 +1457,13 @@ struct BlockEngine {
         e_re64 = sext16(sar(mul(clean.re64, hnl64) + 8192, 14));
 
         AECM_PHASE_MARK(9, e, hnl);
-        W::template phase_priority<10>(r.u.prio_drop);
+        W::template phase_priority<10>();
         if (AECM_STEADY_ALWAYS(W::per_block(u.cng) == 1))                             // :702-705
             comfort_noise<false>(r, clean, hnl, hnl64, e, e_re64, e_im64);
         }
 
         AECM_PHASE_MARK(10, e, r.b.noise_est);
-        W::template phase_priority<11>(r.u.prio_drop);
+        W::template phase_priority<11>();
         // InverseFFTAndWindow (:193-246) + RealInverseFFT (real_fft.c:74-102):
         // Y[c] = (re[c], -im[c]) for c <= 64, conj-symmetric extension for c > 64 (T7).  The negated imaginary part (int16 wrap)
         // is the upper half times 0xffff modulo 2^16
@@ -1480,7 +1481,7 @@ struct BlockEngine {
     static AECM_HD vi tail_block(Regs &r, vi a, vi b, int clean_q) {
         const int out_cfft = fft128<true, false>(a, b, r.k_p);
         AECM_PHASE_MARK(11, a, b);
-        W::template phase_priority<12>(r.u.prio_drop);
+        W::template phase_priority<12>();
         const int sh = out_cfft - clean_q;
         // lane t holds y[bitrev6(t)] (a) and y[bitrev6(t)+64] (b): real parts only, in the UPPER halves (fft_stage_generic: last_real)
         vi first = as_i16(sar(mad16_hi_uc(a, lane_const<LC_HANN_SYN_LO>(r), 8192), 14));                // :219-221
@@ -1488,7 +1489,7 @@ struct BlockEngine {
         vi second = sar(mad16_hi_uc(b, lane_const<LC_HANN_SYN_HI>(r), 0), 14);                          // :229-234
         r.out_ovl = sat16(shift_i31(second, vi(sh)));
         AECM_PHASE_MARK(12, out, r.out_ovl);
-        W::template phase_priority<13>(r.u.prio_drop);
+        W::template phase_priority<13>();
         return out;
     }
 

@@ -8,6 +8,7 @@ recorded issue-port figures only when the fingerprint of the library it just tim
 figures were measured on.
 
     python -m webrtc_aecm_amd.isa_census [lib.so]        # prints the census as JSON
+    python -m webrtc_aecm_amd.isa_census --all [lib.so]  # {kernel symbol: fingerprint, n_instructions} of every kernel
 """
 from __future__ import annotations
 
@@ -160,6 +161,10 @@ def census(lib_path, kernel_substr: str = HEADLINE_KERNEL):
 
 if __name__ == "__main__":
     from . import build as _build
+    if len(sys.argv) > 1 and sys.argv[1] == "--all":       # every kernel of the library: what two builds are compared by
+        all_k = census_of_text(disassemble(sys.argv[2] if len(sys.argv) > 2 else _build.LIB))
+        print(json.dumps({k: dict(fingerprint=c["fingerprint"], n_instructions=c["n_instructions"]) for k, c in sorted(all_k.items())}, indent=1))
+        sys.exit(0)
     lib = sys.argv[1] if len(sys.argv) > 1 else _build.LIB
     c = census(lib, sys.argv[2] if len(sys.argv) > 2 else HEADLINE_KERNEL)
     c["opcodes"] = dict(list(c["opcodes"].items())[:40])
