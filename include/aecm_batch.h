@@ -311,6 +311,19 @@ int32_t WebRtcAecmBatch_SetLaunchChunking(AecmBatch *b, int32_t chunk_blocks, in
  * they save there); after this call launches of any length from min_streams streams are pipelined.  (Shorthand for
  * pipelined_min_streams / pipelined_min_blocks of AecmLaunchPolicy, below; its pipe_* fields override the shape.) */
 int32_t WebRtcAecmBatch_SetLaunchPipelining(AecmBatch *b, int32_t min_streams);
+/* Ragged launches (WebRtcAecmBatch_ProcessBlocksRagged, WebRtcAecmBatch_ProcessRecordingsRagged) that the chip holds at once, pipelined:
+ * enable != 0 and such a launch takes the pipelined form above instead of one wavefront per stream when the fast variant is selected,
+ * there is no clean near-end input, the streams that have blocks to run (not the batch's size: 100 live streams of 65 536 qualify) are
+ * within [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks.  All lengths equal
+ * stays the equal-length launch, and the chunk queue keeps what it takes today.  A workgroup still marches its (up to) four streams in
+ * lock step -- every wavefront executes as many barriers as the workgroup's longest stream has blocks -- and a slot whose stream has
+ * ended only keeps the barriers.  Which stream shares a workgroup and a compute unit with which is planned on the host, longest first
+ * onto the unit with the fewest blocks (WebRtcAecmBatch_RaggedPipePlan).  The unbalanced shapes only: a launch whose size would
+ * pick the balanced six-wavefront shape takes the plain one.  Per batch; OFF by default: the form is new, and although it measured
+ * 1.3 to 2.9 times the one-wavefront-per-stream launch at 256 ... 4 096 streams (profiles/r10_ragged_pipelined.txt), which kernel
+ * existing callers run is changed in a step of its own, not as a side effect of adding the form.
+ * Results never depend on it.  AECM_BAD_PARAMETER_ERROR for a NULL batch. */
+int32_t WebRtcAecmBatch_SetRaggedPipelining(AecmBatch *b, int32_t enable);
 /* Which form a ProcessBlocks launch of num_blocks blocks over the whole batch takes, with (has_clean_input != 0) or
  * without a clean near-end input (for measurement tools that must name
  * the kernel they time): 0 = one wavefront per stream, kernel variants for launches the chip holds at once; 1 = one
@@ -379,12 +392,34 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int
                                              int32_t has_clean_input, AecmLaunchDescription *out);
 /* The same for a ragged launch (WebRtcAecmBatch_ProcessBlocksRagged) of num_streams streams with these lengths, no device needed: form,
  * chunk and grid as above -- the chunk queue when more streams than the queue's threshold have blocks to run and the longest has at
- * least two chunks, else one wavefront per stream; never pipelined; every length equal: exactly DescribeLaunchDetail of that length --
+ * least two chunks, else one wavefront per stream; never pipelined (this call describes a batch that has not opted in:
+ * WebRtcAecmBatch_SetRaggedPipelining, WebRtcAecmBatch_DescribeRaggedLaunchEx); every length equal: exactly DescribeLaunchDetail of that length --
  * plus the queue's item count (*items = sum of ceil(length / chunk); 0 for the other forms), and the sum and the maximum of the
  * lengths in blocks: the useful work and the critical path.  items / sum_blocks / max_blocks may be NULL. */
 int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
                                              const int32_t *blocks_per_stream_host, int32_t has_clean_input, AecmLaunchDescription *out,
                                              int64_t *items, int64_t *sum_blocks, int32_t *max_blocks);
+/* WebRtcAecmBatch_DescribeRaggedLaunch with the batch's opt-in (WebRtcAecmBatch_SetRaggedPipelining) as an argument.  ragged_pipelining
+ * = 0: exactly that call's answer.  Otherwise a launch the rule of SetRaggedPipelining takes is described as form 3: shape as
+ * DescribeLaunchDetail gives it (chunk_blocks 0), the workgroups of the plan (up to the last one that holds a stream), and
+ * cu_load_evenness_x1000 = 1000 x (mean blocks per compute unit) / (blocks on the fullest unit) -- the launch ends when that unit
+ * does.  The mean is over the units the launch's shape puts workgroups on, min(compute units, workgroups of the shape): a launch of
+ * fewer workgroups than the device has units (100 live streams on 256 units) is not called uneven for the units it leaves idle. */
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                               const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
+                                               AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks);
+/* The same for the launch WebRtcAecmBatch_ProcessBlocksRagged would make on THIS batch (blocks_per_stream_host: its num_streams
+ * entries): under its launch policy, its kernel variant (a batch on the safe variant is never pipelined) and its
+ * WebRtcAecmBatch_SetRaggedPipelining switch -- what the engine itself decides by.  -1 for a NULL batch. */
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchOf(const AecmBatch *b, const int32_t *blocks_per_stream_host, int32_t has_clean_input,
+                                               AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks);
+/* Diagnostics: the plan a ragged pipelined launch runs by, whether or not the launch rule would pick the form.  slot_stream[4 x
+ * *workgroups] (capacity entries available; 4 x 4 x compute units always suffice under the default policy): the stream in each of
+ * the four slots of each workgroup, -1 = empty.  Workgroups i, i + compute units, ... share a compute unit.  Streams of length 0
+ * appear nowhere.  AECM_BAD_PARAMETER_ERROR: no stream has blocks, more of them have than pipelined_max_streams, a negative length,
+ * or too small a capacity. */
+int32_t WebRtcAecmBatch_RaggedPipePlan(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                       const int32_t *blocks_per_stream_host, int32_t *slot_stream, int32_t capacity, int32_t *workgroups);
 /* Diagnostics: the plan a ragged chunk-queue launch with chunks of chunk_blocks blocks runs by.  order[num_streams]: the streams by
  * length, longest first (equal lengths in stream order); *num_chunks = ceil(longest / chunk_blocks); first_item[*num_chunks + 1]
  * (first_item_capacity entries available): the items of chunk c are the numbers first_item[c] .. first_item[c + 1], item

@@ -17,6 +17,21 @@ repetition of (a) is faster than every repetition of (b).
 Every point runs in a child process of its own under a time limit; the first child that fails ends the run.
 
     python tools/bench_ragged.py [--sizes 65536,8192] [--blocks 1280] [--reps 5] [--timeout 300]
+
+--pipelined: what the pipelined form of a ragged launch the chip holds at once (WebRtcAecmBatch_SetRaggedPipelining) is worth.
+For S in --sizes (default 256, 1 024, 2 048, 3 072, 4 096 and two non-multiples of the CU count), T = --blocks (default 2 048 here)
+and the distributions uniform and one_long (1 % of the streams 8 x the common length) it records useful frames/s of
+    (a) parent      the library given with --parent (a build of the parent commit: tools/ab_build.py or a copy of its shipped
+                    library under webrtc_aecm_amd/_lib/) running the same ragged launch -- one wavefront per stream
+    (b) off         this build with the switch off
+    (c) on          this build with the switch on
+    (d) equal       this build's equal-length pipelined launch of the same total work (sum of the lengths / S blocks per stream)
+(tools/ab.sh, the usual way to interleave two builds, times bench.py, and bench.py issues equal-length launches only; so this tool
+does the interleaving itself, the same way: one child process per library, $AECM_LIB_PATH naming the library.)
+(a) and (b, c, d) run in child processes of their own, interleaved --passes times; the spread of a figure over the passes and the
+repetitions inside them is printed next to it, and (c) is called faster than (a) only when their ranges do not overlap.
+
+    python tools/bench_ragged.py --pipelined --parent webrtc_aecm_amd/_lib/ab_parent.so [--sizes ...] [--blocks 2048] [--reps 4] [--passes 2]
 """
 from __future__ import annotations
 
@@ -88,6 +103,94 @@ def point(S, T, dist, reps, fs):
     batch.close()
 
 
+def pipelined_point(S, T, reps, fs, with_switch):
+    """One child: both distributions at one size on the library $AECM_LIB_PATH names (or the shipped one)."""
+    import torch
+
+    import webrtc_aecm_amd as aecm
+    from bench import synth_on_device
+    device = torch.device("cuda", 0)
+    far, near = synth_on_device(torch, S, T * 64, 1234, device)
+    out = torch.empty_like(near)
+    ptrs = (far.data_ptr(), near.data_ptr(), out.data_ptr(), far.shape[1], 64)
+    for dist in ("uniform", "one_long"):
+        lens = lengths(dist, S, T)
+        total = int(lens.sum())
+        t_equal = max(1, total // S)
+        batch = aecm.AecmBatch(S, fs, cng_mode=1, echo_mode=1, device=0)
+        runs = {}
+        if with_switch:
+            def on():
+                batch.set_ragged_pipelining(True)
+                batch.process_ragged_device(*ptrs, T, lens)
+
+            def off():
+                batch.set_ragged_pipelining(False)
+                batch.process_ragged_device(*ptrs, T, lens)
+            runs = {"off": off, "on": on, "equal": lambda: batch.process_device(*ptrs, t_equal)}
+        else:
+            runs = {"parent": lambda: batch.process_ragged_device(*ptrs, T, lens)}
+        wall = {k: [] for k in runs}
+        for run in runs.values():
+            run()
+        batch.synchronize()
+        for _ in range(reps):
+            for name, run in runs.items():
+                t0 = time.perf_counter()
+                run()
+                batch.synchronize()
+                wall[name].append(time.perf_counter() - t0)
+        useful = {k: (S * t_equal if k == "equal" else total) for k in runs}
+        rec = {"streams": S, "blocks": T, "dist": dist, "sum_blocks": total, "frames_per_s": {k: [useful[k] / t for t in wall[k]] for k in runs}}
+        if with_switch:
+            batch.set_ragged_pipelining(True)
+            d = batch.describe_ragged_launch(lens)
+            rec.update(form_on=d["form"], shape_on=d["shape"], workgroups_on=d["workgroups"], evenness_on=d["cu_load_evenness_x1000"])
+        print("RESULT " + json.dumps(rec), flush=True)
+        batch.close()
+
+
+def pipelined_main(a):
+    import os
+    sizes = [int(x) for x in (a.sizes if a.sizes != "65536,8192" else "256,1024,1030,2048,3072,3000,4096").split(",")]
+    T = a.blocks if a.blocks != 1280 else 2048
+    acc = {}
+    for p in range(a.passes):
+        for S in sizes:
+            for variant in (("parent", "new") if a.parent else ("new",)):
+                env = dict(os.environ)
+                if variant == "parent":
+                    env["AECM_LIB_PATH"] = str(Path(a.parent).resolve())
+                cmd = [sys.executable, str(Path(__file__).resolve()), "--pipelined-point", str(S), variant, "--blocks", str(T), "--reps", str(a.reps), "--fs", str(a.fs)]
+                try:
+                    r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout, env=env)
+                except subprocess.TimeoutExpired:
+                    print(f"{S} streams, {variant}: no result within {a.timeout} s; stopping", flush=True)
+                    return 2
+                lines = [l for l in r.stdout.splitlines() if l.startswith("RESULT ")]
+                if r.returncode != 0 or len(lines) != 2:
+                    print(f"{S} streams, {variant}: child failed with status {r.returncode}; stopping\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}", flush=True)
+                    return 2
+                for line in lines:
+                    rec = json.loads(line[7:])
+                    slot = acc.setdefault((S, rec["dist"]), {"sum_blocks": rec["sum_blocks"], "f": {}})
+                    for k, v in rec["frames_per_s"].items():
+                        slot["f"].setdefault(k, []).extend(v)
+                    slot.update({k: rec[k] for k in ("form_on", "shape_on", "workgroups_on", "evenness_on") if k in rec})
+    print(f"T = {T} blocks, {a.passes} interleaved passes x {a.reps} repetitions; M useful frames/s, min .. max over all of them")
+    print(f"{'streams':>7} {'dist':>8} {'(a) parent':>17} {'(b) off':>17} {'(c) on':>17} {'(d) equal':>17}  form/shape/wgs/evenness  verdict")
+    for (S, dist), slot in sorted(acc.items()):
+        f = slot["f"]
+        cell = lambda k: f"{min(f[k]) / 1e6:7.1f} ..{max(f[k]) / 1e6:7.1f}" if k in f else f"{'-':>17}"
+        verdict = ""
+        if "parent" in f:
+            verdict = "on > parent" if min(f["on"]) > max(f["parent"]) else "on < parent" if max(f["on"]) < min(f["parent"]) else "within the spread"
+            verdict += "; off = parent" if min(f["off"]) <= max(f["parent"]) and min(f["parent"]) <= max(f["off"]) else "; off != parent"
+        print(f"{S:7d} {dist:>8} {cell('parent')} {cell('off')} {cell('on')} {cell('equal')}  {slot.get('form_on')}/{slot.get('shape_on', 0):#x}/{slot.get('workgroups_on')}/{slot.get('evenness_on')}  {verdict}",
+              flush=True)
+    return 0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="65536,8192")
@@ -96,7 +199,16 @@ def main():
     ap.add_argument("--fs", type=int, default=16000)
     ap.add_argument("--timeout", type=int, default=300, help="seconds per point (one child process each)")
     ap.add_argument("--point", nargs=2, metavar=("STREAMS", "DIST"), help="(internal) run one point in this process")
+    ap.add_argument("--pipelined", action="store_true", help="the sweep of the ragged pipelined form (see the module text)")
+    ap.add_argument("--parent", help="--pipelined: a library built from the parent commit, for column (a)")
+    ap.add_argument("--passes", type=int, default=2, help="--pipelined: interleaved passes over the libraries")
+    ap.add_argument("--pipelined-point", nargs=2, metavar=("STREAMS", "VARIANT"), help="(internal) one size on one library in this process")
     a = ap.parse_args()
+    if a.pipelined_point:
+        pipelined_point(int(a.pipelined_point[0]), a.blocks, a.reps, a.fs, a.pipelined_point[1] == "new")
+        return 0
+    if a.pipelined:
+        return pipelined_main(a)
     if a.point:
         point(int(a.point[0]), a.blocks, a.point[1], a.reps, a.fs)
         return 0

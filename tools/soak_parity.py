@@ -34,6 +34,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=4096, help="streams checked per host round trip")
     ap.add_argument("--ragged", action="store_true", help="every stream its own length, uniform in [blocks / 4, blocks]: each pass is one "
                     "WebRtcAecmBatch_ProcessBlocksRagged launch, every stream is checked over its own first blocks (forces --passes 1)")
+    ap.add_argument("--ragged-pipelining", action="store_true", help="with --ragged: the batch opts into the pipelined form "
+                    "(WebRtcAecmBatch_SetRaggedPipelining) for launches the chip holds at once")
     a = ap.parse_args()
 
     import torch
@@ -54,6 +56,8 @@ def main():
         a.passes = 1
         lens = np.random.RandomState(a.seed).randint(T // 4, T + 1, size=S).astype(np.int32)
         lens[0] = T
+        if a.ragged_pipelining:
+            batch.set_ragged_pipelining(True)
         batch.process_ragged_device(far.data_ptr(), near.data_ptr(), out.data_ptr(), far.shape[1], 64, T, lens,
                                     clean.data_ptr() if clean is not None else None)
     for _ in range(0 if a.ragged else a.passes):
@@ -97,7 +101,7 @@ def main():
             "ok": not bad_streams, "mismatching_streams": bad_streams[:32], "mismatching_samples": bad_samples,
             "mismatching_digests": bad_digests, "cpu_cores": cores, "cpu_seconds_wall": round(time.perf_counter() - t0, 1),
             "launch_form": dict(zip(("form", "chunk_blocks"), batch.describe_launch(T, bool(a.clean)))) if lens is None else
-                           {k: v for k, v in batch.describe_ragged_launch(lens, bool(a.clean)).items() if k in ("form", "chunk_blocks", "items")},      # 2 = chunk queue (include/aecm_batch.h)
+                           {k: v for k, v in batch.describe_ragged_launch(lens, bool(a.clean)).items() if k in ("form", "chunk_blocks", "items", "shape", "workgroups")},      # 2 = chunk queue (include/aecm_batch.h)
             "library": str(aecm.library_path()), "build": _build.build_info()}
     print(json.dumps(line))
     return 0 if not bad_streams else 1

@@ -355,6 +355,12 @@ int32_t WebRtcAecmBatch_SetLaunchPipelining(AecmBatch *b, int32_t min_streams) {
     return 0;
 }
 
+int32_t WebRtcAecmBatch_SetRaggedPipelining(AecmBatch *b, int32_t enable) {
+    if (!b) return AECM_BAD_PARAMETER_ERROR;
+    b->engine->set_ragged_pipelining(enable != 0);
+    return 0;
+}
+
 int32_t WebRtcAecmBatch_DescribeLaunch(const AecmBatch *b, int32_t num_blocks, int32_t has_clean_input, int32_t *chunk_blocks) {
     if (!b) return -1;
     return b->engine->DescribeLaunch(num_blocks, has_clean_input != 0, chunk_blocks);
@@ -440,33 +446,86 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int
     return 0;
 }
 
-int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
-                                             const int32_t *blocks_per_stream_host, int32_t has_clean_input, AecmLaunchDescription *out,
-                                             int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
-    if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
+// The policy a planning call runs by (the caller's, or the default one of compute_units) and the longest of the lengths; 0 or the error code.
+static int32_t RaggedPlanningArguments(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, const int32_t *lens,
+                                       aecm::LaunchPolicy *p, int32_t *longest) {
     if (num_streams <= 0) return AECM_BAD_PARAMETER_ERROR;
-    aecm::LaunchPolicy p;
     if (policy) {
         if (policy->struct_size != (int32_t)sizeof(AecmLaunchPolicy)) return AECM_BAD_PARAMETER_ERROR;
-        p = PolicyFromAbi(*policy);
-        if (!aecm::LaunchPolicyValid(p) || p.compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
+        *p = PolicyFromAbi(*policy);
+        if (!aecm::LaunchPolicyValid(*p) || p->compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
     } else {
         if (compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
-        p = aecm::DefaultLaunchPolicy(compute_units);
+        *p = aecm::DefaultLaunchPolicy(compute_units);
     }
-    int32_t longest = 0;
+    *longest = 0;
     for (int32_t s = 0; s < num_streams; ++s) {
-        if (blocks_per_stream_host[s] < 0) return AECM_BAD_PARAMETER_ERROR;
-        if (blocks_per_stream_host[s] > longest) longest = blocks_per_stream_host[s];
+        if (lens[s] < 0) return AECM_BAD_PARAMETER_ERROR;
+        if (lens[s] > *longest) *longest = lens[s];
     }
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                               const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
+                                               AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
+    if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
+    aecm::LaunchPolicy p;
+    int32_t longest = 0;
+    if (const int32_t rc = RaggedPlanningArguments(policy, compute_units, num_streams, blocks_per_stream_host, &p, &longest)) return rc;
     aecm::RaggedPlan plan;
     const aecm::LaunchDescription d = aecm::DescribeRaggedLaunchWith(p, aecm::kVariantFast, num_streams, longest, blocks_per_stream_host,
-                                                                     has_clean_input != 0, &plan);
+                                                                     has_clean_input != 0, &plan, ragged_pipelining != 0, nullptr);
     if (d.form < 0) return AECM_BAD_PARAMETER_ERROR;
     DescriptionToAbi(d, out);
     if (items) *items = d.form == 2 ? plan.items : 0;
     if (sum_blocks) *sum_blocks = plan.sum_blocks;
     if (max_blocks) *max_blocks = plan.max_blocks;
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                             const int32_t *blocks_per_stream_host, int32_t has_clean_input, AecmLaunchDescription *out,
+                                             int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
+    return WebRtcAecmBatch_DescribeRaggedLaunchEx(policy, compute_units, num_streams, blocks_per_stream_host, has_clean_input, 0, out, items,
+                                                  sum_blocks, max_blocks);
+}
+
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchOf(const AecmBatch *b, const int32_t *blocks_per_stream_host, int32_t has_clean_input,
+                                               AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
+    if (!b) return -1;
+    if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
+    int32_t longest = 0;
+    for (int32_t s = 0; s < b->engine->num_streams(); ++s) {
+        if (blocks_per_stream_host[s] < 0) return AECM_BAD_PARAMETER_ERROR;
+        if (blocks_per_stream_host[s] > longest) longest = blocks_per_stream_host[s];
+    }
+    aecm::RaggedPlan plan;
+    const aecm::LaunchDescription d = b->engine->DescribeRaggedLaunch(longest, blocks_per_stream_host, has_clean_input != 0, &plan);
+    if (d.form < 0) return AECM_BAD_PARAMETER_ERROR;
+    DescriptionToAbi(d, out);
+    if (items) *items = d.form == 2 ? plan.items : 0;
+    if (sum_blocks) *sum_blocks = plan.sum_blocks;
+    if (max_blocks) *max_blocks = plan.max_blocks;
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_RaggedPipePlan(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                       const int32_t *blocks_per_stream_host, int32_t *slot_stream, int32_t capacity, int32_t *workgroups) {
+    if (!blocks_per_stream_host || !slot_stream || !workgroups) return AECM_NULL_POINTER_ERROR;
+    aecm::LaunchPolicy p;
+    int32_t longest = 0;
+    if (const int32_t rc = RaggedPlanningArguments(policy, compute_units, num_streams, blocks_per_stream_host, &p, &longest)) return rc;
+    int32_t live = 0;
+    for (int32_t s = 0; s < num_streams; ++s) live += blocks_per_stream_host[s] > 0;
+    if (live == 0 || live > p.pipelined_max_streams) return AECM_BAD_PARAMETER_ERROR;
+    aecm::RaggedPipePlan plan;
+    if (!aecm::BuildRaggedPipePlan(blocks_per_stream_host, num_streams, aecm::RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe),
+                                   p.compute_units, &plan))
+        return AECM_BAD_PARAMETER_ERROR;
+    if (capacity < 4 * plan.workgroups) return AECM_BAD_PARAMETER_ERROR;
+    *workgroups = plan.workgroups;
+    for (int32_t i = 0; i < 4 * plan.workgroups; ++i) slot_stream[i] = plan.slot_stream()[i];
     return 0;
 }
 

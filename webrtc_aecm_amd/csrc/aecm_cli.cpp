@@ -208,7 +208,7 @@ int ProcessPair(Wav &far_w, Wav &near_w) {
     return 1;
 }
 
-int RunBatch(const char *list_path, const std::vector<int> &devices) {
+int RunBatch(const char *list_path, const std::vector<int> &devices, bool ragged_pipelining) {
     FILE *f = fopen(list_path, "r");
     if (!f) { fprintf(stderr, "cannot open %s\n", list_path); return 1; }
     struct Job { std::string far_path, near_path; Wav far_w, near_w; };
@@ -267,6 +267,7 @@ int RunBatch(const char *list_path, const std::vector<int> &devices) {
                 const auto s0 = std::chrono::steady_clock::now();
                 int32_t rc = WebRtcAecmBatch_Init(batch, (int32_t)rate);
                 if (rc == 0) rc = WebRtcAecmBatch_set_config(batch, cfg, 0, -1);
+                if (rc == 0 && ragged_pipelining) rc = WebRtcAecmBatch_SetRaggedPipelining(batch, 1);
                 if (rc == 0)
                     rc = WebRtcAecmBatch_ProcessRecordingsRaggedHost(batch, &far_all[first * stride], &near_all[first * stride], /*nearendClean*/ nullptr,
                                                                      &out_all[first * stride], (int64_t)stride, frame, (int32_t)max_calls,
@@ -305,7 +306,7 @@ int RunBatch(const char *list_path, const std::vector<int> &devices) {
 
 int main(int argc, char **argv) {
     printf("WebRTC Acoustic Echo Canceller for Mobile -- MI355X engine\n");
-    printf("usage : aecm_run [--device N] far_file.wav near_file.wav | aecm_run --batch pairs.txt [--devices 0,1,...] | aecm_run --decode in.wav out.wav\n");
+    printf("usage : aecm_run [--device N] far_file.wav near_file.wav | aecm_run --batch pairs.txt [--devices 0,1,...] [--ragged-pipelining] | aecm_run --decode in.wav out.wav\n");
     if (argc >= 3 && strcmp(argv[1], "--device") == 0) {     // the HIP device of the single-pair form (WebRtcAecm_Create has no device argument)
         WebRtcAecm_SetDefaultDevice(atoi(argv[2]));
         argv += 2;
@@ -320,16 +321,21 @@ int main(int argc, char **argv) {
     }
     if (strcmp(argv[1], "--batch") == 0) {
         // --devices: HIP device ids to shard the recordings over (one host thread + one batch each); default: device 0
+        // --ragged-pipelining: recordings of different lengths the chip holds at once run pipelined (WebRtcAecmBatch_SetRaggedPipelining; default off)
         std::vector<int> devices;
-        if (argc >= 5 && strcmp(argv[3], "--devices") == 0) {
-            for (const char *p = argv[4]; *p;) {
-                devices.push_back(atoi(p));
-                while (*p && *p != ',') ++p;
-                if (*p == ',') ++p;
+        bool ragged_pipelining = false;
+        for (int i = 3; i < argc; ++i) {
+            if (strcmp(argv[i], "--ragged-pipelining") == 0) ragged_pipelining = true;
+            else if (strcmp(argv[i], "--devices") == 0 && i + 1 < argc && devices.empty()) {
+                for (const char *p = argv[++i]; *p;) {
+                    devices.push_back(atoi(p));
+                    while (*p && *p != ',') ++p;
+                    if (*p == ',') ++p;
+                }
             }
         }
         if (devices.empty()) devices.push_back(0);
-        return RunBatch(argv[2], devices);
+        return RunBatch(argv[2], devices, ragged_pipelining);
     }
     Wav far_w, near_w;
     if (!ReadWav(argv[2], &near_w) || !ReadWav(argv[1], &far_w)) { printf("failed to read wav files.\n"); return 1; }

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <atomic>
 #include <thread>
+#include <utility>
 #include <vector>
 
 namespace aecm {
@@ -349,8 +350,76 @@ bool BuildRaggedPlan(const int32_t *lens, int S, int num_blocks, int chunk_block
     return true;
 }
 
+PipeShape RaggedPipeShapeFor(int live, int max_blocks, int compute_units, const PipeWishes &wishes) {
+    PipeShape sh = PipelinedShapeFor(live, max_blocks, compute_units, wishes);
+    if (sh.balance) {                 // the size that picks the balanced six-wave shape takes the plain one (no ragged instantiation of it)
+        sh.balance = false;
+        sh.raw = false;
+    }
+    return sh;
+}
+
+// The plan of a ragged pipelined launch (aecm_engine.h: RaggedPipePlan).  O(S + longest) for the order (BuildRaggedPlan's counting
+// sort), O(live x log cus) for the placement.
+bool BuildRaggedPipePlan(const int32_t *lens, int S, const PipeShape &shape, int compute_units, RaggedPipePlan *plan) {
+    RaggedPipePlan &p = *plan;
+    p = RaggedPipePlan();
+    p.shape = shape;
+    if (S <= 0 || !lens || shape.balance || shape.workgroups <= 0) return false;
+    int longest = 0;
+    for (int s = 0; s < S; ++s) {
+        if (lens[s] < 0) return false;
+        longest = std::max(longest, (int)lens[s]);
+    }
+    RaggedPlan sorted;
+    if (!BuildRaggedPlan(lens, S, longest, 0, &sorted) || sorted.live_streams == 0) return false;
+    const int cus = compute_units > 0 ? compute_units : 256, W = shape.workgroups, live = sorted.live_streams;
+    if ((int64_t)W * 4 < live) return false;
+    p.num_streams = S;
+    p.live_streams = live;
+    p.max_blocks = sorted.max_blocks;
+    p.sum_blocks = sorted.sum_blocks;
+    p.used_cus = std::min(cus, W);
+    // longest first onto the unit with the fewest blocks that has a free slot: a min-heap of (blocks, unit); a full unit leaves it
+    std::vector<std::vector<uint32_t>> of_cu((size_t)p.used_cus);
+    std::vector<std::pair<int64_t, int>> heap;
+    heap.reserve((size_t)p.used_cus);
+    for (int c = 0; c < p.used_cus; ++c) heap.emplace_back(0, c);
+    auto later = [](const std::pair<int64_t, int> &a, const std::pair<int64_t, int> &b) { return a > b; };      // (heap of the smallest)
+    const auto wgs_of = [&](int c) { return (W - c + cus - 1) / cus; };      // workgroups c, c + cus, ... < W
+    const uint32_t *order = sorted.order();
+    for (int r = 0; r < live; ++r) {
+        const uint32_t s = order[r];
+        std::pop_heap(heap.begin(), heap.end(), later);
+        std::pair<int64_t, int> &least = heap.back();
+        of_cu[(size_t)least.second].push_back(s);
+        least.first += lens[s];
+        p.fullest_cu_blocks = std::max(p.fullest_cu_blocks, least.first);
+        if ((int)of_cu[(size_t)least.second].size() == 4 * wgs_of(least.second)) heap.pop_back();
+        else std::push_heap(heap.begin(), heap.end(), later);
+    }
+    // a unit's streams (already longest first) in consecutive runs over its workgroups; slots 0, 2, 1, 3 by length
+    static const int kSlotOrder[4] = {0, 2, 1, 3};
+    std::vector<int32_t> slots((size_t)W * 4, -1);
+    for (int c = 0; c < p.used_cus; ++c) {
+        const std::vector<uint32_t> &mine = of_cu[(size_t)c];
+        const int g = wgs_of(c), n = (int)mine.size(), base = n / g, rem = n % g;
+        int at = 0;
+        for (int j = 0; j < g; ++j) {
+            const int wg = c + j * cus, take = base + (j < rem ? 1 : 0);
+            for (int k = 0; k < take; ++k) slots[(size_t)wg * 4 + kSlotOrder[k]] = (int32_t)mine[(size_t)at + k];
+            at += take;
+            if (take > 0) p.workgroups = std::max(p.workgroups, wg + 1);
+        }
+    }
+    p.words.resize((size_t)p.workgroups * 4 + (size_t)S);
+    for (size_t i = 0; i < (size_t)p.workgroups * 4; ++i) p.words[i] = (uint32_t)slots[i];
+    for (int s = 0; s < S; ++s) p.words[(size_t)p.workgroups * 4 + s] = (uint32_t)lens[s];
+    return true;
+}
+
 LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, const int32_t *lens, bool has_clean,
-                                           RaggedPlan *plan_out) {
+                                           RaggedPlan *plan_out, bool ragged_pipelining, RaggedPipePlan *pipe_out) {
     RaggedPlan local;
     RaggedPlan &plan = plan_out ? *plan_out : local;
     LaunchDescription d;
@@ -385,6 +454,23 @@ LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, i
         q.queue_chunk_explicit = true;
         q.queue_min_streams = 0;
         d = DescribeLaunchWith(q, variant, chunk ? live : count, longest, has_clean);
+        // the opt-in: a ragged launch the chip holds at once, pipelined -- by the LIVE streams, not the batch's size
+        if (ragged_pipelining && chunk == 0 && PipelinedLaunchApplies(p, variant, live, longest, has_clean, false)) {
+            RaggedPipePlan pipe_local;
+            RaggedPipePlan &pipe = pipe_out ? *pipe_out : pipe_local;
+            const PipeShape sh = RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe);
+            if (BuildRaggedPipePlan(lens, count, sh, p.compute_units, &pipe)) {
+                const int cus = p.compute_units > 0 ? p.compute_units : 256;
+                d = LaunchDescription();
+                d.form = 3;
+                d.shape = PipeShapeBits(sh);
+                d.workgroups = pipe.workgroups;
+                d.waves_per_workgroup = PipelinedWorkgroupWaves(sh);
+                d.workgroups_per_cu = p.pipe.wgs_per_cu > 0 ? p.pipe.wgs_per_cu : PipelinedWorkgroupsPerCu(sh);
+                d.rounds_x1000 = (int)((int64_t)1000 * d.workgroups / ((int64_t)cus * std::max(1, d.workgroups_per_cu)));
+                d.cu_load_evenness_x1000 = pipe.evenness_x1000();
+            }
+        }
     }
     BuildRaggedPlan(lens, count, num_blocks, chunk, &plan);
     return d;
@@ -422,14 +508,14 @@ bool BatchEngine::EnsurePlanStaging(size_t words) {
     return plan_uploaded_ || AECM_HIP_OK(hipEventCreateWithFlags(&plan_uploaded_, hipEventDisableTiming));
 }
 
-bool BatchEngine::UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev) {
-    const size_t words = plan.words.size();
+bool BatchEngine::UploadPlanWords(const std::vector<uint32_t> &plan_words, uint32_t *dst_dev) {
+    const size_t words = plan_words.size();
     if (plan_upload_pending_) {
         if (!AECM_HIP_OK(hipEventSynchronize(plan_uploaded_))) return false;
         plan_upload_pending_ = false;
     }
     if (!EnsurePlanStaging(words)) return false;
-    memcpy(plan_host_, plan.words.data(), words * sizeof(uint32_t));
+    memcpy(plan_host_, plan_words.data(), words * sizeof(uint32_t));
     if (!AECM_HIP_OK(hipMemcpyAsync(dst_dev, plan_host_, words * sizeof(uint32_t), hipMemcpyHostToDevice, stream_))) return false;
     if (!AECM_HIP_OK(hipEventRecord(plan_uploaded_, stream_))) return false;
     plan_upload_pending_ = true;
@@ -437,8 +523,15 @@ bool BatchEngine::UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev) {
 }
 
 bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev,
-                               const RaggedPlan *ragged, int ragged_form) {
+                               const RaggedPlan *ragged, int ragged_form, const RaggedPipePlan *pipe) {
     if (launch_failed_) return false;                 // streams half processed by an abandoned launch: nothing runs until Init
+    if (ragged && ragged_form == 3) {
+        // the pipelined form: its plan (slots, then lengths) at the start of the control buffer; no control words, nothing to clear
+        if (!pipe || pipe->num_streams != count) return false;
+        if (!EnsureLaunchControl(pipe->words.size() * sizeof(uint32_t))) return false;
+        if (!UploadPlanWords(pipe->words, queue_ctl_)) return false;
+        return AECM_HIP_OK(LaunchProcessBlocksPipelinedRagged(st, io, count, pipe->shape, pipe->workgroups, queue_ctl_, stream_));
+    }
     if (ragged) {
         // one upload per launch, on the engine's stream, behind the control words the queue form clears: the whole plan for the queue,
         // for one wavefront per stream its first part (the lengths) is what aecm_process_kernel reads
@@ -527,15 +620,19 @@ int32_t BatchEngine::ProcessBlocksRagged(const IoView &io, int num_blocks, const
 int32_t BatchEngine::ProcessBlocksRaggedRange(const IoView &io, int num_blocks, int first, int count, const int32_t *lens) {
     if (first < 0 || count < 0 || first + count > num_streams_ || num_blocks < 0 || !lens) return kErrBadParameter;
     RaggedPlan plan;
-    const LaunchDescription d = DescribeRaggedLaunchWith(policy_, variant_, count, num_blocks, lens, io.near_clean != nullptr, &plan);
+    RaggedPipePlan pipe;
+    const LaunchDescription d = DescribeRaggedLaunchWith(policy_, variant_, count, num_blocks, lens, io.near_clean != nullptr, &plan, ragged_pipelining_, &pipe);
     if (d.form < 0) return kErrBadParameter;
     if (plan.max_blocks == 0) return 0;
     if (plan.sum_blocks == (int64_t)count * plan.max_blocks)          // every stream the same length: today's launch, whatever its form
         return TimedLaunch(io, plan.max_blocks, first, count, nullptr, nullptr, 0) ? 0 : kErrUnspecified;
-    if (!AECM_HIP_OK(hipSetDevice(device_)) || !EnsureLaunchControl(RaggedQueueControlBytes(count, plan.n_chunks)) ||
-        !EnsurePlanStaging(plan.words.size()))
+    // (allocations ahead of the launch's timing events)
+    const bool pipelined = d.form == 3;
+    if (!AECM_HIP_OK(hipSetDevice(device_)) ||
+        !EnsureLaunchControl(pipelined ? pipe.words.size() * sizeof(uint32_t) : RaggedQueueControlBytes(count, plan.n_chunks)) ||
+        !EnsurePlanStaging(pipelined ? pipe.words.size() : plan.words.size()))
         return kErrUnspecified;
-    return TimedLaunch(io, plan.max_blocks, first, count, nullptr, &plan, d.form) ? 0 : kErrUnspecified;
+    return TimedLaunch(io, plan.max_blocks, first, count, nullptr, &plan, d.form, pipelined ? &pipe : nullptr) ? 0 : kErrUnspecified;
 }
 
 // Host audio: the live blocks are packed into dense device rows, run, and the blocks that were written are copied back.
@@ -580,7 +677,7 @@ int32_t BatchEngine::ProcessBlocksRaggedHost(const IoView &io, int num_blocks, c
 }
 
 bool BatchEngine::TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged,
-                              int ragged_form) {
+                              int ragged_form, const RaggedPipePlan *pipe) {
     if (first < 0 || count < 0 || first + count > num_streams_) return false;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
     if (!HarvestTimers(false)) return false;
@@ -594,7 +691,7 @@ bool BatchEngine::TimedLaunch(const IoView &io, int num_blocks, int first, int c
     st.vec += (size_t)first * kVecWordsPerStream;
     st.scal += (size_t)first * kNumScal;
     st.hist += (size_t)first * kHistWordsPerStream;
-    if (!LaunchBlocks(st, io, count, num_blocks, blocks_per_stream_dev, ragged, ragged_form)) return false;
+    if (!LaunchBlocks(st, io, count, num_blocks, blocks_per_stream_dev, ragged, ragged_form, pipe)) return false;
     if (!AECM_HIP_OK(hipEventRecord(ev_stop_[slot], stream_))) return false;
     ++timer_pending_;
     return true;

@@ -67,12 +67,42 @@ struct RaggedPlan {
 };
 // false: a length outside [0, num_blocks] (the plan is then not usable).
 bool BuildRaggedPlan(const int32_t *blocks_per_stream, int num_streams, int num_blocks, int chunk_blocks, RaggedPlan *plan);
+// The plan of a ragged PIPELINED launch (aecm_process_pipelined_ragged_kernel): which stream sits in which of the four slots
+// of which workgroup.  Pure host logic.  Workgroups i, i + cus, ... share a compute unit (the dispatcher deals them out in turn);
+// a stream stays on its unit for the whole launch, so the launch ends when the unit with the most blocks does.  The live streams
+// (len > 0), longest first, each go to the unit with the fewest blocks so far that still has a free slot (longest processing time
+// first); a unit's streams, in that order, are cut into its workgroups in consecutive runs of as equal a size as can be (lock-step
+// partners have similar lengths); in a workgroup the longest takes slot 0, the next slot 2, then 1, then 3 (the two longest on
+// different two-slot front / tail / delay waves; 1 / 2 / 3 streams use the slots of the equal-length kernel's table).
+struct RaggedPipePlan {
+    int num_streams = 0, live_streams = 0, max_blocks = 0;
+    int workgroups = 0;               // of the launch: up to the last one that has a stream
+    int used_cus = 0;                 // compute units that carry a workgroup
+    int64_t sum_blocks = 0;
+    int64_t fullest_cu_blocks = 0;    // blocks on the unit that carries the most: the launch's critical path in blocks of one unit
+    PipeShape shape{};
+    std::vector<uint32_t> words;      // what the kernel reads: slot_stream[workgroups][4] (-1 = empty), then len[num_streams]
+    const int32_t *slot_stream() const { return reinterpret_cast<const int32_t *>(words.data()); }
+    // 1000 x (mean blocks per compute unit) / (blocks on the fullest unit)
+    int evenness_x1000() const {
+        return fullest_cu_blocks > 0 && used_cus > 0 ? (int)((1000 * sum_blocks / used_cus) / fullest_cu_blocks) : 1000;
+    }
+};
+// The shape a ragged pipelined launch of `live` streams, the longest of max_blocks blocks, takes: PipelinedShapeFor without the
+// progress-feedback balance (its "slowest workgroup" rule assumes equal work; a launch whose size would pick it takes the plain
+// six-wave shape).
+PipeShape RaggedPipeShapeFor(int live, int max_blocks, int compute_units, const PipeWishes &wishes);
+// false: a negative length, no live stream, a balanced shape, or more live streams than the shape's workgroups have slots.
+bool BuildRaggedPipePlan(const int32_t *blocks_per_stream, int num_streams, const PipeShape &shape, int compute_units, RaggedPipePlan *plan);
 // Which form a ragged launch takes under a policy; *plan_out (may be null) receives the plan it would run with.  Every length equal:
 // exactly DescribeLaunchWith of that length.  Otherwise the chunk queue when the fast variant is selected, more than queue_min_streams
-// streams are live, the longest stream has at least two chunks and the items fit 31 bits; else one wavefront per stream, each with its
-// own block count.  Never pipelined.  form < 0: a length outside [0, num_blocks].
+// streams are live, the longest stream has at least two chunks and the items fit 31 bits; else -- only with ragged_pipelining, the
+// batch's opt-in (BatchEngine::set_ragged_pipelining) -- pipelined (form 3; *pipe_out, may be null, receives that plan) when the fast
+// variant is selected, there is no clean input, the LIVE streams are within [pipelined_min_streams, pipelined_max_streams] and the
+// longest has at least pipelined_min_blocks blocks; else one wavefront per stream, each with its own block count.
+// form < 0: a length outside [0, num_blocks].
 LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, const int32_t *blocks_per_stream,
-                                           bool has_clean, RaggedPlan *plan_out);
+                                           bool has_clean, RaggedPlan *plan_out, bool ragged_pipelining = false, RaggedPipePlan *pipe_out = nullptr);
 
 class BatchEngine {
 public:
@@ -109,8 +139,11 @@ public:
     bool ProcessRecordingsRagged(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, int frame,
                                  int n_calls, const int32_t *calls_per_stream_host, int16_t ms, bool host_pointers, int32_t *rc, int32_t *codes_host);
     LaunchDescription DescribeRaggedLaunch(int num_blocks, const int32_t *blocks_per_stream_host, bool has_clean, RaggedPlan *plan_out) const {
-        return DescribeRaggedLaunchWith(policy_, variant_, num_streams_, num_blocks, blocks_per_stream_host, has_clean, plan_out);
+        return DescribeRaggedLaunchWith(policy_, variant_, num_streams_, num_blocks, blocks_per_stream_host, has_clean, plan_out, ragged_pipelining_);
     }
+    // Ragged launches the chip holds at once take the pipelined form (DescribeRaggedLaunchWith's rule).  Off by default.
+    void set_ragged_pipelining(bool on) { ragged_pipelining_ = on; }
+    bool ragged_pipelining() const { return ragged_pipelining_; }
     // Whole recordings as sessions: every stream is driven like a fresh WebRtcAecm_* session by
     // n_calls x (BufferFarend, Process) of `frame` samples with a constant msInSndCardBuf
     // (aecm_session_flow.h).  far/near/clean/out: [S][>= n_calls*frame], device (or host) pointers; clean
@@ -167,9 +200,12 @@ private:
     bool queue_unchecked_ = false;       // a queue launch has been enqueued since the error word was last read
     bool launch_failed_ = false;         // a wave of a queue launch gave up: sticky until Init (CheckQueueError)
     // ragged (may be null): the plan of a ragged launch and the form DescribeRaggedLaunchWith gave it; num_blocks is then its longest stream
+    // (ragged_form 3: the pipelined form, by *pipe)
     bool LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev,
-                      const RaggedPlan *ragged = nullptr, int ragged_form = 0);
-    bool TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged, int ragged_form);
+                      const RaggedPlan *ragged = nullptr, int ragged_form = 0, const RaggedPipePlan *pipe = nullptr);
+    bool TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged, int ragged_form,
+                     const RaggedPipePlan *pipe = nullptr);
+    bool ragged_pipelining_ = false;
     // The plan's way to the device: a pinned staging buffer (grown on first use) and the event behind its last upload -- the
     // buffer is rewritten only when that copy has run, so ragged launches queue back to back like the others.
     uint32_t *plan_host_ = nullptr;
@@ -177,7 +213,8 @@ private:
     hipEvent_t plan_uploaded_ = nullptr;
     bool plan_upload_pending_ = false;
     bool EnsurePlanStaging(size_t words);
-    bool UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev);
+    bool UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev) { return UploadPlanWords(plan.words, dst_dev); }
+    bool UploadPlanWords(const std::vector<uint32_t> &plan_words, uint32_t *dst_dev);
     bool CheckQueueError();
     bool Drain();
     bool EnsureLaunchErrorWord();

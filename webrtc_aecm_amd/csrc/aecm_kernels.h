@@ -84,6 +84,13 @@ size_t PipelinedControlBytes(int n_workgroups);
 size_t PipelinedTraceOffsetBytes(int n_workgroups);     // diagnostics builds (-DAECM_PIPE_TRACE): where the per-wave records follow the progress words
 hipError_t LaunchProcessBlocksPipelined(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, const PipeShape &shape, uint32_t *progress,
                                         hipStream_t stream);
+// The same form for streams of different lengths (aecm_process_pipelined_ragged_kernel: the unbalanced shapes): plan_dev =
+// RaggedPipePlanWords(n_workgroups, n_streams) words uploaded ahead of the launch on the same stream -- slot_stream[n_workgroups][4]
+// (the stream of each of a workgroup's four slots, -1 = empty), then len[n_streams] (aecm_engine.h: RaggedPipePlan).  A slot whose
+// stream has ended keeps the workgroup's barriers and does nothing else; a stream of length 0 has no slot.
+size_t RaggedPipePlanWords(int n_workgroups, int n_streams);
+hipError_t LaunchProcessBlocksPipelinedRagged(const StatePtrs &st, const IoView &io, int n_streams, const PipeShape &shape, int n_workgroups,
+                                              const uint32_t *plan_dev, hipStream_t stream);
 
 // Replicate one stream image (vec: kNumVec*64 words, scal: 64 words, both on the device) into
 // streams [first, first + count) and clear their far-spectrum history.

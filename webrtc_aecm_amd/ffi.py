@@ -47,6 +47,8 @@ BATCH_SYMBOLS = [
     "WebRtcAecm_SetDefaultDevice", "WebRtcAecmBatch_DevicePciBusId",
     "WebRtcAecmBatch_ProcessBlocksRagged", "WebRtcAecmBatch_ProcessBlocksRaggedHost", "WebRtcAecmBatch_ProcessRecordingsRagged",
     "WebRtcAecmBatch_ProcessRecordingsRaggedHost", "WebRtcAecmBatch_DescribeRaggedLaunch", "WebRtcAecmBatch_RaggedPlan",
+    "WebRtcAecmBatch_SetRaggedPipelining", "WebRtcAecmBatch_DescribeRaggedLaunchEx", "WebRtcAecmBatch_RaggedPipePlan",
+    "WebRtcAecmBatch_DescribeRaggedLaunchOf",
 ]
 SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_Create", "WebRtcAecmSessions_Free", "WebRtcAecmSessions_Init", "WebRtcAecmSessions_set_config",
@@ -140,6 +142,15 @@ def load():
                                                          C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                          C.POINTER(C.c_int32)]
     lib.WebRtcAecmBatch_RaggedPlan.argtypes = [C.c_int32, vp, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+    # (a library built from an older tree -- tools/bench_ragged.py --parent -- lacks these: calling one on it raises AttributeError)
+    if hasattr(lib, "WebRtcAecmBatch_SetRaggedPipelining"):
+        lib.WebRtcAecmBatch_DescribeRaggedLaunchOf.argtypes = [vp, vp, C.c_int32, C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64),
+                                                               C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+        lib.WebRtcAecmBatch_SetRaggedPipelining.argtypes = [vp, C.c_int32]
+        lib.WebRtcAecmBatch_DescribeRaggedLaunchEx.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32,
+                                                               C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                               C.POINTER(C.c_int32)]
+        lib.WebRtcAecmBatch_RaggedPipePlan.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.WebRtcAecmBatch_Synchronize.argtypes = [vp]
     lib.WebRtcAecmBatch_GetLastLaunchMs.argtypes = [vp, C.POINTER(C.c_float)]
     lib.WebRtcAecmBatch_GetTimers.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -308,6 +319,11 @@ class AecmBatch:
         any length do what min_streams says."""
         self._check(self.lib.WebRtcAecmBatch_SetLaunchPipelining(self.h, min_streams), "SetLaunchPipelining")
 
+    def set_ragged_pipelining(self, enable):
+        """Ragged launches the chip holds at once take the pipelined form (include/aecm_batch.h: WebRtcAecmBatch_SetRaggedPipelining;
+        results never depend on it).  Off by default."""
+        self._check(self.lib.WebRtcAecmBatch_SetRaggedPipelining(self.h, 1 if enable else 0), "SetRaggedPipelining")
+
     def launch_policy(self) -> AecmLaunchPolicy:
         p = AecmLaunchPolicy()
         self._check(self.lib.WebRtcAecmBatch_GetLaunchPolicy(self.h, C.byref(p)), "WebRtcAecmBatch_GetLaunchPolicy")
@@ -440,8 +456,14 @@ class AecmBatch:
         return rc, out, codes
 
     def describe_ragged_launch(self, blocks_per_stream, clean=False) -> dict:
-        """describe_ragged_launch (module level) under this batch's launch policy."""
-        return describe_ragged_launch(self._lengths(blocks_per_stream), clean=clean, policy=self.launch_policy())
+        """describe_ragged_launch (module level) as the engine decides it for this batch: under its launch policy, its kernel
+        variant and its set_ragged_pipelining switch."""
+        lens = self._lengths(blocks_per_stream)
+        d = AecmLaunchDescription()
+        items, total, longest = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._check(self.lib.WebRtcAecmBatch_DescribeRaggedLaunchOf(self.h, lens.ctypes.data, 1 if clean else 0, C.byref(d), C.byref(items),
+                                                                    C.byref(total), C.byref(longest)), "DescribeRaggedLaunchOf")
+        return dict(d.as_dict(), items=items.value, sum_blocks=total.value, max_blocks=longest.value)
 
     def synchronize(self):
         self._check(self.lib.WebRtcAecmBatch_Synchronize(self.h), "Synchronize")
@@ -768,18 +790,39 @@ def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int
     return d.as_dict()
 
 
-def describe_ragged_launch(blocks_per_stream, compute_units: int = 0, clean: bool = False, policy=None) -> dict:
+def describe_ragged_launch(blocks_per_stream, compute_units: int = 0, clean: bool = False, policy=None, ragged_pipelining: bool = False) -> dict:
     """describe_launch_detail for a ragged launch (one block count per stream), without a device: the AecmLaunchDescription
     fields plus items (the chunk queue's (chunk, stream) items; 0 for the other forms), sum_blocks (the useful work) and
-    max_blocks (the critical path)."""
+    max_blocks (the critical path).  ragged_pipelining: the answer for a batch that has opted in (AecmBatch.set_ragged_pipelining)."""
     lens = np.ascontiguousarray(blocks_per_stream, dtype=np.int32)
     d = AecmLaunchDescription()
     items, total, longest = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-    rc = load().WebRtcAecmBatch_DescribeRaggedLaunch(C.byref(policy) if policy is not None else None, compute_units, lens.size, lens.ctypes.data,
-                                                     1 if clean else 0, C.byref(d), C.byref(items), C.byref(total), C.byref(longest))
+    pol = C.byref(policy) if policy is not None else None
+    if ragged_pipelining:
+        name = "WebRtcAecmBatch_DescribeRaggedLaunchEx"
+        rc = load().WebRtcAecmBatch_DescribeRaggedLaunchEx(pol, compute_units, lens.size, lens.ctypes.data, 1 if clean else 0, 1, C.byref(d),
+                                                           C.byref(items), C.byref(total), C.byref(longest))
+    else:
+        name = "WebRtcAecmBatch_DescribeRaggedLaunch"
+        rc = load().WebRtcAecmBatch_DescribeRaggedLaunch(pol, compute_units, lens.size, lens.ctypes.data, 1 if clean else 0, C.byref(d),
+                                                         C.byref(items), C.byref(total), C.byref(longest))
     if rc != 0:
-        raise AecmError(rc, "WebRtcAecmBatch_DescribeRaggedLaunch")
+        raise AecmError(rc, name)
     return dict(d.as_dict(), items=items.value, sum_blocks=total.value, max_blocks=longest.value)
+
+
+def ragged_pipe_plan(blocks_per_stream, compute_units: int = 0, policy=None):
+    """slot_stream[workgroups][4] of the plan a ragged pipelined launch runs by (include/aecm_batch.h: WebRtcAecmBatch_RaggedPipePlan):
+    the stream in each slot of each workgroup, -1 = empty; workgroups i, i + compute units, ... share a compute unit."""
+    lens = np.ascontiguousarray(blocks_per_stream, dtype=np.int32)
+    cap = 4 * max(int((lens > 0).sum()), 1)              # a workgroup of the plan holds at least one stream
+    slots = np.full(cap, -1, dtype=np.int32)
+    n_wg = C.c_int32(0)
+    rc = load().WebRtcAecmBatch_RaggedPipePlan(C.byref(policy) if policy is not None else None, compute_units, lens.size, lens.ctypes.data,
+                                               slots.ctypes.data, cap, C.byref(n_wg))
+    if rc != 0:
+        raise AecmError(rc, "WebRtcAecmBatch_RaggedPipePlan")
+    return slots[:4 * n_wg.value].reshape(n_wg.value, 4)
 
 
 def ragged_plan(blocks_per_stream, chunk_blocks: int):
