@@ -298,8 +298,8 @@ int32_t WebRtcAecmBatch_SetKernelVariant(AecmBatch *b, int32_t variant);
  * chunk_blocks = 0: one wavefront keeps one stream for the whole launch, always.  min_streams < 0 (default): the
  * threshold above; >= 0: the queue form above that many streams (diagnostics / tests). */
 int32_t WebRtcAecmBatch_SetLaunchChunking(AecmBatch *b, int32_t chunk_blocks, int32_t min_streams);
-/* Launches the chip holds at once (<= 16 streams per compute unit = 4 096 streams on an MI355X; fast variant, no clean
- * near-end input) run pipelined: a workgroup serves up to four streams with the state-independent transforms of a block in
+/* Launches the chip holds at once (<= 16 streams per compute unit = 4 096 streams on an MI355X; fast variant; with a clean
+ * near-end input only after WebRtcAecmBatch_SetCleanPipelining) run pipelined: a workgroup serves up to four streams with the state-independent transforms of a block in
  * "front" wavefronts of their own, one block ahead of the rest.  Shape by streams per compute unit: up to 8 (2 048 streams)
  * sixteen wavefronts per workgroup, two workgroups per unit -- the delay estimator one block ahead, the gain half of the block and
  * the inverse transforms one block behind, each in wavefronts of their own; up to 12 (3 072) eight wavefronts (front and "tail"
@@ -313,7 +313,8 @@ int32_t WebRtcAecmBatch_SetLaunchChunking(AecmBatch *b, int32_t chunk_blocks, in
 int32_t WebRtcAecmBatch_SetLaunchPipelining(AecmBatch *b, int32_t min_streams);
 /* Ragged launches (WebRtcAecmBatch_ProcessBlocksRagged, WebRtcAecmBatch_ProcessRecordingsRagged) that the chip holds at once, pipelined:
  * enable != 0 and such a launch takes the pipelined form above instead of one wavefront per stream when the fast variant is selected,
- * there is no clean near-end input, the streams that have blocks to run (not the batch's size: 100 live streams of 65 536 qualify) are
+ * there is no clean near-end input (WebRtcAecmBatch_SetCleanPipelining does not extend to ragged launches: the two switches do not
+ * combine yet), the streams that have blocks to run (not the batch's size: 100 live streams of 65 536 qualify) are
  * within [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks.  All lengths equal
  * stays the equal-length launch, and the chunk queue keeps what it takes today.  A workgroup still marches its (up to) four streams in
  * lock step -- every wavefront executes as many barriers as the workgroup's longest stream has blocks -- and a slot whose stream has
@@ -324,13 +325,30 @@ int32_t WebRtcAecmBatch_SetLaunchPipelining(AecmBatch *b, int32_t min_streams);
  * existing callers run is changed in a step of its own, not as a side effect of adding the form.
  * Results never depend on it.  AECM_BAD_PARAMETER_ERROR for a NULL batch. */
 int32_t WebRtcAecmBatch_SetRaggedPipelining(AecmBatch *b, int32_t enable);
+/* Equal-length launches WITH a clean near-end input (near_clean_dev: the output of a noise suppressor next to the noisy signal) that
+ * the chip holds at once, pipelined: enable != 0 and such a launch takes the pipelined form under exactly the conditions of a launch
+ * without a clean input -- fast variant, pipelined_min_streams <= streams <= pipelined_max_streams, at least pipelined_min_blocks
+ * blocks -- instead of one wavefront per stream.  The front wavefronts then run three transforms per block and hand the clean
+ * spectrum on; the shapes are those with formed spectra and without progress feedback: by workgroups of four streams per compute
+ * unit, up to two sixteen wavefronts (shape bits 0x1a02), up to three eight (0x002), above that six (0x000); pipe_* wishes that
+ * name another shape land on the nearest of these (the raw hand-over is dropped, four front wavefronts without delay and gain
+ * wavefronts become two; pipe_delay_waves 4 with pipe_gain_waves 0 gives twelve wavefronts, 0x802) -- never a launch error.
+ * DescribeLaunch reports these launches with the shape bits + 0x2000.  ProcessRecordings* with a clean input run their blocks
+ * through the same launch rule.  Ragged launches with a clean input stay as they are (one wavefront per stream, or the chunk
+ * queue), whatever this switch and WebRtcAecmBatch_SetRaggedPipelining say: the two do not combine yet; a ragged call whose lengths
+ * are all equal IS the equal-length launch.  out_dev may alias near_clean_dev as for every other form (no input row is read after
+ * an output row of the same launch has been written).  Per batch; OFF by default, for the reason given above: with it off every
+ * launch takes exactly the form it took before the switch existed.  Static checks, and the sweep to run: profiles/r11_clean_pipelined.txt.
+ * Results never depend on it.  AECM_BAD_PARAMETER_ERROR for a NULL batch. */
+int32_t WebRtcAecmBatch_SetCleanPipelining(AecmBatch *b, int32_t enable);
 /* Which form a ProcessBlocks launch of num_blocks blocks over the whole batch takes, with (has_clean_input != 0) or
  * without a clean near-end input (for measurement tools that must name
  * the kernel they time): 0 = one wavefront per stream, kernel variants for launches the chip holds at once; 1 = one
  * wavefront per stream, issue priority by phase; 2 = the chunk queue (*chunk_blocks, if not NULL, receives the chunk);
  * 3 = pipelined (*chunk_blocks then receives the shape: the "tail" wavefronts per workgroup, 0 or 2, + 0x100 when the
  * launch balances its workgroups' progress, + 0x200 with four front wavefronts instead of two, + 0x400 when the back
- * wavefronts form the spectra, + 0x800 with delay wavefronts, + 0x1000 with gain wavefronts). */
+ * wavefronts form the spectra, + 0x800 with delay wavefronts, + 0x1000 with gain wavefronts, + 0x2000 for the kernel that takes
+ * a clean near-end input: WebRtcAecmBatch_SetCleanPipelining -- on a batch this call answers by the batch's own switch). */
 #define AECM_LAUNCH_RESIDENT 0
 #define AECM_LAUNCH_PER_STREAM 1
 #define AECM_LAUNCH_CHUNK_QUEUE 2
@@ -390,6 +408,12 @@ typedef struct AecmLaunchDescription {
 } AecmLaunchDescription;
 int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
                                              int32_t has_clean_input, AecmLaunchDescription *out);
+/* WebRtcAecmBatch_DescribeLaunchDetail with the batch's opt-in for clean inputs (WebRtcAecmBatch_SetCleanPipelining) as an argument.
+ * clean_pipelining = 0: exactly that call's answer.  Otherwise a launch with a clean input is pipelined under the conditions of one
+ * without (form 3, shape bits + 0x2000); launches without a clean input are described as before.  (AecmLaunchPolicy is unchanged:
+ * the switch is a property of the batch, not of the policy.) */
+int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
+                                               int32_t has_clean_input, int32_t clean_pipelining, AecmLaunchDescription *out);
 /* The same for a ragged launch (WebRtcAecmBatch_ProcessBlocksRagged) of num_streams streams with these lengths, no device needed: form,
  * chunk and grid as above -- the chunk queue when more streams than the queue's threshold have blocks to run and the longest has at
  * least two chunks, else one wavefront per stream; never pipelined (this call describes a batch that has not opted in:

@@ -9,6 +9,7 @@ that library did not travel) on all usable host cores and compares every output 
 stream's final state digest.  ~50 s of CPU per pass of 65 536 x 1 280 frames on 16 cores.
 
     python tools/soak_parity.py [--streams 65536] [--blocks 1280] [--passes 2] [--fs 16000] [--clean] [--echo-mode 1] [--cng 1]
+    python tools/soak_parity.py --streams 4096 --clean --clean-pipelining     # the pipelined form of a launch with a clean input
 """
 import argparse, json, sys, time
 from concurrent.futures import ThreadPoolExecutor
@@ -36,6 +37,8 @@ def main():
                     "WebRtcAecmBatch_ProcessBlocksRagged launch, every stream is checked over its own first blocks (forces --passes 1)")
     ap.add_argument("--ragged-pipelining", action="store_true", help="with --ragged: the batch opts into the pipelined form "
                     "(WebRtcAecmBatch_SetRaggedPipelining) for launches the chip holds at once")
+    ap.add_argument("--clean-pipelining", action="store_true", help="with --clean: the batch opts into the pipelined form "
+                    "(WebRtcAecmBatch_SetCleanPipelining) for launches the chip holds at once")
     a = ap.parse_args()
 
     import torch
@@ -51,6 +54,8 @@ def main():
     batch = aecm.AecmBatch(S, a.fs, cng_mode=a.cng, echo_mode=a.echo_mode, device=0,
                            variant=aecm.KERNEL_FAST if a.variant == "fast" else aecm.KERNEL_SAFE)
     out = torch.empty_like(near)
+    if a.clean_pipelining:
+        batch.set_clean_pipelining(True)
     lens = None
     if a.ragged:
         a.passes = 1

@@ -4,6 +4,7 @@
 //   aecm_process_ragged_queue_kernel  the same queue for streams of different lengths: items by a host-made plan, longest streams first
 //   aecm_process_pipelined_kernel  launches the chip holds at once: six waves per four streams, transforms one block ahead
 //   aecm_process_pipelined_ragged_kernel  the same for streams of different lengths (opt-in): each slot of a workgroup its own length
+//   aecm_process_pipelined_clean_kernel   the same for launches with a clean near-end input (opt-in): three transforms in the front waves
 // (aecm_engine.cpp: LaunchBlocks picks by the size of the launch; the forms give identical results.)
 //
 // The whole persistent state of a stream (~40 lane vectors + ~50 scalars) is loaded into registers once, n_blocks blocks
@@ -294,6 +295,12 @@ struct PipeRawSlot {        // the same hand-over BEFORE the spectra are formed 
     int fa[2][kLanes], fb[2][kLanes];     // BlockEngine::front_transforms: far end [0], near end [1]
     int q[2], pad[2];
 };
+struct PipeCleanSlot {       // the hand-over of a launch with a clean near-end input: BlockEngine::CleanHandOver (aecm_wave.h), 256 B more
+    int clean_x[kLanes];     // clean spectrum, bins 0..63: re | im << 16
+    int mags[kLanes];        // far-end magnitude | near-end magnitude << 16 (PipeSlot's row)
+    int clean_mag[kLanes];   // clean magnitude
+    int scalars[kLanes];     // lanes 0, 1: far mag[64], Q; 3, 4: near mag[64], Q (PipeSlot's lanes); 5, 6, 7: clean re[64], mag[64], Q
+};
 struct PipeTailSlot {       // the residual spectrum of one block of one stream on its way from the middle to the tail wave
     int a[kLanes], b[kLanes];   // BlockEngine::TailInput
     int clean_q, pad[3];
@@ -306,10 +313,17 @@ struct PipeGainState {      // the gain wave's part of the stream state on its w
     int echo_filt[kLanes], near_filt_ctrs[kLanes], noise_est[kLanes];      // (near_filt | low_ctr << 16 | high_ctr << 19: the V_NEARFILT layout)
     int scal[16];
 };
-template <int kTail, bool kRaw = false, int kDelay = 0, int kGain = 0>
-struct PipeShared {
+// Clean launches: the clean input's samples of each stream's LAST block on their way from the front wave, which has them in
+// registers, to the wave that stores V_OUTBUF (out_ovl | c_old << 16: the tail wave, or the back wave without tail waves) -- written
+// in the front waves' last step, read behind the launch's last barrier.  (A base class: nothing is added to the other launches' LDS.)
+template <bool kClean> struct PipeCleanLast {};
+template <> struct PipeCleanLast<true> { int c_last[kPipeStreams][kLanes]; };
+template <int kTail, bool kRaw = false, int kDelay = 0, int kGain = 0, bool kClean = false>
+struct PipeShared : PipeCleanLast<kClean> {
+    static_assert(!(kRaw && kClean), "clean launches: the formed-spectra hand-over");
     // [block modulo the ring: 2, + 1 with delay waves, + 1 with gain waves][stream of the workgroup]
-    typename std::conditional<kRaw, PipeRawSlot, PipeSlot>::type slots[2 + (kDelay ? 1 : 0) + (kGain ? 1 : 0)][kPipeStreams];
+    typename std::conditional<kRaw, PipeRawSlot, typename std::conditional<kClean, PipeCleanSlot, PipeSlot>::type>::type
+        slots[2 + (kDelay ? 1 : 0) + (kGain ? 1 : 0)][kPipeStreams];
     PipeTailSlot tails[kTail ? 2 : 1][kTail ? kPipeStreams : 1];
     int delays[2][kPipeStreams];          // delay_block's result on its way from the delay to the middle wave ...
     int far_rows[kDelay ? 2 : 1][kDelay ? kPipeStreams : 1][kLanes];      // ... and the far-history row that goes with it (AlignedFarend)
@@ -422,7 +436,7 @@ __global__ __launch_bounds__(64 * PipeWaves(kTail, kFront, kDelay, kGain))
 __attribute__((amdgpu_waves_per_eu(PipeWavesPerEu(kGain), AECM_MAX_WAVES_PER_EU)))
 void aecm_process_pipelined_kernel(StatePtrs st, IoView io, int streams_base, int streams_rem, int n_blocks, uint32_t *progress, int n_workgroups,
                                     int wgs_per_round, int rot, int prio) {
-    constexpr bool kRagged = false;
+    constexpr bool kRagged = false, kClean = false;
 #include "aecm_pipelined_body.inc"
 }
 template <int kTail, bool kBalance, bool kRaw = false, int kFront = 2, int kDelay = 0, int kGain = 0>
@@ -430,18 +444,38 @@ __global__ __launch_bounds__(64 * PipeWaves(kTail, kFront, kDelay, kGain))
 __attribute__((amdgpu_waves_per_eu(PipeWavesPerEu(kGain), AECM_MAX_WAVES_PER_EU)))
 void aecm_process_pipelined_ragged_kernel(StatePtrs st, IoView io, int streams_base, int streams_rem, int n_blocks, uint32_t *progress, int n_workgroups,
                                            int wgs_per_round, int rot, int prio) {
-    constexpr bool kRagged = true;
+    constexpr bool kRagged = true, kClean = false;
+#include "aecm_pipelined_body.inc"
+}
+// The same body for launches with a clean near-end input (io.near_clean; opt-in per batch): the front waves run the third transform
+// and hand the clean spectrum over in the near-end spectrum's place (PipeCleanSlot), the roles behind them run the three-signal
+// block (BlockEngine<.., true>).  A kernel of its own, as the ragged one and for the same reason.  Formed spectra only, no balance:
+// the shapes 6 / 8 / 12 / 16 waves (LaunchProcessBlocksPipelined's keys 20, 220, 4220, 42240).
+template <int kTail, bool kBalance, bool kRaw = false, int kFront = 2, int kDelay = 0, int kGain = 0>
+__global__ __launch_bounds__(64 * PipeWaves(kTail, kFront, kDelay, kGain))
+__attribute__((amdgpu_waves_per_eu(PipeWavesPerEu(kGain), AECM_MAX_WAVES_PER_EU)))
+void aecm_process_pipelined_clean_kernel(StatePtrs st, IoView io, int streams_base, int streams_rem, int n_blocks, uint32_t *progress, int n_workgroups,
+                                          int wgs_per_round, int rot, int prio) {
+    constexpr bool kRagged = false, kClean = true;
 #include "aecm_pipelined_body.inc"
 }
 #undef AECM_PIPE_BARRIER
 
 // Streams a pipelined launch keeps resident at once: workgroups per CU by wave slots (4 SIMDs x 7) and by LDS (160 KB).
-template <int kTail, int kFront = 2, int kDelay = 0, int kGain = 0>
+template <int kTail, int kFront = 2, int kDelay = 0, int kGain = 0, bool kClean = false>
 constexpr int PipeWorkgroupsPerCu() {
     constexpr int by_waves = 4 * PipeWavesPerEu(kGain) / PipeWaves(kTail, kFront, kDelay, kGain);
-    constexpr int by_lds = (int)((160 * 1024) / (sizeof(LdsTables) + (kDelay ? sizeof(PipeShared<kTail, false, kDelay, kGain>) : sizeof(PipeShared<kTail, true>))));
+    constexpr size_t shared = kClean ? sizeof(PipeShared<kTail, false, kDelay, kGain, true>)
+                              : kDelay ? sizeof(PipeShared<kTail, false, kDelay, kGain>) : sizeof(PipeShared<kTail, true>);
+    constexpr int by_lds = (int)((160 * 1024) / (sizeof(LdsTables) + shared));
     return by_waves < by_lds ? by_waves : by_lds;
 }
+// The clean shapes' larger hand-over slots (30 / 34 / 38 / 49 KB of LDS per workgroup with the tables) leave every carried shape the
+// workgroups per CU that PipelinedStreamLimit -- and with it the launch rule's stream limit -- assumes for the shape without a clean input.
+static_assert(PipeWorkgroupsPerCu<0, 2, 0, 0, true>() == PipeWorkgroupsPerCu<0>(), "clean six-wave shape: four workgroups per CU");
+static_assert(PipeWorkgroupsPerCu<2, 2, 0, 0, true>() == PipeWorkgroupsPerCu<2>(), "clean eight-wave shape: three workgroups per CU");
+static_assert(PipeWorkgroupsPerCu<2, 2, 4, 0, true>() == PipeWorkgroupsPerCu<2, 2, 4>(), "clean twelve-wave shape: two workgroups per CU");
+static_assert(PipeWorkgroupsPerCu<2, 4, 2, 4, true>() == PipeWorkgroupsPerCu<2, 4, 2, 4>(), "clean sixteen-wave shape: two workgroups per CU");
 // Streams a pipelined launch of this shape keeps resident at once: workgroups per CU by wave slots (4 SIMDs x 7) and by LDS (160 KB).
 int PipelinedStreamLimit(int compute_units, int tail_waves, int front_waves, int delay_waves, int gain_waves, int wgs_per_cu) {
     const int per_cu = wgs_per_cu > 0 ? wgs_per_cu
@@ -526,6 +560,21 @@ PipeShape PipelinedShapeFor(int n_streams, int n_blocks, int compute_units, cons
     return sh;
 }
 
+// The shape of a pipelined launch WITH a clean near-end input: the same rule by size on the set of shapes the clean kernel is carried
+// in -- formed spectra, no balance: sixteen waves up to two workgroups of four per CU, eight waves up to three, six above (shape bits
+// 0x1a02 / 0x002 / 0x000; twelve waves, 0x802, by wish) -- so a wish that names another shape lands on the nearest of these: the raw
+// hand-over is dropped, four front waves without delay and gain waves become two.  Never a shape the launcher refuses.
+PipeShape PipelinedCleanShapeFor(int n_streams, int n_blocks, int compute_units, const PipeWishes &wishes) {
+    PipeWishes w = wishes;
+    w.raw = 0;                                    // (also: no balance -- there is no balanced instantiation without the raw hand-over)
+    PipeShape sh = PipelinedShapeFor(n_streams, n_blocks, compute_units, w);
+    if (sh.front_waves == 4 && sh.gain_waves == 0) {
+        w.front_waves = 2;
+        sh = PipelinedShapeFor(n_streams, n_blocks, compute_units, w);
+    }
+    return sh;
+}
+
 int PipelinedWorkgroupWaves(const PipeShape &shape) { return PipeWaves(shape.tail_waves, shape.front_waves, shape.delay_waves, shape.gain_waves); }
 int PipelinedWorkgroupsPerCu(const PipeShape &shape) {
     return PipelinedStreamLimit(1, shape.tail_waves, shape.front_waves, shape.delay_waves, shape.gain_waves) / kPipeStreams;
@@ -550,7 +599,17 @@ hipError_t LaunchProcessBlocksPipelined(const StatePtrs &st, const IoView &io, i
                                                               stream, st, io, streams_base, streams_rem, n_blocks, progress, (int)grid.x, shape.wgs_per_round, shape.rot, shape.prio)
     // The instantiations the library carries (PipelinedShapeFor only ever asks for these).
     const int key = shape.gain_waves * 10000 + shape.delay_waves * 1000 + shape.tail_waves * 100 + shape.front_waves * 10 + (shape.raw ? 1 : 0);
-    if (shape.balance) { if (key != 21) return hipErrorInvalidValue; AECM_LAUNCH_PIPE(0, true, true, 2, 0, 0); }
+#define AECM_LAUNCH_PIPE_CLEAN(T, F, D, G) hipLaunchKernelGGL((aecm_process_pipelined_clean_kernel<T, false, false, F, D, G>), grid, block,               \
+                                                              sizeof(LdsTables) + sizeof(PipeShared<T, false, D, G, true>), stream, st, io, streams_base, \
+                                                              streams_rem, n_blocks, nullptr, (int)grid.x, shape.wgs_per_round, shape.rot, shape.prio)
+    if (io.near_clean != nullptr) {               // PipelinedCleanShapeFor only ever asks for these
+        if (shape.balance) return hipErrorInvalidValue;
+        if (key == 20) AECM_LAUNCH_PIPE_CLEAN(0, 2, 0, 0);
+        else if (key == 220) AECM_LAUNCH_PIPE_CLEAN(2, 2, 0, 0);
+        else if (key == 4220) AECM_LAUNCH_PIPE_CLEAN(2, 2, 4, 0);
+        else if (key == 42240) AECM_LAUNCH_PIPE_CLEAN(2, 4, 2, 4);
+        else return hipErrorInvalidValue;
+    } else if (shape.balance) { if (key != 21) return hipErrorInvalidValue; AECM_LAUNCH_PIPE(0, true, true, 2, 0, 0); }
     else if (key == 20) AECM_LAUNCH_PIPE(0, false, false, 2, 0, 0);
     else if (key == 220) AECM_LAUNCH_PIPE(2, false, false, 2, 0, 0);
     else if (key == 221) AECM_LAUNCH_PIPE(2, false, true, 2, 0, 0);
@@ -559,6 +618,7 @@ hipError_t LaunchProcessBlocksPipelined(const StatePtrs &st, const IoView &io, i
     else if (key == 42240) AECM_LAUNCH_PIPE(2, false, false, 4, 2, 4);
     else return hipErrorInvalidValue;
 #undef AECM_LAUNCH_PIPE
+#undef AECM_LAUNCH_PIPE_CLEAN
     return hipGetLastError();
 }
 

@@ -361,6 +361,12 @@ int32_t WebRtcAecmBatch_SetRaggedPipelining(AecmBatch *b, int32_t enable) {
     return 0;
 }
 
+int32_t WebRtcAecmBatch_SetCleanPipelining(AecmBatch *b, int32_t enable) {
+    if (!b) return AECM_BAD_PARAMETER_ERROR;
+    b->engine->set_clean_pipelining(enable != 0);
+    return 0;
+}
+
 int32_t WebRtcAecmBatch_DescribeLaunch(const AecmBatch *b, int32_t num_blocks, int32_t has_clean_input, int32_t *chunk_blocks) {
     if (!b) return -1;
     return b->engine->DescribeLaunch(num_blocks, has_clean_input != 0, chunk_blocks);
@@ -431,6 +437,11 @@ static void DescriptionToAbi(const aecm::LaunchDescription &d, AecmLaunchDescrip
 
 int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
                                              int32_t has_clean_input, AecmLaunchDescription *out) {
+    return WebRtcAecmBatch_DescribeLaunchDetailEx(policy, compute_units, num_streams, num_blocks, has_clean_input, 0, out);
+}
+
+int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
+                                               int32_t has_clean_input, int32_t clean_pipelining, AecmLaunchDescription *out) {
     if (!out) return AECM_NULL_POINTER_ERROR;
     if (num_streams <= 0 || num_blocks <= 0) return AECM_BAD_PARAMETER_ERROR;
     aecm::LaunchPolicy p;
@@ -442,7 +453,7 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int
         if (compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
         p = aecm::DefaultLaunchPolicy(compute_units);
     }
-    DescriptionToAbi(aecm::DescribeLaunchWith(p, aecm::kVariantFast, num_streams, num_blocks, has_clean_input != 0), out);
+    DescriptionToAbi(aecm::DescribeLaunchWith(p, aecm::kVariantFast, num_streams, num_blocks, has_clean_input != 0, clean_pipelining != 0), out);
     return 0;
 }
 

@@ -250,7 +250,8 @@ bool BatchEngine::EnsureLaunchControl(size_t need) {
 //                 4 096 streams and that too -- every wave is resident there, but the SIMD's arbiter favours its oldest wave, the waves
 //                 dispatched first pull ahead, and with items claimed in order those waves simply take more of the work (4 608 streams
 //                 728 -> 830 M frames/s, 6 144: 844 -> 930 M; profiles/r04_experiments.md section 4).  Shorter chunks there: a quarter.
-//   pipelined     launches the chip holds at once: fast variant, no clean input, every stream the same number of blocks
+//   pipelined     launches the chip holds at once: fast variant, every stream the same number of blocks, and no clean input unless the
+//                 batch has opted in (set_clean_pipelining: aecm_process_pipelined_clean_kernel)
 namespace {
 int QueueMinStreams(const LaunchPolicy &p) { return p.queue_min_streams >= 0 ? p.queue_min_streams : p.pipelined_max_streams; }
 // (The quarter rule is for the default chunk; a length set by the caller is taken as it is.)
@@ -258,17 +259,18 @@ int QueueChunkFor(const LaunchPolicy &p, int count) {
     if (p.queue_chunk_blocks <= 0 || count > p.resident_waves || p.queue_chunk_explicit) return p.queue_chunk_blocks;
     return std::max(8, p.queue_chunk_blocks / 4);
 }
-bool PipelinedLaunchApplies(const LaunchPolicy &p, int variant, int count, int num_blocks, bool clean, bool ragged) {
-    return variant == kVariantFast && !clean && !ragged && count >= p.pipelined_min_streams && count <= p.pipelined_max_streams &&
+bool PipelinedLaunchApplies(const LaunchPolicy &p, int variant, int count, int num_blocks, bool clean, bool ragged, bool clean_pipelining = false) {
+    return variant == kVariantFast && (!clean || clean_pipelining) && !ragged && count >= p.pipelined_min_streams && count <= p.pipelined_max_streams &&
            num_blocks >= p.pipelined_min_blocks;
 }
 int PipeShapeBits(const PipeShape &sh) {
     return sh.tail_waves | (sh.balance ? 0x100 : 0) | (sh.front_waves == 4 ? 0x200 : 0) | (sh.raw ? 0x400 : 0) | (sh.delay_waves ? 0x800 : 0) |
            (sh.gain_waves ? 0x1000 : 0);
 }
+constexpr int kPipeShapeCleanBit = 0x2000;        // the launch runs aecm_process_pipelined_clean_kernel
 }  // namespace
 
-LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, bool has_clean) {
+LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, bool has_clean, bool clean_pipelining) {
     LaunchDescription d;
     const int cus = p.compute_units > 0 ? p.compute_units : 256;
     auto rounds = [&](LaunchDescription &x) { x.rounds_x1000 = (int)((int64_t)1000 * x.workgroups / ((int64_t)cus * std::max(1, x.workgroups_per_cu))); };
@@ -282,10 +284,10 @@ LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int cou
         rounds(d);
         return d;
     }
-    if (PipelinedLaunchApplies(p, variant, count, num_blocks, has_clean, false)) {
-        const PipeShape sh = PipelinedShapeFor(count, num_blocks, p.compute_units, p.pipe);
+    if (PipelinedLaunchApplies(p, variant, count, num_blocks, has_clean, false, clean_pipelining)) {
+        const PipeShape sh = has_clean ? PipelinedCleanShapeFor(count, num_blocks, p.compute_units, p.pipe) : PipelinedShapeFor(count, num_blocks, p.compute_units, p.pipe);
         d.form = 3;
-        d.shape = PipeShapeBits(sh);
+        d.shape = PipeShapeBits(sh) | (has_clean ? kPipeShapeCleanBit : 0);
         d.workgroups = sh.workgroups;
         d.waves_per_workgroup = PipelinedWorkgroupWaves(sh);
         d.workgroups_per_cu = p.pipe.wgs_per_cu > 0 ? p.pipe.wgs_per_cu : PipelinedWorkgroupsPerCu(sh);
@@ -419,7 +421,7 @@ bool BuildRaggedPipePlan(const int32_t *lens, int S, const PipeShape &shape, int
 }
 
 LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, const int32_t *lens, bool has_clean,
-                                           RaggedPlan *plan_out, bool ragged_pipelining, RaggedPipePlan *pipe_out) {
+                                           RaggedPlan *plan_out, bool ragged_pipelining, RaggedPipePlan *pipe_out, bool clean_pipelining) {
     RaggedPlan local;
     RaggedPlan &plan = plan_out ? *plan_out : local;
     LaunchDescription d;
@@ -438,7 +440,7 @@ LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, i
     if (longest == 0) {
         // nothing to launch
     } else if (sum == (int64_t)count * longest) {                 // every stream the same length: the equal-length launch, whatever its form
-        d = DescribeLaunchWith(p, variant, count, longest, has_clean);
+        d = DescribeLaunchWith(p, variant, count, longest, has_clean, clean_pipelining);
         chunk = d.form == 2 ? d.chunk_blocks : 0;                 // (the plan then tells the caller the queue's item count)
     } else {
         chunk = QueueChunkFor(p, live);
@@ -554,8 +556,9 @@ bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, int count,
         queue_unchecked_ = true;
         return AECM_HIP_OK(LaunchProcessBlocksQueued(st, io, count, num_blocks, chunk, policy_.resident_waves, queue_ctl_, queue_err_, stream_));
     }
-    if (PipelinedLaunchApplies(policy_, variant_, count, num_blocks, io.near_clean != nullptr, blocks_per_stream_dev != nullptr)) {
-        const PipeShape shape = PipelinedShapeFor(count, num_blocks, policy_.compute_units, policy_.pipe);
+    if (PipelinedLaunchApplies(policy_, variant_, count, num_blocks, io.near_clean != nullptr, blocks_per_stream_dev != nullptr, clean_pipelining_)) {
+        const PipeShape shape = io.near_clean ? PipelinedCleanShapeFor(count, num_blocks, policy_.compute_units, policy_.pipe)
+                                              : PipelinedShapeFor(count, num_blocks, policy_.compute_units, policy_.pipe);
         bool need_ctl = shape.balance;
 #if defined(AECM_PIPE_TRACE)
         need_ctl = true;                      // (the diagnostics build keeps the buffer: its per-wave records live behind the progress words)
@@ -568,7 +571,7 @@ bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, int count,
 }
 
 int BatchEngine::DescribeLaunch(int num_blocks, bool has_clean, int *chunk_blocks) const {
-    const LaunchDescription d = DescribeLaunchWith(policy_, variant_, num_streams_, num_blocks, has_clean);
+    const LaunchDescription d = DescribeLaunchWith(policy_, variant_, num_streams_, num_blocks, has_clean, clean_pipelining_);
     if (chunk_blocks) *chunk_blocks = d.form == 2 ? d.chunk_blocks : d.form == 3 ? d.shape : 0;
     return d.form;
 }
@@ -621,7 +624,7 @@ int32_t BatchEngine::ProcessBlocksRaggedRange(const IoView &io, int num_blocks, 
     if (first < 0 || count < 0 || first + count > num_streams_ || num_blocks < 0 || !lens) return kErrBadParameter;
     RaggedPlan plan;
     RaggedPipePlan pipe;
-    const LaunchDescription d = DescribeRaggedLaunchWith(policy_, variant_, count, num_blocks, lens, io.near_clean != nullptr, &plan, ragged_pipelining_, &pipe);
+    const LaunchDescription d = DescribeRaggedLaunchWith(policy_, variant_, count, num_blocks, lens, io.near_clean != nullptr, &plan, ragged_pipelining_, &pipe, clean_pipelining_);
     if (d.form < 0) return kErrBadParameter;
     if (plan.max_blocks == 0) return 0;
     if (plan.sum_blocks == (int64_t)count * plan.max_blocks)          // every stream the same length: today's launch, whatever its form

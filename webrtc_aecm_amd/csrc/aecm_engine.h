@@ -45,7 +45,9 @@ struct LaunchDescription {
     int rounds_x1000 = 0;           // 1000 x workgroups / (CUs x workgroups_per_cu): 1000 = the chip exactly full once; 9140 = nine full rounds and one 14 % full
     int cu_load_evenness_x1000 = 1000;   // pipelined: 1000 x (streams / CUs) / streams on the fullest CU
 };
-LaunchDescription DescribeLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, bool has_clean);
+// clean_pipelining: the batch's opt-in (BatchEngine::set_clean_pipelining) -- a launch WITH a clean input that meets the pipelined form's
+// other conditions is pipelined too (shape bits of PipelinedCleanShapeFor + 0x2000); false: such a launch is never pipelined.
+LaunchDescription DescribeLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, bool has_clean, bool clean_pipelining = false);
 LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units);
 
 // A ragged launch: stream s runs len[s] blocks.  Pure host logic (no device), so that it can be tested and used for planning.
@@ -102,7 +104,8 @@ bool BuildRaggedPipePlan(const int32_t *blocks_per_stream, int num_streams, cons
 // longest has at least pipelined_min_blocks blocks; else one wavefront per stream, each with its own block count.
 // form < 0: a length outside [0, num_blocks].
 LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, const int32_t *blocks_per_stream,
-                                           bool has_clean, RaggedPlan *plan_out, bool ragged_pipelining = false, RaggedPipePlan *pipe_out = nullptr);
+                                           bool has_clean, RaggedPlan *plan_out, bool ragged_pipelining = false, RaggedPipePlan *pipe_out = nullptr,
+                                           bool clean_pipelining = false);      // (clean_pipelining: for the all-lengths-equal case, which IS the equal-length launch)
 
 class BatchEngine {
 public:
@@ -139,11 +142,16 @@ public:
     bool ProcessRecordingsRagged(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, int frame,
                                  int n_calls, const int32_t *calls_per_stream_host, int16_t ms, bool host_pointers, int32_t *rc, int32_t *codes_host);
     LaunchDescription DescribeRaggedLaunch(int num_blocks, const int32_t *blocks_per_stream_host, bool has_clean, RaggedPlan *plan_out) const {
-        return DescribeRaggedLaunchWith(policy_, variant_, num_streams_, num_blocks, blocks_per_stream_host, has_clean, plan_out, ragged_pipelining_);
+        return DescribeRaggedLaunchWith(policy_, variant_, num_streams_, num_blocks, blocks_per_stream_host, has_clean, plan_out, ragged_pipelining_, nullptr,
+                                        clean_pipelining_);
     }
     // Ragged launches the chip holds at once take the pipelined form (DescribeRaggedLaunchWith's rule).  Off by default.
     void set_ragged_pipelining(bool on) { ragged_pipelining_ = on; }
     bool ragged_pipelining() const { return ragged_pipelining_; }
+    // Equal-length launches with a clean near-end input that the chip holds at once take the pipelined form (DescribeLaunchWith's rule).
+    // Off by default.  Ragged launches with a clean input are not pipelined by either switch.
+    void set_clean_pipelining(bool on) { clean_pipelining_ = on; }
+    bool clean_pipelining() const { return clean_pipelining_; }
     // Whole recordings as sessions: every stream is driven like a fresh WebRtcAecm_* session by
     // n_calls x (BufferFarend, Process) of `frame` samples with a constant msInSndCardBuf
     // (aecm_session_flow.h).  far/near/clean/out: [S][>= n_calls*frame], device (or host) pointers; clean
@@ -206,6 +214,7 @@ private:
     bool TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged, int ragged_form,
                      const RaggedPipePlan *pipe = nullptr);
     bool ragged_pipelining_ = false;
+    bool clean_pipelining_ = false;
     // The plan's way to the device: a pinned staging buffer (grown on first use) and the event behind its last upload -- the
     // buffer is rewritten only when that copy has run, so ragged launches queue back to back like the others.
     uint32_t *plan_host_ = nullptr;

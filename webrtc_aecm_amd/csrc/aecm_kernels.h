@@ -49,8 +49,8 @@ hipError_t LaunchProcessBlocksRaggedQueued(const StatePtrs &st, const IoView &io
 
 // The pipelined form of a launch the chip holds at once (aecm_block_kernels.hip): a workgroup serves four streams with one
 // "back" wave per stream and, in waves of their own, the state-independent forward transforms one block ahead (front waves)
-// and -- in some shapes -- the inverse transforms one block behind (tail waves).  Fast variant, no clean input, every stream
-// the same number of blocks.
+// and -- in some shapes -- the inverse transforms one block behind (tail waves).  Fast variant, every stream the same number of
+// blocks; a launch with a clean input (io.near_clean) takes aecm_process_pipelined_clean_kernel, in the shapes PipelinedCleanShapeFor gives.
 struct PipeShape {
     int tail_waves;      // 0 or 2 per workgroup
     int front_waves;     // 2 (two streams each) or 4 (one each; with tail waves only)
@@ -74,6 +74,10 @@ struct PipeWishes {
 };
 // The shape a launch of this size takes on a device of compute_units CUs.
 PipeShape PipelinedShapeFor(int n_streams, int n_blocks, int compute_units, const PipeWishes &wishes = PipeWishes());
+// The same for a launch with a clean near-end input: by the same sizes, on the shapes the clean kernel is carried in (formed spectra,
+// no balance: 6, 8, 12 and 16 waves); a wish for another shape lands on the nearest of them.  The stream limits are those of the
+// shapes without a clean input (aecm_block_kernels.hip asserts that the larger hand-over slots leave the workgroups per CU alone).
+PipeShape PipelinedCleanShapeFor(int n_streams, int n_blocks, int compute_units, const PipeWishes &wishes = PipeWishes());
 int PipelinedStreamLimit(int compute_units, int tail_waves, int front_waves = 2, int delay_waves = 0, int gain_waves = 0, int wgs_per_cu = 0);
 // Waves of a workgroup of this shape, and how many such workgroups a CU holds at once (by the wave slots the kernel is built for and the LDS it declares).
 int PipelinedWorkgroupWaves(const PipeShape &shape);

@@ -1,5 +1,6 @@
-// The text of the pipelined kernels' body (aecm_block_kernels.hip includes it into aecm_process_pipelined_kernel and
-// aecm_process_pipelined_ragged_kernel, behind a `constexpr bool kRagged`; not a header: no guard, no declarations of its own).
+// The text of the pipelined kernels' body (aecm_block_kernels.hip includes it into aecm_process_pipelined_kernel,
+// aecm_process_pipelined_ragged_kernel and aecm_process_pipelined_clean_kernel, behind `constexpr bool kRagged, kClean`; not a
+// header: no guard, no declarations of its own).
 // In scope: the template arguments kTail, kBalance, kRaw, kFront, kDelay, kGain and the kernel arguments st, io, streams_base,
 // streams_rem, n_blocks, progress, n_workgroups, wgs_per_round, rot, prio.
     constexpr int kFrontBehind = kBalance ? kPipeFrontPrioBehind : AECM_PIPE_FRONT_PRIO;
@@ -15,15 +16,22 @@
     static_assert(kDelay == 0 || (kPipeStreams % kDelay == 0 && !kRaw), "delay waves: in the shapes with formed spectra");
     static_assert(kGain == 0 || (kGain == kPipeStreams && kDelay != 0), "gain waves: one per stream, with delay waves");
     static_assert(!kRagged || !kBalance, "ragged launches: the unbalanced shapes (the balance's slowest-workgroup rule assumes equal work)");
+    static_assert(!kClean || (!kRaw && !kBalance && !kRagged), "clean launches: formed spectra, no balance, equal lengths");
     constexpr int kWaves = PipeWaves(kTail, kFront, kDelay, kGain), kPipeFrontWaves = kFront, kPipeStreamsPerFront = kPipeStreams / kFront;
     constexpr int kLagD = kDelay ? 1 : 0, kLagG = kGain ? 1 : 0;           // steps the delay / gain waves put between the front waves and the rest
     constexpr int kSlots = 2 + kLagD + kLagG;
-    PipeShared<kTail, kRaw, kDelay, kGain> &sh = *reinterpret_cast<PipeShared<kTail, kRaw, kDelay, kGain> *>(&g_lds[1]);        // behind the tables
+    PipeShared<kTail, kRaw, kDelay, kGain, kClean> &sh = *reinterpret_cast<PipeShared<kTail, kRaw, kDelay, kGain, kClean> *>(&g_lds[1]);        // behind the tables
     if (kBalance && threadIdx.x == 0) { sh.ahead = 0; sh.level = kFrontBehind; }
     FillLdsTables<64 * kWaves>(st.consts);                              // ends in a barrier
     using W = Gfx950Wave<true, true>;
-    using E = BlockEngine<W, false>;
-    using EF = BlockEngine<Gfx950Wave<true, false>, false>;               // the front and tail waves keep one priority (no per-phase s_setprio)
+    using E = BlockEngine<W, kClean>;
+    using EF = BlockEngine<Gfx950Wave<true, false>, kClean>;              // the front and tail waves keep one priority (no per-phase s_setprio)
+    // Clean launches (kClean): the front waves run the clean input's transform with the other two and hand the three spectra over as
+    // BlockEngine::CleanHandOver (PipeCleanSlot); everything behind the delay waves works with the clean spectrum `cf` where the other
+    // launches pass the near-end one twice.  c_old, the clean input's last block, shares V_OUTBUF's word with the overlap buffer: the
+    // front wave loads its half at the start, and leaves the launch's last clean block in sh.c_last in its last (otherwise empty)
+    // step -- before a barrier every wave executes -- for the wave that stores that word.  No input row is read again at the end:
+    // out may alias an input.
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // This workgroup's streams (PipeSplit, below): streams_base of them, one more in the first streams_rem workgroups -- the
     // dispatcher deals workgroups out to the CUs in turn, so the CUs' loads differ by at most one stream.  A workgroup with fewer
@@ -103,9 +111,13 @@
         for (int blk = 0; blk < n_blocks; ++blk) {                        // step blk + 1 (+ 1 with delay waves)
             if (live && (!kRagged || blk < len)) {
                 const int lane = W::lane_id();
-                typename E::Spectrum xf, df;
+                typename E::Spectrum xf, df, cf;
+                const typename E::Spectrum &clean = kClean ? cf : df;
                 r.table_index = W::table_index_for_this_block();
-                if constexpr (kRaw) {
+                if constexpr (kClean) {
+                    const PipeCleanSlot &slot_in = sh.slots[slot_idx][slot];
+                    E::unpack_clean_hand_over({slot_in.clean_x[lane], slot_in.mags[lane], slot_in.clean_mag[lane], slot_in.scalars[lane]}, xf, df, cf);
+                } else if constexpr (kRaw) {
                     const PipeRawSlot &slot_in = sh.slots[slot_idx][slot];
                     const int fa0 = slot_in.fa[0][lane], fb0 = slot_in.fb[0][lane], fa1 = slot_in.fa[1][lane], fb1 = slot_in.fb[1][lane];
                     const int q0 = __builtin_amdgcn_readfirstlane(slot_in.q[0]), q1 = __builtin_amdgcn_readfirstlane(slot_in.q[1]);
@@ -135,20 +147,20 @@
                 if constexpr (kTail != 0) {
                     if constexpr (kGain != 0) {
                         W::template phase_priority<3>();
-                        E::track_q(r.u, df, df);
+                        E::track_q(r.u, df, clean);
                         const typename E::GainInput g = E::template channel_block<true>(r, hist, xf, df, delay_given, far_given);
                         PipeGainSlot &gs = sh.gains[blk & 1][slot];
                         gs.echo_est[lane] = g.echo_est;
                         if (lane == 0) { gs.echo_est64 = g.echo_est64; gs.far_q = g.far_q; gs.cur_vad = g.cur_vad; gs.near0 = g.near0; gs.stored0 = g.stored0; }
                     } else {
-                        const typename E::TailInput t = E::template middle_block<kDelay != 0>(r, hist, xf, df, df, delay_given, far_given);
+                        const typename E::TailInput t = E::template middle_block<kDelay != 0>(r, hist, xf, df, clean, delay_given, far_given);
                         PipeTailSlot &ts = sh.tails[blk & 1][slot];
                         ts.a[lane] = t.a;
                         ts.b[lane] = t.b;
                         if (lane == 0) ts.clean_q = t.clean_q;
                     }
                 } else {
-                    const typename E::TailInput t = E::template middle_block<kDelay != 0>(r, hist, xf, df, df, delay_given, far_given);
+                    const typename E::TailInput t = E::template middle_block<kDelay != 0>(r, hist, xf, df, clean, delay_given, far_given);
                     const int out = E::tail_block(r, t.a, t.b, t.clean_q);        // (= back_block)
                     sio.out(r, blk, out);
                 }
@@ -173,6 +185,8 @@
                 r.b64.echo_filt = S(4); r.b64.near_filt = S(5); r.b64.noise_est = S(6); r.b64.low_ctr = S(7); r.b64.high_ctr = S(8);
             }
         }
+        if constexpr (kClean && kTail == 0)
+            if (live) r.c_old = sh.c_last[slot][W::lane_id()];            // (the front wave's last step lies before this wave's last barrier)
         if (live) E::template store_state<false, kTail == 0, kDelay == 0>(r, vec, scal);
     } else if (wave < kPipeStreams + kPipeFrontWaves) {
         // ---- front wave: two streams, the transforms of the block after the one their back waves are at ----
@@ -182,6 +196,7 @@
         SetPrioDynamic(level);
         k0 = slot_of((wave - kPipeStreams) * kPipeStreamsPerFront, rot_front);        // (a wave of two slots: k0 and the one after it, round the ring)
         int x_old[kPipeStreamsPerFront], d_old[kPipeStreamsPerFront], far_next[kPipeStreamsPerFront], near_next[kPipeStreamsPerFront];
+        int c_prev[kPipeStreamsPerFront], clean_next[kPipeStreamsPerFront];      // (clean launches)
         bool live[kPipeStreamsPerFront];
         int len[kPipeStreamsPerFront];
         int64_t strm[kPipeStreamsPerFront];                               // (ragged: the plan is read once per wave)
@@ -196,6 +211,11 @@
                 typename EF::StridedIo sio{io, stream * io.stream_stride};
                 far_next[k] = sio.far(r, 0);
                 near_next[k] = sio.near(r, 0);
+                if constexpr (kClean) {
+                    int ovl_unused;
+                    EF::load_tail_state(st.vec + stream * (int64_t)kVecWordsPerStream, r.lane, ovl_unused, c_prev[k]);
+                    clean_next[k] = sio.clean(r, 0);
+                }
             }
         }
         int slot_idx = 0;                                                 // blk mod kSlots
@@ -236,9 +256,27 @@
                         far_next[k] = sio.far(r, blk + 1);
                         near_next[k] = sio.near(r, blk + 1);
                     }
+                    int clean_cur = 0;
+                    if constexpr (kClean) {
+                        clean_cur = clean_next[k];
+                        if (blk + 1 < n_blocks) {
+                            typename EF::StridedIo sio{io, slot_stream(ks(k)) * io.stream_stride};
+                            clean_next[k] = sio.clean(r, blk + 1);
+                        }
+                    }
                     r.table_index = Gfx950Wave<true, false>::table_index_for_this_block();
                     const int lane = W::lane_id();
-                    if constexpr (kRaw) {
+                    if constexpr (kClean) {
+                        typename EF::Spectrum xf, df, cf;
+                        EF::front_block(r, x_old[k], far_cur, d_old[k], near_cur, c_prev[k], clean_cur, xf, df, cf);
+                        const typename EF::CleanHandOver h = EF::pack_clean_hand_over(xf, df, cf);
+                        PipeCleanSlot &slot = sh.slots[slot_idx][ks(k)];
+                        slot.clean_x[lane] = h.clean_x;
+                        slot.mags[lane] = h.mags;
+                        slot.clean_mag[lane] = h.clean_mag;
+                        slot.scalars[lane] = h.scalars;
+                        c_prev[k] = clean_cur;
+                    } else if constexpr (kRaw) {
                         int fa[2], fb[2], q[2];
                         EF::front_transforms(r, x_old[k], far_cur, d_old[k], near_cur, fa, fb, q);
                         PipeRawSlot &slot = sh.slots[slot_idx][ks(k)];
@@ -261,6 +299,13 @@
                     }
                     x_old[k] = far_cur;
                     d_old[k] = near_cur;
+                }
+            }
+            if constexpr (kClean) {
+                if (blk == n_blocks) {                                    // the last step: the clean input's last block -> the wave that stores V_OUTBUF
+#pragma unroll
+                    for (int k = 0; k < kPipeStreamsPerFront; ++k)
+                        if (live[k]) sh.c_last[ks(k)][W::lane_id()] = c_prev[k];
                 }
             }
             if (monitor) {
@@ -325,6 +370,9 @@
             AECM_PIPE_BARRIER();
         }
         if (kGain != 0) AECM_PIPE_BARRIER();                              // (state hand-over of the gain waves)
+        if constexpr (kClean)
+            for (int k = 0; k < kPer; ++k)
+                if (live[k]) c_old[k] = sh.c_last[ks(k)][W::lane_id()];
         for (int k = 0; k < kPer; ++k)
             if (live[k]) EF::store_tail_state(st.vec + (kRagged ? strm[k] : slot_stream(ks(k))) * (int64_t)kVecWordsPerStream, r.lane, ovl[k], c_old[k]);
     } else if constexpr (kDelay != 0) {
@@ -379,7 +427,7 @@
                     fetch[k] = false;
                     if (!live[k]) continue;
                     if (kRagged && blk >= len[k]) continue;
-                    const PipeSlot &slot = sh.slots[slot_idx][ks(k)];
+                    const auto &slot = sh.slots[slot_idx][ks(k)];             // (PipeSlot or PipeCleanSlot: the same two rows)
                     const int m = slot.mags[lane], sc = slot.scalars[lane];
                     typename EF::Spectrum xf, df;
                     xf.mag = zext16(m);
@@ -439,15 +487,22 @@
             for (int blk = 0; blk < n_blocks; ++blk) {                    // step blk + 3
                 if (live && (!kRagged || blk < len)) {
                     const int lane = W::lane_id();
-                    const PipeSlot &slot = sh.slots[slot_idx][k];
-                    const int x = slot.near_x[lane], m = slot.mags[lane], sc = slot.scalars[lane];
-                    typename EF::Spectrum df;
-                    df.re = sext16(x);
-                    df.im = sar(x, 16);
-                    df.mag = lsr(m, 16);
-                    df.re64 = __builtin_amdgcn_readlane(sc, 2);
-                    df.mag64 = __builtin_amdgcn_readlane(sc, 3);
-                    df.q = __builtin_amdgcn_readlane(sc, 4);
+                    typename EF::Spectrum df, cf;
+                    const typename EF::Spectrum &clean = kClean ? cf : df;
+                    if constexpr (kClean) {
+                        const PipeCleanSlot &slot = sh.slots[slot_idx][k];
+                        typename EF::Spectrum xf;
+                        EF::unpack_clean_hand_over({slot.clean_x[lane], slot.mags[lane], slot.clean_mag[lane], slot.scalars[lane]}, xf, df, cf);
+                    } else {
+                        const PipeSlot &slot = sh.slots[slot_idx][k];
+                        const int x = slot.near_x[lane], m = slot.mags[lane], sc = slot.scalars[lane];
+                        df.re = sext16(x);
+                        df.im = sar(x, 16);
+                        df.mag = lsr(m, 16);
+                        df.re64 = __builtin_amdgcn_readlane(sc, 2);
+                        df.mag64 = __builtin_amdgcn_readlane(sc, 3);
+                        df.q = __builtin_amdgcn_readlane(sc, 4);
+                    }
                     const PipeGainSlot &gs = sh.gains[blk & 1][k];
                     typename EF::GainInput g;
                     g.echo_est = gs.echo_est[lane];
@@ -457,8 +512,8 @@
                     g.near0 = __builtin_amdgcn_readfirstlane(gs.near0);
                     g.stored0 = __builtin_amdgcn_readfirstlane(gs.stored0);
                     r.table_index = Gfx950Wave<true, false>::table_index_for_this_block();
-                    EF::track_q(r.u, df, df);
-                    const typename EF::TailInput t = EF::gain_block(r, df, df, g);
+                    EF::track_q(r.u, df, clean);
+                    const typename EF::TailInput t = EF::gain_block(r, df, clean, g);
                     PipeTailSlot &ts = sh.tails[blk & 1][k];
                     ts.a[lane] = t.a;
                     ts.b[lane] = t.b;

@@ -1251,6 +1251,48 @@ struct BlockEngine {
         fft128<false, true, 2, 1>(fa, fb, r.k_p);
     }
 
+    // The three spectra of a block on their way from the front role to the roles behind it when the launch has a clean input (the
+    // pipelined kernel's PipeCleanSlot, and the lane simulator's copy of it): what those roles read and nothing else -- of the far end
+    // mag / mag64 / q, of the near end the same (its bins feed the energies and the delay estimator only), of the clean input everything.
+    //   clean_x    clean re | im << 16            mags       far mag | near mag << 16 (both <= 46 340)
+    //   clean_mag  clean mag                      scalars    lanes 0, 1: far mag64, q; 3, 4: near mag64, q; 5, 6, 7: clean re64, mag64, q
+    // (lanes 0..4 of `scalars` and `mags` are PipeSlot's, which the delay waves read without knowing which of the two they have)
+    struct CleanHandOver {
+        vi clean_x, mags, clean_mag, scalars;
+    };
+    static AECM_HD CleanHandOver pack_clean_hand_over(const Spectrum &xf, const Spectrum &df, const Spectrum &cf) {
+        CleanHandOver h;
+        h.clean_x = (cf.re & 0xffff) | shl(cf.im, 16);
+        h.mags = xf.mag | shl(df.mag, 16);
+        h.clean_mag = cf.mag;
+        vi sc = vi(0);
+        sc = W::writelane(sc, xf.mag64, 0);
+        sc = W::writelane(sc, xf.q, 1);
+        sc = W::writelane(sc, df.mag64, 3);
+        sc = W::writelane(sc, df.q, 4);
+        sc = W::writelane(sc, cf.re64, 5);
+        sc = W::writelane(sc, cf.mag64, 6);
+        sc = W::writelane(sc, cf.q, 7);
+        h.scalars = sc;
+        return h;
+    }
+    static AECM_HD void unpack_clean_hand_over(const CleanHandOver &h, Spectrum &xf, Spectrum &df, Spectrum &cf) {
+        xf.re = xf.im = vi(0); xf.re64 = 0;
+        xf.mag = zext16(h.mags);
+        xf.mag64 = W::readlane(h.scalars, 0);
+        xf.q = W::readlane(h.scalars, 1);
+        df.re = df.im = vi(0); df.re64 = 0;
+        df.mag = lsr(h.mags, 16);
+        df.mag64 = W::readlane(h.scalars, 3);
+        df.q = W::readlane(h.scalars, 4);
+        cf.re = sext16(h.clean_x);
+        cf.im = sar(h.clean_x, 16);
+        cf.mag = h.clean_mag;
+        cf.re64 = W::readlane(h.scalars, 5);
+        cf.mag64 = W::readlane(h.scalars, 6);
+        cf.q = W::readlane(h.scalars, 7);
+    }
+
     static AECM_HD vi process_block(Regs &r, uint16_t *hist, vi far_new, vi near_new, vi clean_new) {
         update_startup(r.u);
         if (W::kLaneConstsInTable) r.table_index = W::table_index_for_this_block();

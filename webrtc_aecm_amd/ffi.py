@@ -49,6 +49,7 @@ BATCH_SYMBOLS = [
     "WebRtcAecmBatch_ProcessRecordingsRaggedHost", "WebRtcAecmBatch_DescribeRaggedLaunch", "WebRtcAecmBatch_RaggedPlan",
     "WebRtcAecmBatch_SetRaggedPipelining", "WebRtcAecmBatch_DescribeRaggedLaunchEx", "WebRtcAecmBatch_RaggedPipePlan",
     "WebRtcAecmBatch_DescribeRaggedLaunchOf",
+    "WebRtcAecmBatch_SetCleanPipelining", "WebRtcAecmBatch_DescribeLaunchDetailEx",
 ]
 SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_Create", "WebRtcAecmSessions_Free", "WebRtcAecmSessions_Init", "WebRtcAecmSessions_set_config",
@@ -151,6 +152,10 @@ def load():
                                                                C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                                C.POINTER(C.c_int32)]
         lib.WebRtcAecmBatch_RaggedPipePlan.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, vp, vp, C.c_int32, C.POINTER(C.c_int32)]
+    if hasattr(lib, "WebRtcAecmBatch_SetCleanPipelining"):      # (as above: absent from a library built from an older tree)
+        lib.WebRtcAecmBatch_SetCleanPipelining.argtypes = [vp, C.c_int32]
+        lib.WebRtcAecmBatch_DescribeLaunchDetailEx.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                               C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmBatch_Synchronize.argtypes = [vp]
     lib.WebRtcAecmBatch_GetLastLaunchMs.argtypes = [vp, C.POINTER(C.c_float)]
     lib.WebRtcAecmBatch_GetTimers.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -323,6 +328,11 @@ class AecmBatch:
         """Ragged launches the chip holds at once take the pipelined form (include/aecm_batch.h: WebRtcAecmBatch_SetRaggedPipelining;
         results never depend on it).  Off by default."""
         self._check(self.lib.WebRtcAecmBatch_SetRaggedPipelining(self.h, 1 if enable else 0), "SetRaggedPipelining")
+
+    def set_clean_pipelining(self, enable=True):
+        """Equal-length launches with a clean near-end input that the chip holds at once take the pipelined form
+        (include/aecm_batch.h: WebRtcAecmBatch_SetCleanPipelining; results never depend on it).  Off by default."""
+        self._check(self.lib.WebRtcAecmBatch_SetCleanPipelining(self.h, 1 if enable else 0), "SetCleanPipelining")
 
     def launch_policy(self) -> AecmLaunchPolicy:
         p = AecmLaunchPolicy()
@@ -779,12 +789,17 @@ def default_launch_policy(compute_units: int) -> AecmLaunchPolicy:
     return p
 
 
-def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int = 0, clean: bool = False, policy=None) -> dict:
+def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int = 0, clean: bool = False, policy=None,
+                           clean_pipelining: bool = False) -> dict:
     """Form, shape, grid and chip quantisation of a launch (include/aecm_batch.h: AecmLaunchDescription), without a device:
-    under `policy` (an AecmLaunchPolicy) or the default policy of compute_units."""
+    under `policy` (an AecmLaunchPolicy) or the default policy of compute_units.  clean_pipelining: as on a batch that has
+    opted in (AecmBatch.set_clean_pipelining)."""
     d = AecmLaunchDescription()
-    rc = load().WebRtcAecmBatch_DescribeLaunchDetail(C.byref(policy) if policy is not None else None, compute_units, num_streams, num_blocks,
-                                                     1 if clean else 0, C.byref(d))
+    pol = C.byref(policy) if policy is not None else None
+    if clean_pipelining:
+        rc = load().WebRtcAecmBatch_DescribeLaunchDetailEx(pol, compute_units, num_streams, num_blocks, 1 if clean else 0, 1, C.byref(d))
+    else:
+        rc = load().WebRtcAecmBatch_DescribeLaunchDetail(pol, compute_units, num_streams, num_blocks, 1 if clean else 0, C.byref(d))
     if rc != 0:
         raise AecmError(rc, "WebRtcAecmBatch_DescribeLaunchDetail")
     return d.as_dict()
