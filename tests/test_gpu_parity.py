@@ -2209,3 +2209,46 @@ def test_session_migrates_mid_call_between_session_batches(fs, frame, with_clean
     assert rc == 0 and again == sa.export_session(2)[1]                  # slot 0 still mirrors session 2, tick for tick
     sa.close()
     sb.close()
+
+
+@pytest.mark.parametrize("clean_opt_in", [False, True])
+@pytest.mark.parametrize("S,T,pad", [(8, 4, 0), (8, 48, 64), (2 * 8192, 3, 0)])
+def test_host_entry_points_launch_what_the_device_entry_point_launches(S, T, pad, clean_opt_in):
+    """The three host paths of WebRtcAecmBatch_ProcessBlocksHost each make the launch plan of their own launches: the mapped path
+    (the buffers fit 64 KB), the staged path (above it; here with a stream stride that is not dense) and the chunked host pipeline
+    (dense, from 2 x 8 192 streams).  From a fresh Init each must write the bytes and leave the states WebRtcAecmBatch_ProcessBlocks
+    does on device pointers -- without a clean input, and with one on a batch that has opted in to pipelining such launches."""
+    import torch
+    fs, K = 16000, 8
+    far_u, near_u = synth_streams(list(range(900, 900 + K)), max(T, 16), fs)      # (the synthesiser's echo taps need some 10 blocks)
+    idx = np.arange(S) % K
+    stride = T * 64 + pad
+
+    def rows(a):
+        full = np.zeros((S, stride), dtype=np.int16)
+        full[:, :T * 64] = a[idx, :T * 64]
+        return full
+    far, near = rows(far_u), rows(near_u)
+    clean = rows(synth_clean(near_u)) if clean_opt_in else None
+    batches = []
+    for _ in range(2):
+        b = aecm.AecmBatch(S, fs)
+        if clean_opt_in:
+            b.set_clean_pipelining(True)
+        batches.append(b)
+    host, dev = batches
+    out_host = np.zeros_like(near)
+    assert host.lib.WebRtcAecmBatch_ProcessBlocksHost(host.h, far.ctypes.data, near.ctypes.data, None if clean is None else clean.ctypes.data,
+                                                      out_host.ctypes.data, stride, 64, T) == 0
+    dfar, dnear = torch.from_numpy(far).cuda(), torch.from_numpy(near).cuda()
+    dclean = None if clean is None else torch.from_numpy(clean).cuda()
+    dout = torch.zeros_like(dnear)
+    torch.cuda.synchronize()
+    dev.process_device(dfar.data_ptr(), dnear.data_ptr(), dout.data_ptr(), stride, 64, T, None if dclean is None else dclean.data_ptr())
+    dev.synchronize()
+    assert np.array_equal(out_host, dout.cpu().numpy())
+    assert out_host[:, :T * 64].any()
+    for s in sorted(set(range(min(S, K))) | {S // 2 - 1, S // 2, S - 1}):
+        assert np.array_equal(host.digest(s), dev.digest(s)), s
+    host.close()
+    dev.close()

@@ -5,7 +5,7 @@
 //   aecm_process_pipelined_kernel  launches the chip holds at once: six waves per four streams, transforms one block ahead
 //   aecm_process_pipelined_ragged_kernel  the same for streams of different lengths (opt-in): each slot of a workgroup its own length
 //   aecm_process_pipelined_clean_kernel   the same for launches with a clean near-end input (opt-in): three transforms in the front waves
-// (aecm_engine.cpp: LaunchBlocks picks by the size of the launch; the forms give identical results.)
+// (aecm_engine.cpp: PlanLaunch picks by the size of the launch; the forms give identical results.)
 //
 // The whole persistent state of a stream (~40 lane vectors + ~50 scalars) is loaded into registers once, n_blocks blocks
 // are processed back to back (WebRtcAecm_ProcessBlock-equivalents, aecm_wave.h), and the state is written back once.  Per
@@ -663,8 +663,8 @@ size_t PipelinedTraceOffsetBytes(int n_workgroups) {
 size_t QueueControlBytes(int n_streams) { return ((size_t)kQueueCtlWords + (size_t)n_streams) * sizeof(uint32_t); }
 
 // Whether a launch of this shape takes the chunk-queue kernel (chunk_blocks > 0: the engine's setting).
-bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_blocks, int min_streams, bool ragged) {
-    if (chunk_blocks <= 0 || variant != kVariantFast || ragged) return false;
+bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_blocks, int min_streams) {
+    if (chunk_blocks <= 0 || variant != kVariantFast) return false;
     if (n_streams <= min_streams || n_blocks < 2 * chunk_blocks) return false;
     const int64_t items = (int64_t)n_streams * ((n_blocks + chunk_blocks - 1) / chunk_blocks);
     return items < (int64_t(1) << 31);
@@ -724,7 +724,7 @@ int RotationStreamLimit(int compute_units) {
 }
 
 hipError_t LaunchProcessBlocks(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, int variant,
-                               int rotation_stream_limit, hipStream_t stream, const int32_t *blocks_per_stream) {
+                               bool phase_priority, hipStream_t stream, const int32_t *blocks_per_stream) {
     if (n_streams <= 0 || n_blocks <= 0) return hipSuccess;
     const dim3 grid((n_streams + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup);
     const dim3 block(64 * kWavesPerWorkgroup);
@@ -732,9 +732,9 @@ hipError_t LaunchProcessBlocks(const StatePtrs &st, const IoView &io, int n_stre
     const bool clean = io.near_clean != nullptr;
     // Issue priority by phase of the block when the launch is more waves than the chip holds at once (they then run in
     // rounds and spread over the phases by themselves), the per-block rotation when every wave of the launch is resident
-    // from the start and they would otherwise march in lock step (wave_gfx950.h: kPhasePrio).  The limit belongs to the
-    // engine's device (RotationStreamLimit of its CU count, taken once in BatchEngine::Create): nothing cached here.
-    const bool phase = n_streams > rotation_stream_limit;
+    // from the start and they would otherwise march in lock step (wave_gfx950.h: kPhasePrio).  Which of the two is the launch
+    // plan's decision (aecm_engine.cpp: PlanLaunch, by RotationStreamLimit of the engine's device).
+    const bool phase = phase_priority;
 #define AECM_LAUNCH(F, C, P) hipLaunchKernelGGL((aecm_process_kernel<F, C, P>), grid, block, lds, stream, st, io, n_streams, n_blocks, blocks_per_stream)
     if (variant == kVariantFast) {
         if (clean) { if (phase) AECM_LAUNCH(true, true, true); else AECM_LAUNCH(true, true, false); }

@@ -375,9 +375,9 @@ int32_t WebRtcAecmBatch_DescribeLaunch(const AecmBatch *b, int32_t num_blocks, i
 int32_t WebRtcAecmBatch_DescribeLaunchFor(int32_t num_streams, int32_t compute_units, int32_t num_blocks, int32_t has_clean_input,
                                           int32_t *chunk_blocks) {
     if (num_streams <= 0 || compute_units <= 0 || num_blocks <= 0) return -1;
-    const aecm::LaunchDescription d = aecm::DescribeLaunchWith(aecm::DefaultLaunchPolicy(compute_units), aecm::kVariantFast, num_streams, num_blocks,
-                                                               has_clean_input != 0);
-    if (chunk_blocks) *chunk_blocks = d.form == 2 ? d.chunk_blocks : d.form == 3 ? d.shape : 0;
+    const aecm::LaunchPolicy p = aecm::DefaultLaunchPolicy(compute_units);
+    const aecm::LaunchDescription d = aecm::DescribePlan(p, aecm::PlanLaunch(p, aecm::LaunchSwitches(), num_streams, num_blocks, has_clean_input != 0));
+    if (chunk_blocks) *chunk_blocks = d.detail();
     return d.form;
 }
 
@@ -440,27 +440,8 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int
     return WebRtcAecmBatch_DescribeLaunchDetailEx(policy, compute_units, num_streams, num_blocks, has_clean_input, 0, out);
 }
 
-int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
-                                               int32_t has_clean_input, int32_t clean_pipelining, AecmLaunchDescription *out) {
-    if (!out) return AECM_NULL_POINTER_ERROR;
-    if (num_streams <= 0 || num_blocks <= 0) return AECM_BAD_PARAMETER_ERROR;
-    aecm::LaunchPolicy p;
-    if (policy) {
-        if (policy->struct_size != (int32_t)sizeof(AecmLaunchPolicy)) return AECM_BAD_PARAMETER_ERROR;
-        p = PolicyFromAbi(*policy);
-        if (!aecm::LaunchPolicyValid(p) || p.compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
-    } else {
-        if (compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
-        p = aecm::DefaultLaunchPolicy(compute_units);
-    }
-    DescriptionToAbi(aecm::DescribeLaunchWith(p, aecm::kVariantFast, num_streams, num_blocks, has_clean_input != 0, clean_pipelining != 0), out);
-    return 0;
-}
-
-// The policy a planning call runs by (the caller's, or the default one of compute_units) and the longest of the lengths; 0 or the error code.
-static int32_t RaggedPlanningArguments(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, const int32_t *lens,
-                                       aecm::LaunchPolicy *p, int32_t *longest) {
-    if (num_streams <= 0) return AECM_BAD_PARAMETER_ERROR;
+// The policy a planning call runs by: the caller's if it is a valid one, else the default one of compute_units; 0 or the error code.
+static int32_t ResolvePolicy(const AecmLaunchPolicy *policy, int32_t compute_units, aecm::LaunchPolicy *p) {
     if (policy) {
         if (policy->struct_size != (int32_t)sizeof(AecmLaunchPolicy)) return AECM_BAD_PARAMETER_ERROR;
         *p = PolicyFromAbi(*policy);
@@ -469,6 +450,11 @@ static int32_t RaggedPlanningArguments(const AecmLaunchPolicy *policy, int32_t c
         if (compute_units <= 0) return AECM_BAD_PARAMETER_ERROR;
         *p = aecm::DefaultLaunchPolicy(compute_units);
     }
+    return 0;
+}
+
+// The longest of the lengths; 0 or AECM_BAD_PARAMETER_ERROR (a negative length).
+static int32_t LongestLength(const int32_t *lens, int32_t num_streams, int32_t *longest) {
     *longest = 0;
     for (int32_t s = 0; s < num_streams; ++s) {
         if (lens[s] < 0) return AECM_BAD_PARAMETER_ERROR;
@@ -477,22 +463,40 @@ static int32_t RaggedPlanningArguments(const AecmLaunchPolicy *policy, int32_t c
     return 0;
 }
 
+// What the ragged describing calls return: the description and (each may be null) the plan's sums.
+static int32_t RaggedDescriptionToAbi(const aecm::LaunchDescription &d, const aecm::LaunchPlan &plan, AecmLaunchDescription *out, int64_t *items,
+                                      int64_t *sum_blocks, int32_t *max_blocks) {
+    if (d.form < 0) return AECM_BAD_PARAMETER_ERROR;
+    DescriptionToAbi(d, out);
+    if (items) *items = d.form == 2 ? plan.ragged.items : 0;
+    if (sum_blocks) *sum_blocks = plan.ragged.sum_blocks;
+    if (max_blocks) *max_blocks = plan.ragged.max_blocks;
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
+                                               int32_t has_clean_input, int32_t clean_pipelining, AecmLaunchDescription *out) {
+    if (!out) return AECM_NULL_POINTER_ERROR;
+    if (num_streams <= 0 || num_blocks <= 0) return AECM_BAD_PARAMETER_ERROR;
+    aecm::LaunchPolicy p;
+    if (const int32_t rc = ResolvePolicy(policy, compute_units, &p)) return rc;
+    const aecm::LaunchSwitches sw{aecm::kVariantFast, false, clean_pipelining != 0};
+    DescriptionToAbi(aecm::DescribePlan(p, aecm::PlanLaunch(p, sw, num_streams, num_blocks, has_clean_input != 0)), out);
+    return 0;
+}
+
 int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
                                                const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
                                                AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
     if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
+    if (num_streams <= 0) return AECM_BAD_PARAMETER_ERROR;
     aecm::LaunchPolicy p;
     int32_t longest = 0;
-    if (const int32_t rc = RaggedPlanningArguments(policy, compute_units, num_streams, blocks_per_stream_host, &p, &longest)) return rc;
-    aecm::RaggedPlan plan;
-    const aecm::LaunchDescription d = aecm::DescribeRaggedLaunchWith(p, aecm::kVariantFast, num_streams, longest, blocks_per_stream_host,
-                                                                     has_clean_input != 0, &plan, ragged_pipelining != 0, nullptr);
-    if (d.form < 0) return AECM_BAD_PARAMETER_ERROR;
-    DescriptionToAbi(d, out);
-    if (items) *items = d.form == 2 ? plan.items : 0;
-    if (sum_blocks) *sum_blocks = plan.sum_blocks;
-    if (max_blocks) *max_blocks = plan.max_blocks;
-    return 0;
+    if (const int32_t rc = ResolvePolicy(policy, compute_units, &p)) return rc;
+    if (const int32_t rc = LongestLength(blocks_per_stream_host, num_streams, &longest)) return rc;
+    const aecm::LaunchSwitches sw{aecm::kVariantFast, ragged_pipelining != 0, false};
+    const aecm::LaunchPlan plan = aecm::PlanRaggedLaunch(p, sw, num_streams, longest, blocks_per_stream_host, has_clean_input != 0);
+    return RaggedDescriptionToAbi(aecm::DescribePlan(p, plan), plan, out, items, sum_blocks, max_blocks);
 }
 
 int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
@@ -507,26 +511,20 @@ int32_t WebRtcAecmBatch_DescribeRaggedLaunchOf(const AecmBatch *b, const int32_t
     if (!b) return -1;
     if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
     int32_t longest = 0;
-    for (int32_t s = 0; s < b->engine->num_streams(); ++s) {
-        if (blocks_per_stream_host[s] < 0) return AECM_BAD_PARAMETER_ERROR;
-        if (blocks_per_stream_host[s] > longest) longest = blocks_per_stream_host[s];
-    }
-    aecm::RaggedPlan plan;
+    if (const int32_t rc = LongestLength(blocks_per_stream_host, b->engine->num_streams(), &longest)) return rc;
+    aecm::LaunchPlan plan;
     const aecm::LaunchDescription d = b->engine->DescribeRaggedLaunch(longest, blocks_per_stream_host, has_clean_input != 0, &plan);
-    if (d.form < 0) return AECM_BAD_PARAMETER_ERROR;
-    DescriptionToAbi(d, out);
-    if (items) *items = d.form == 2 ? plan.items : 0;
-    if (sum_blocks) *sum_blocks = plan.sum_blocks;
-    if (max_blocks) *max_blocks = plan.max_blocks;
-    return 0;
+    return RaggedDescriptionToAbi(d, plan, out, items, sum_blocks, max_blocks);
 }
 
 int32_t WebRtcAecmBatch_RaggedPipePlan(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
                                        const int32_t *blocks_per_stream_host, int32_t *slot_stream, int32_t capacity, int32_t *workgroups) {
     if (!blocks_per_stream_host || !slot_stream || !workgroups) return AECM_NULL_POINTER_ERROR;
+    if (num_streams <= 0) return AECM_BAD_PARAMETER_ERROR;
     aecm::LaunchPolicy p;
     int32_t longest = 0;
-    if (const int32_t rc = RaggedPlanningArguments(policy, compute_units, num_streams, blocks_per_stream_host, &p, &longest)) return rc;
+    if (const int32_t rc = ResolvePolicy(policy, compute_units, &p)) return rc;
+    if (const int32_t rc = LongestLength(blocks_per_stream_host, num_streams, &longest)) return rc;
     int32_t live = 0;
     for (int32_t s = 0; s < num_streams; ++s) live += blocks_per_stream_host[s] > 0;
     if (live == 0 || live > p.pipelined_max_streams) return AECM_BAD_PARAMETER_ERROR;
@@ -545,10 +543,7 @@ int32_t WebRtcAecmBatch_RaggedPlan(int32_t num_streams, const int32_t *blocks_pe
     if (!blocks_per_stream_host || !order || !first_item || !num_chunks) return AECM_NULL_POINTER_ERROR;
     if (num_streams <= 0 || chunk_blocks <= 0) return AECM_BAD_PARAMETER_ERROR;
     int32_t longest = 0;
-    for (int32_t s = 0; s < num_streams; ++s) {
-        if (blocks_per_stream_host[s] < 0) return AECM_BAD_PARAMETER_ERROR;
-        if (blocks_per_stream_host[s] > longest) longest = blocks_per_stream_host[s];
-    }
+    if (const int32_t rc = LongestLength(blocks_per_stream_host, num_streams, &longest)) return rc;
     aecm::RaggedPlan plan;
     if (!aecm::BuildRaggedPlan(blocks_per_stream_host, num_streams, longest, chunk_blocks, &plan)) return AECM_BAD_PARAMETER_ERROR;
     if (plan.items >= (int64_t(1) << 31) || first_item_capacity < plan.n_chunks + 1) return AECM_BAD_PARAMETER_ERROR;

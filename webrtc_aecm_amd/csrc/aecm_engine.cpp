@@ -228,8 +228,6 @@ bool BatchEngine::EnsureLaunchErrorWord() {
     return AECM_HIP_OK(hipMalloc((void **)&queue_err_, sizeof(uint32_t))) && AECM_HIP_OK(hipMemsetAsync(queue_err_, 0, sizeof(uint32_t), stream_));
 }
 
-// One launch of the block kernels over `count` streams (st, io already offset to the first of them), in the chunk-queue form
-// when the launch is larger than the chip (see QueueLaunchApplies).
 // The control words of a chunk-queue or pipelined launch (one buffer, grown on first use; launches on stream_ are ordered, so
 // consecutive launches may share it).
 bool BatchEngine::EnsureLaunchControl(size_t need) {
@@ -244,7 +242,7 @@ bool BatchEngine::EnsureLaunchControl(size_t need) {
 }
 
 // Which form a launch of `count` streams x num_blocks blocks takes under a policy (host logic, no device): the rules of
-// INTEGRATION.md's table.
+// INTEGRATION.md's table, held by PlanLaunch and PlanRaggedLaunch and by nothing else.
 //   chunk queue   every launch of more streams than the pipelined form takes (or than queue_min_streams, when set) that is at least
 //                 two chunks long: above the chip's resident waves because the launch would otherwise end in a long drain, and between
 //                 4 096 streams and that too -- every wave is resident there, but the SIMD's arbiter favours its oldest wave, the waves
@@ -252,6 +250,7 @@ bool BatchEngine::EnsureLaunchControl(size_t need) {
 //                 728 -> 830 M frames/s, 6 144: 844 -> 930 M; profiles/r04_experiments.md section 4).  Shorter chunks there: a quarter.
 //   pipelined     launches the chip holds at once: fast variant, every stream the same number of blocks, and no clean input unless the
 //                 batch has opted in (set_clean_pipelining: aecm_process_pipelined_clean_kernel)
+//   else          one wavefront per stream: by phase priority (form 1) when the launch is more waves than the rotation kernels are built for
 namespace {
 int QueueMinStreams(const LaunchPolicy &p) { return p.queue_min_streams >= 0 ? p.queue_min_streams : p.pipelined_max_streams; }
 // (The quarter rule is for the default chunk; a length set by the caller is taken as it is.)
@@ -259,42 +258,64 @@ int QueueChunkFor(const LaunchPolicy &p, int count) {
     if (p.queue_chunk_blocks <= 0 || count > p.resident_waves || p.queue_chunk_explicit) return p.queue_chunk_blocks;
     return std::max(8, p.queue_chunk_blocks / 4);
 }
-bool PipelinedLaunchApplies(const LaunchPolicy &p, int variant, int count, int num_blocks, bool clean, bool ragged, bool clean_pipelining = false) {
-    return variant == kVariantFast && (!clean || clean_pipelining) && !ragged && count >= p.pipelined_min_streams && count <= p.pipelined_max_streams &&
+bool PipelinedLaunchApplies(const LaunchPolicy &p, int variant, int count, int num_blocks, bool clean, bool clean_pipelining) {
+    return variant == kVariantFast && (!clean || clean_pipelining) && count >= p.pipelined_min_streams && count <= p.pipelined_max_streams &&
            num_blocks >= p.pipelined_min_blocks;
 }
+int WavePerStreamForm(const LaunchPolicy &p, int variant, int count) { return variant == kVariantFast && count > p.rotation_stream_limit ? 1 : 0; }
 int PipeShapeBits(const PipeShape &sh) {
     return sh.tail_waves | (sh.balance ? 0x100 : 0) | (sh.front_waves == 4 ? 0x200 : 0) | (sh.raw ? 0x400 : 0) | (sh.delay_waves ? 0x800 : 0) |
            (sh.gain_waves ? 0x1000 : 0);
 }
 constexpr int kPipeShapeCleanBit = 0x2000;        // the launch runs aecm_process_pipelined_clean_kernel
+int RoundsX1000(int workgroups, int cus, int workgroups_per_cu) { return (int)((int64_t)1000 * workgroups / ((int64_t)cus * std::max(1, workgroups_per_cu))); }
+// The control buffer a ragged plan needs: the pipelined form's plan alone, else the queue's control words with the plan behind them.
+size_t RaggedControlBytes(const LaunchPlan &plan) {
+    return plan.form == 3 ? plan.pipe.words.size() * sizeof(uint32_t) : RaggedQueueControlBytes(plan.count, plan.ragged.n_chunks);
+}
+LaunchPlan UndecidedPlan(int variant, int count, int num_blocks, bool has_clean) {
+    LaunchPlan plan;
+    plan.variant = variant, plan.count = count, plan.num_blocks = num_blocks, plan.has_clean = has_clean;
+    return plan;
+}
 }  // namespace
 
-LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, bool has_clean, bool clean_pipelining) {
-    LaunchDescription d;
-    const int cus = p.compute_units > 0 ? p.compute_units : 256;
-    auto rounds = [&](LaunchDescription &x) { x.rounds_x1000 = (int)((int64_t)1000 * x.workgroups / ((int64_t)cus * std::max(1, x.workgroups_per_cu))); };
+LaunchPlan PlanLaunch(const LaunchPolicy &p, const LaunchSwitches &sw, int count, int num_blocks, bool has_clean) {
+    LaunchPlan plan = UndecidedPlan(sw.variant, count, num_blocks, has_clean);
     const int chunk = QueueChunkFor(p, count);
-    if (QueueLaunchApplies(count, num_blocks, variant, chunk, QueueMinStreams(p), false)) {
-        d.form = 2;
-        d.chunk_blocks = chunk;
-        d.waves_per_workgroup = kWavesPerWorkgroup;
-        d.workgroups = QueueGridWorkgroups(count, p.resident_waves);
-        d.workgroups_per_cu = std::max(p.resident_waves / (cus * kWavesPerWorkgroup), 1);
-        rounds(d);
-        return d;
+    if (QueueLaunchApplies(count, num_blocks, sw.variant, chunk, QueueMinStreams(p))) {
+        plan.form = 2;
+        plan.chunk_blocks = chunk;
+    } else if (PipelinedLaunchApplies(p, sw.variant, count, num_blocks, has_clean, sw.clean_pipelining)) {
+        plan.form = 3;
+        plan.shape = has_clean ? PipelinedCleanShapeFor(count, num_blocks, p.compute_units, p.pipe) : PipelinedShapeFor(count, num_blocks, p.compute_units, p.pipe);
+    } else {
+        plan.form = WavePerStreamForm(p, sw.variant, count);
     }
-    if (PipelinedLaunchApplies(p, variant, count, num_blocks, has_clean, false, clean_pipelining)) {
-        const PipeShape sh = has_clean ? PipelinedCleanShapeFor(count, num_blocks, p.compute_units, p.pipe) : PipelinedShapeFor(count, num_blocks, p.compute_units, p.pipe);
-        d.form = 3;
-        d.shape = PipeShapeBits(sh) | (has_clean ? kPipeShapeCleanBit : 0);
-        d.workgroups = sh.workgroups;
+    return plan;
+}
+
+LaunchDescription DescribePlan(const LaunchPolicy &p, const LaunchPlan &plan) {
+    LaunchDescription d;
+    d.form = plan.form < 0 ? -1 : plan.form;
+    if (plan.form < 0 || (plan.is_ragged && plan.num_blocks == 0)) return d;      // refused lengths; nothing to launch
+    const int cus = p.compute_units > 0 ? p.compute_units : 256;
+    if (plan.form == 2) {
+        d.chunk_blocks = plan.chunk_blocks;
+        d.waves_per_workgroup = kWavesPerWorkgroup;
+        d.workgroups = QueueGridWorkgroups(plan.is_ragged ? plan.ragged.live_streams : plan.count, p.resident_waves);
+        d.workgroups_per_cu = std::max(p.resident_waves / (cus * kWavesPerWorkgroup), 1);
+    } else if (plan.form == 3) {
+        const PipeShape &sh = plan.shape;
+        d.shape = PipeShapeBits(sh) | (plan.has_clean ? kPipeShapeCleanBit : 0);
+        d.workgroups = plan.is_ragged ? plan.pipe.workgroups : sh.workgroups;
         d.waves_per_workgroup = PipelinedWorkgroupWaves(sh);
         d.workgroups_per_cu = p.pipe.wgs_per_cu > 0 ? p.pipe.wgs_per_cu : PipelinedWorkgroupsPerCu(sh);
-        rounds(d);
-        // workgroups i, i + CUs, ... share a CU (the dispatcher deals them out in turn); the first count % workgroups serve one stream more
-        {
-            const int base = count / sh.workgroups, rem = count % sh.workgroups;
+        if (plan.is_ragged) {
+            d.cu_load_evenness_x1000 = plan.pipe.evenness_x1000();
+        } else {
+            // workgroups i, i + CUs, ... share a CU (the dispatcher deals them out in turn); the first count % workgroups serve one stream more
+            const int count = plan.count, base = count / sh.workgroups, rem = count % sh.workgroups;
             int fullest = 0;
             for (int c = 0; c < std::min(cus, sh.workgroups); ++c) {
                 int load = 0;
@@ -303,13 +324,12 @@ LaunchDescription DescribeLaunchWith(const LaunchPolicy &p, int variant, int cou
             }
             d.cu_load_evenness_x1000 = (int)((int64_t)1000 * count / ((int64_t)std::max(fullest, 1) * std::min(cus, sh.workgroups)));
         }
-        return d;
+    } else {
+        d.waves_per_workgroup = kWavesPerWorkgroup;
+        d.workgroups = (plan.count + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup;
+        d.workgroups_per_cu = (plan.form == 1 ? p.resident_waves : std::max(p.rotation_stream_limit, 1)) / (cus * kWavesPerWorkgroup);
     }
-    d.form = variant == kVariantFast && count > p.rotation_stream_limit ? 1 : 0;
-    d.waves_per_workgroup = kWavesPerWorkgroup;
-    d.workgroups = (count + kWavesPerWorkgroup - 1) / kWavesPerWorkgroup;
-    d.workgroups_per_cu = (d.form == 1 ? p.resident_waves : std::max(p.rotation_stream_limit, 1)) / (cus * kWavesPerWorkgroup);
-    rounds(d);
+    d.rounds_x1000 = RoundsX1000(d.workgroups, cus, d.workgroups_per_cu);
     return d;
 }
 
@@ -420,12 +440,9 @@ bool BuildRaggedPipePlan(const int32_t *lens, int S, const PipeShape &shape, int
     return true;
 }
 
-LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, int count, int num_blocks, const int32_t *lens, bool has_clean,
-                                           RaggedPlan *plan_out, bool ragged_pipelining, RaggedPipePlan *pipe_out, bool clean_pipelining) {
-    RaggedPlan local;
-    RaggedPlan &plan = plan_out ? *plan_out : local;
-    LaunchDescription d;
-    // one pass over the lengths decides the form; the plan is then built once, with the chunk that form runs by
+LaunchPlan PlanRaggedLaunch(const LaunchPolicy &p, const LaunchSwitches &sw, int count, int num_blocks, const int32_t *lens, bool has_clean) {
+    LaunchPlan plan;
+    // one pass over the lengths decides the form; the ragged plan is then built once, with the chunk that form runs by
     int live = 0, longest = 0;
     int64_t sum = 0;
     bool valid = count >= 0 && num_blocks >= 0 && (lens || count == 0);
@@ -435,47 +452,28 @@ LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &p, int variant, i
         longest = std::max(longest, (int)lens[s]);
         sum += lens[s];
     }
-    if (!valid) { d.form = -1; return d; }
-    int chunk = 0;
-    if (longest == 0) {
-        // nothing to launch
-    } else if (sum == (int64_t)count * longest) {                 // every stream the same length: the equal-length launch, whatever its form
-        d = DescribeLaunchWith(p, variant, count, longest, has_clean, clean_pipelining);
-        chunk = d.form == 2 ? d.chunk_blocks : 0;                 // (the plan then tells the caller the queue's item count)
+    if (!valid) { plan.form = -1; return plan; }
+    if (longest > 0 && sum == (int64_t)count * longest) {         // every stream the same length: the equal-length launch, whatever its form
+        plan = PlanLaunch(p, sw, count, longest, has_clean);       // (the ragged plan then tells the caller the queue's item count)
     } else {
-        chunk = QueueChunkFor(p, live);
-        int64_t items = 0;
-        if (chunk > 0 && variant == kVariantFast && live > QueueMinStreams(p) && longest >= 2 * chunk)
-            for (int s = 0; s < count; ++s) items += (lens[s] + chunk - 1) / chunk;
-        if (items == 0 || items >= (int64_t(1) << 31)) chunk = 0;
-        // the queue over the live streams, or one wavefront per stream of the whole range, each with its own count (a wave of a
-        // zero-length stream leaves at once): the grid arithmetic is the equal-length launch's with the queue's threshold taken or refused
-        LaunchPolicy q = p;
-        q.pipelined_min_streams = 0x7fffffff;
-        q.queue_chunk_blocks = chunk;
-        q.queue_chunk_explicit = true;
-        q.queue_min_streams = 0;
-        d = DescribeLaunchWith(q, variant, chunk ? live : count, longest, has_clean);
-        // the opt-in: a ragged launch the chip holds at once, pipelined -- by the LIVE streams, not the batch's size
-        if (ragged_pipelining && chunk == 0 && PipelinedLaunchApplies(p, variant, live, longest, has_clean, false)) {
-            RaggedPipePlan pipe_local;
-            RaggedPipePlan &pipe = pipe_out ? *pipe_out : pipe_local;
-            const PipeShape sh = RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe);
-            if (BuildRaggedPipePlan(lens, count, sh, p.compute_units, &pipe)) {
-                const int cus = p.compute_units > 0 ? p.compute_units : 256;
-                d = LaunchDescription();
-                d.form = 3;
-                d.shape = PipeShapeBits(sh);
-                d.workgroups = pipe.workgroups;
-                d.waves_per_workgroup = PipelinedWorkgroupWaves(sh);
-                d.workgroups_per_cu = p.pipe.wgs_per_cu > 0 ? p.pipe.wgs_per_cu : PipelinedWorkgroupsPerCu(sh);
-                d.rounds_x1000 = (int)((int64_t)1000 * d.workgroups / ((int64_t)cus * std::max(1, d.workgroups_per_cu)));
-                d.cu_load_evenness_x1000 = pipe.evenness_x1000();
+        plan = UndecidedPlan(sw.variant, count, longest, has_clean);      // (longest 0: nothing to launch)
+        plan.is_ragged = true;
+        // the queue over the live streams; else -- the opt-in -- a launch the chip holds at once pipelined, by the LIVE streams, not the
+        // batch's size; else one wavefront per stream of the whole range, each with its own count (a wave of a zero-length stream leaves at once)
+        const int chunk = QueueChunkFor(p, live);
+        if (QueueLaunchApplies(live, longest, sw.variant, chunk, QueueMinStreams(p))) {
+            plan.form = 2;
+            plan.chunk_blocks = chunk;
+        } else if (longest > 0) {
+            plan.form = WavePerStreamForm(p, sw.variant, count);
+            if (sw.ragged_pipelining && PipelinedLaunchApplies(p, sw.variant, live, longest, has_clean, false)) {
+                plan.shape = RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe);
+                if (BuildRaggedPipePlan(lens, count, plan.shape, p.compute_units, &plan.pipe)) plan.form = 3;
             }
         }
     }
-    BuildRaggedPlan(lens, count, num_blocks, chunk, &plan);
-    return d;
+    BuildRaggedPlan(lens, count, num_blocks, plan.form == 2 ? plan.chunk_blocks : 0, &plan.ragged);
+    return plan;
 }
 
 // A tick of a session batch (aecm_kernels.hip: aecm_tick_flow_kernel): one wavefront per session, four per workgroup, seven such
@@ -487,7 +485,7 @@ LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units) {
     d.waves_per_workgroup = TickWorkgroupWaves();
     d.workgroups = (num_sessions + d.waves_per_workgroup - 1) / d.waves_per_workgroup;
     d.workgroups_per_cu = TickWorkgroupsPerCu();
-    d.rounds_x1000 = (int)((int64_t)1000 * d.workgroups / ((int64_t)cus * d.workgroups_per_cu));
+    d.rounds_x1000 = RoundsX1000(d.workgroups, cus, d.workgroups_per_cu);
     return d;
 }
 
@@ -524,55 +522,49 @@ bool BatchEngine::UploadPlanWords(const std::vector<uint32_t> &plan_words, uint3
     return true;
 }
 
-bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev,
-                               const RaggedPlan *ragged, int ragged_form, const RaggedPipePlan *pipe) {
+// One launch of the block kernels: the plan's form on the plan's streams (st, io already offset to the first of them).
+bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, const LaunchPlan &plan) {
     if (launch_failed_) return false;                 // streams half processed by an abandoned launch: nothing runs until Init
-    if (ragged && ragged_form == 3) {
-        // the pipelined form: its plan (slots, then lengths) at the start of the control buffer; no control words, nothing to clear
-        if (!pipe || pipe->num_streams != count) return false;
-        if (!EnsureLaunchControl(pipe->words.size() * sizeof(uint32_t))) return false;
-        if (!UploadPlanWords(pipe->words, queue_ctl_)) return false;
-        return AECM_HIP_OK(LaunchProcessBlocksPipelinedRagged(st, io, count, pipe->shape, pipe->workgroups, queue_ctl_, stream_));
+    if (plan.form < 0 || plan.has_clean != (io.near_clean != nullptr)) return false;      // not the plan of this launch
+    const int count = plan.count, num_blocks = plan.num_blocks;
+    const int32_t *lens_dev = nullptr;
+    if (plan.is_ragged) {
+        // one upload per launch, on the engine's stream.  Pipelined: the plan (slots, then lengths) at the start of the control buffer; no
+        // control words, nothing to clear.  Else behind the control words the queue form clears: the whole plan for the queue, for one
+        // wavefront per stream its first part (the lengths) is what aecm_process_kernel reads
+        if (plan.form == 3 && plan.pipe.num_streams != count) return false;
+        if (!EnsureLaunchControl(RaggedControlBytes(plan))) return false;
+        uint32_t *plan_dev = queue_ctl_ + (plan.form == 3 ? 0 : RaggedPlanOffsetWords(count));
+        if (!UploadPlanWords(plan.words(), plan_dev)) return false;
+        lens_dev = reinterpret_cast<const int32_t *>(plan_dev);
     }
-    if (ragged) {
-        // one upload per launch, on the engine's stream, behind the control words the queue form clears: the whole plan for the queue,
-        // for one wavefront per stream its first part (the lengths) is what aecm_process_kernel reads
-        if (!EnsureLaunchControl(RaggedQueueControlBytes(count, ragged->n_chunks))) return false;
-        uint32_t *plan_dev = queue_ctl_ + RaggedPlanOffsetWords(count);
-        if (!UploadRaggedPlan(*ragged, plan_dev)) return false;
-        if (ragged_form == 2) {
-            if (!EnsureLaunchErrorWord()) return false;
-            queue_unchecked_ = true;
-            return AECM_HIP_OK(LaunchProcessBlocksRaggedQueued(st, io, count, ragged->live_streams, (uint32_t)ragged->items, ragged->chunk_blocks,
-                                                               policy_.resident_waves, queue_ctl_, queue_err_, stream_));
-        }
-        return AECM_HIP_OK(LaunchProcessBlocks(st, io, count, num_blocks, variant_, policy_.rotation_stream_limit, stream_,
-                                               reinterpret_cast<const int32_t *>(plan_dev)));
-    }
-    const int chunk = QueueChunkFor(policy_, count);
-    if (QueueLaunchApplies(count, num_blocks, variant_, chunk, QueueMinStreams(policy_), blocks_per_stream_dev != nullptr)) {
-        if (!EnsureLaunchControl(QueueControlBytes(count))) return false;
+    switch (plan.form) {
+    case 2:
+        if (!plan.is_ragged && !EnsureLaunchControl(QueueControlBytes(count))) return false;
         if (!EnsureLaunchErrorWord()) return false;
         queue_unchecked_ = true;
-        return AECM_HIP_OK(LaunchProcessBlocksQueued(st, io, count, num_blocks, chunk, policy_.resident_waves, queue_ctl_, queue_err_, stream_));
-    }
-    if (PipelinedLaunchApplies(policy_, variant_, count, num_blocks, io.near_clean != nullptr, blocks_per_stream_dev != nullptr, clean_pipelining_)) {
-        const PipeShape shape = io.near_clean ? PipelinedCleanShapeFor(count, num_blocks, policy_.compute_units, policy_.pipe)
-                                              : PipelinedShapeFor(count, num_blocks, policy_.compute_units, policy_.pipe);
-        bool need_ctl = shape.balance;
+        if (plan.is_ragged)
+            return AECM_HIP_OK(LaunchProcessBlocksRaggedQueued(st, io, count, plan.ragged.live_streams, (uint32_t)plan.ragged.items, plan.chunk_blocks,
+                                                               policy_.resident_waves, queue_ctl_, queue_err_, stream_));
+        return AECM_HIP_OK(LaunchProcessBlocksQueued(st, io, count, num_blocks, plan.chunk_blocks, policy_.resident_waves, queue_ctl_, queue_err_, stream_));
+    case 3: {
+        if (plan.is_ragged) return AECM_HIP_OK(LaunchProcessBlocksPipelinedRagged(st, io, count, plan.shape, plan.pipe.workgroups, queue_ctl_, stream_));
+        bool need_ctl = plan.shape.balance;
 #if defined(AECM_PIPE_TRACE)
         need_ctl = true;                      // (the diagnostics build keeps the buffer: its per-wave records live behind the progress words)
-        trace_streams_ = shape.workgroups;
+        trace_streams_ = plan.shape.workgroups;
 #endif
-        if (need_ctl && !EnsureLaunchControl(PipelinedControlBytes(shape.workgroups))) return false;
-        return AECM_HIP_OK(LaunchProcessBlocksPipelined(st, io, count, num_blocks, shape, need_ctl ? queue_ctl_ : nullptr, stream_));
+        if (need_ctl && !EnsureLaunchControl(PipelinedControlBytes(plan.shape.workgroups))) return false;
+        return AECM_HIP_OK(LaunchProcessBlocksPipelined(st, io, count, num_blocks, plan.shape, need_ctl ? queue_ctl_ : nullptr, stream_));
     }
-    return AECM_HIP_OK(LaunchProcessBlocks(st, io, count, num_blocks, variant_, policy_.rotation_stream_limit, stream_, blocks_per_stream_dev));
+    default:
+        return AECM_HIP_OK(LaunchProcessBlocks(st, io, count, num_blocks, plan.variant, plan.form == 1, stream_, lens_dev));
+    }
 }
 
 int BatchEngine::DescribeLaunch(int num_blocks, bool has_clean, int *chunk_blocks) const {
-    const LaunchDescription d = DescribeLaunchWith(policy_, variant_, num_streams_, num_blocks, has_clean, clean_pipelining_);
-    if (chunk_blocks) *chunk_blocks = d.form == 2 ? d.chunk_blocks : d.form == 3 ? d.shape : 0;
+    const LaunchDescription d = DescribePlan(policy_, PlanLaunch(policy_, switches_, num_streams_, num_blocks, has_clean));
+    if (chunk_blocks) *chunk_blocks = d.detail();
     return d.form;
 }
 
@@ -607,13 +599,13 @@ bool BatchEngine::CheckQueueError() {
     return err == 0;
 }
 
-bool BatchEngine::ProcessBlocks(const IoView &io, int num_blocks, const int32_t *blocks_per_stream_dev) {
-    return ProcessBlocksRange(io, num_blocks, 0, num_streams_, blocks_per_stream_dev);
+bool BatchEngine::ProcessBlocks(const IoView &io, int num_blocks, const int32_t *retired) {
+    return !retired && ProcessBlocksRange(io, num_blocks, 0, num_streams_);
 }
 
-// Streams [first, first + count); io (and blocks_per_stream_dev) are indexed from `first`.
-bool BatchEngine::ProcessBlocksRange(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev) {
-    return TimedLaunch(io, num_blocks, first, count, blocks_per_stream_dev, nullptr, 0);
+// Streams [first, first + count); io is indexed from `first`.
+bool BatchEngine::ProcessBlocksRange(const IoView &io, int num_blocks, int first, int count) {
+    return TimedLaunch(io, first, PlanLaunch(policy_, switches_, count, num_blocks, io.near_clean != nullptr));
 }
 
 int32_t BatchEngine::ProcessBlocksRagged(const IoView &io, int num_blocks, const int32_t *blocks_per_stream_host) {
@@ -622,20 +614,13 @@ int32_t BatchEngine::ProcessBlocksRagged(const IoView &io, int num_blocks, const
 
 int32_t BatchEngine::ProcessBlocksRaggedRange(const IoView &io, int num_blocks, int first, int count, const int32_t *lens) {
     if (first < 0 || count < 0 || first + count > num_streams_ || num_blocks < 0 || !lens) return kErrBadParameter;
-    RaggedPlan plan;
-    RaggedPipePlan pipe;
-    const LaunchDescription d = DescribeRaggedLaunchWith(policy_, variant_, count, num_blocks, lens, io.near_clean != nullptr, &plan, ragged_pipelining_, &pipe, clean_pipelining_);
-    if (d.form < 0) return kErrBadParameter;
-    if (plan.max_blocks == 0) return 0;
-    if (plan.sum_blocks == (int64_t)count * plan.max_blocks)          // every stream the same length: today's launch, whatever its form
-        return TimedLaunch(io, plan.max_blocks, first, count, nullptr, nullptr, 0) ? 0 : kErrUnspecified;
+    const LaunchPlan plan = PlanRaggedLaunch(policy_, switches_, count, num_blocks, lens, io.near_clean != nullptr);
+    if (plan.form < 0) return kErrBadParameter;
+    if (plan.num_blocks == 0) return 0;
     // (allocations ahead of the launch's timing events)
-    const bool pipelined = d.form == 3;
-    if (!AECM_HIP_OK(hipSetDevice(device_)) ||
-        !EnsureLaunchControl(pipelined ? pipe.words.size() * sizeof(uint32_t) : RaggedQueueControlBytes(count, plan.n_chunks)) ||
-        !EnsurePlanStaging(pipelined ? pipe.words.size() : plan.words.size()))
+    if (plan.is_ragged && (!AECM_HIP_OK(hipSetDevice(device_)) || !EnsureLaunchControl(RaggedControlBytes(plan)) || !EnsurePlanStaging(plan.words().size())))
         return kErrUnspecified;
-    return TimedLaunch(io, plan.max_blocks, first, count, nullptr, &plan, d.form, pipelined ? &pipe : nullptr) ? 0 : kErrUnspecified;
+    return TimedLaunch(io, first, plan) ? 0 : kErrUnspecified;
 }
 
 // Host audio: the live blocks are packed into dense device rows, run, and the blocks that were written are copied back.
@@ -679,9 +664,8 @@ int32_t BatchEngine::ProcessBlocksRaggedHost(const IoView &io, int num_blocks, c
     return 0;
 }
 
-bool BatchEngine::TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged,
-                              int ragged_form, const RaggedPipePlan *pipe) {
-    if (first < 0 || count < 0 || first + count > num_streams_) return false;
+bool BatchEngine::TimedLaunch(const IoView &io, int first, const LaunchPlan &plan) {
+    if (first < 0 || plan.count < 0 || first + plan.count > num_streams_) return false;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
     if (!HarvestTimers(false)) return false;
     if (timer_pending_ == kTimerSlots) {         // ring full: wait for the oldest launch only
@@ -694,7 +678,7 @@ bool BatchEngine::TimedLaunch(const IoView &io, int num_blocks, int first, int c
     st.vec += (size_t)first * kVecWordsPerStream;
     st.scal += (size_t)first * kNumScal;
     st.hist += (size_t)first * kHistWordsPerStream;
-    if (!LaunchBlocks(st, io, count, num_blocks, blocks_per_stream_dev, ragged, ragged_form, pipe)) return false;
+    if (!LaunchBlocks(st, io, plan)) return false;
     if (!AECM_HIP_OK(hipEventRecord(ev_stop_[slot], stream_))) return false;
     ++timer_pending_;
     return true;
@@ -789,7 +773,7 @@ bool BatchEngine::ProcessBlocksHostMapped(const IoView &io, int num_blocks) {
     if (io.near_clean) rows(io.near_clean, mapped_host_ + 2 * per, true);
     IoView dev{mapped_dev_, mapped_dev_ + per, io.near_clean ? mapped_dev_ + 2 * per : nullptr, mapped_dev_ + (size_t)n_in * per,
                (int64_t)row, kBlock};
-    if (!LaunchBlocks(st_, dev, num_streams_, num_blocks, nullptr)) return false;
+    if (!LaunchBlocks(st_, dev, PlanLaunch(policy_, switches_, num_streams_, num_blocks, io.near_clean != nullptr))) return false;
     if (!Drain()) return false;
     rows(io.out, mapped_host_ + (size_t)n_in * per, false);
     return true;
@@ -841,7 +825,7 @@ bool BatchEngine::ProcessBlocksHostPipelined(const IoView &io, int num_blocks) {
         st.scal += first * kNumScal;
         st.hist += first * kHistWordsPerStream;
         IoView dev{dfar + off, dnear + off, io.near_clean ? dclean + off : nullptr, dout + off, (int64_t)row, kBlock};
-        up = up && LaunchBlocks(st, dev, (int)count, num_blocks, nullptr) &&
+        up = up && LaunchBlocks(st, dev, PlanLaunch(policy_, switches_, (int)count, num_blocks, io.near_clean != nullptr)) &&
              AECM_HIP_OK(hipEventRecord(done[k], stream_));
         if (!up) failed = true;
         launched.store(k + 1, std::memory_order_release);
@@ -961,7 +945,7 @@ bool BatchEngine::ProcessRecordingsRagged(const int16_t *far, const int16_t *nea
             if (ok) {
                 IoView io{bfar, bnear, clean ? bclean : nullptr, bout, n_blk, kBlock};
                 ok = calls ? ProcessBlocksRaggedRange(io, sch.n_blocks, (int)s0, (int)C, lens.data() + s0) == 0
-                           : ProcessBlocksRange(io, sch.n_blocks, (int)s0, (int)C, nullptr);
+                           : ProcessBlocksRange(io, sch.n_blocks, (int)s0, (int)C);
             }
         }
         // pass-through samples of the start-up phase come from the clean near-end when there is one

@@ -44,10 +44,8 @@ struct LaunchDescription {
     int workgroups_per_cu = 0;      // of this kernel a CU holds at once
     int rounds_x1000 = 0;           // 1000 x workgroups / (CUs x workgroups_per_cu): 1000 = the chip exactly full once; 9140 = nine full rounds and one 14 % full
     int cu_load_evenness_x1000 = 1000;   // pipelined: 1000 x (streams / CUs) / streams on the fullest CU
+    int detail() const { return form == 2 ? chunk_blocks : form == 3 ? shape : 0; }      // what WebRtcAecmBatch_DescribeLaunch returns beside the form
 };
-// clean_pipelining: the batch's opt-in (BatchEngine::set_clean_pipelining) -- a launch WITH a clean input that meets the pipelined form's
-// other conditions is pipelined too (shape bits of PipelinedCleanShapeFor + 0x2000); false: such a launch is never pipelined.
-LaunchDescription DescribeLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, bool has_clean, bool clean_pipelining = false);
 LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units);
 
 // A ragged launch: stream s runs len[s] blocks.  Pure host logic (no device), so that it can be tested and used for planning.
@@ -96,16 +94,37 @@ struct RaggedPipePlan {
 PipeShape RaggedPipeShapeFor(int live, int max_blocks, int compute_units, const PipeWishes &wishes);
 // false: a negative length, no live stream, a balanced shape, or more live streams than the shape's workgroups have slots.
 bool BuildRaggedPipePlan(const int32_t *blocks_per_stream, int num_streams, const PipeShape &shape, int compute_units, RaggedPipePlan *plan);
-// Which form a ragged launch takes under a policy; *plan_out (may be null) receives the plan it would run with.  Every length equal:
-// exactly DescribeLaunchWith of that length.  Otherwise the chunk queue when the fast variant is selected, more than queue_min_streams
-// streams are live, the longest stream has at least two chunks and the items fit 31 bits; else -- only with ragged_pipelining, the
-// batch's opt-in (BatchEngine::set_ragged_pipelining) -- pipelined (form 3; *pipe_out, may be null, receives that plan) when the fast
-// variant is selected, there is no clean input, the LIVE streams are within [pipelined_min_streams, pipelined_max_streams] and the
-// longest has at least pipelined_min_blocks blocks; else one wavefront per stream, each with its own block count.
-// form < 0: a length outside [0, num_blocks].
-LaunchDescription DescribeRaggedLaunchWith(const LaunchPolicy &policy, int variant, int num_streams, int num_blocks, const int32_t *blocks_per_stream,
-                                           bool has_clean, RaggedPlan *plan_out, bool ragged_pipelining = false, RaggedPipePlan *pipe_out = nullptr,
-                                           bool clean_pipelining = false);      // (clean_pipelining: for the all-lengths-equal case, which IS the equal-length launch)
+// The switches of a batch that the launch rule reads besides the policy.
+struct LaunchSwitches {
+    int variant = kVariantFast;
+    bool ragged_pipelining = false;   // BatchEngine::set_ragged_pipelining: ragged launches the chip holds at once are pipelined
+    bool clean_pipelining = false;    // BatchEngine::set_clean_pipelining: equal-length launches WITH a clean input are pipelined too
+};
+// Everything one launch of the block kernels runs by.  PlanLaunch and PlanRaggedLaunch (pure host logic) are the only places that
+// decide it; BatchEngine launches a plan as it stands and DescribePlan reports it, so what is reported is what runs.
+struct LaunchPlan {
+    int form = 0;                     // AECM_LAUNCH_*; < 0: a length outside [0, num_blocks] (nothing else is set)
+    int variant = kVariantFast;
+    int count = 0, num_blocks = 0;    // streams of the launch; blocks of each (ragged: of the longest; 0: nothing to launch)
+    bool has_clean = false;
+    int chunk_blocks = 0;             // form 2: blocks per item of the queue
+    PipeShape shape{};                // form 3
+    bool is_ragged = false;           // the lengths differ: forms 0 to 2 run by `ragged`, form 3 by `pipe`
+    RaggedPlan ragged;                // PlanRaggedLaunch always fills in the sums (equal lengths too: items = the queue's, if it is form 2)
+    RaggedPipePlan pipe;
+    const std::vector<uint32_t> &words() const { return form == 3 ? pipe.words : ragged.words; }      // (is_ragged) what is uploaded
+};
+// An equal-length launch (the rules of INTEGRATION.md's table; aecm_engine.cpp has the reasons).
+LaunchPlan PlanLaunch(const LaunchPolicy &policy, const LaunchSwitches &sw, int num_streams, int num_blocks, bool has_clean);
+// A ragged launch.  Every length equal: exactly PlanLaunch of that length.  Otherwise the chunk queue when the fast variant is
+// selected, more than queue_min_streams streams are live, the longest stream has at least two chunks and the items fit 31 bits;
+// else -- only with sw.ragged_pipelining -- pipelined when the fast variant is selected, there is no clean input, the LIVE streams
+// are within [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks; else one
+// wavefront per stream, each with its own block count.
+LaunchPlan PlanRaggedLaunch(const LaunchPolicy &policy, const LaunchSwitches &sw, int num_streams, int num_blocks, const int32_t *blocks_per_stream,
+                            bool has_clean);
+// The reporting arithmetic (grid, residency, rounds, evenness): O(workgroups) for a pipelined plan, so never on the launch path.
+LaunchDescription DescribePlan(const LaunchPolicy &policy, const LaunchPlan &plan);
 
 class BatchEngine {
 public:
@@ -125,9 +144,10 @@ public:
     bool SetConfig(int cng_mode, int echo_mode, int first, int count);
     bool SetCngMode(int cng_mode, int first, int count);
     bool Control(int fixed_delay, int nlp_flag, int first, int count);
-    // async; blocks_per_stream_dev (may be null): per-stream block counts <= num_blocks
-    bool ProcessBlocks(const IoView &io_dev, int num_blocks, const int32_t *blocks_per_stream_dev = nullptr);
-    bool ProcessBlocksRange(const IoView &io_dev, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev);
+    // async.  The third parameter is retired (ragged launches go through ProcessBlocksRagged): anything but null is refused.  It stays
+    // in the signature because the engine's CPU double (tests/sim/sim_engine.cpp) defines this member as it has always been declared.
+    bool ProcessBlocks(const IoView &io_dev, int num_blocks, const int32_t *retired = nullptr);
+    bool ProcessBlocksRange(const IoView &io_dev, int num_blocks, int first, int count);
     bool ProcessBlocksHost(const IoView &io_host, int num_blocks);     // sync
     // Ragged launches: stream s runs its first blocks_per_stream_host[s] blocks only (host array, read before the call returns;
     // the Range form's array and io are indexed from `first`).  Its state afterwards is the state after exactly that many blocks,
@@ -141,17 +161,18 @@ public:
     // codes_host (may be null): what each session's calls returned (first non-zero); *rc = the first non-zero of them.
     bool ProcessRecordingsRagged(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, int frame,
                                  int n_calls, const int32_t *calls_per_stream_host, int16_t ms, bool host_pointers, int32_t *rc, int32_t *codes_host);
-    LaunchDescription DescribeRaggedLaunch(int num_blocks, const int32_t *blocks_per_stream_host, bool has_clean, RaggedPlan *plan_out) const {
-        return DescribeRaggedLaunchWith(policy_, variant_, num_streams_, num_blocks, blocks_per_stream_host, has_clean, plan_out, ragged_pipelining_, nullptr,
-                                        clean_pipelining_);
+    // *plan receives the plan described: its `ragged` carries items, sum_blocks and max_blocks.
+    LaunchDescription DescribeRaggedLaunch(int num_blocks, const int32_t *blocks_per_stream_host, bool has_clean, LaunchPlan *plan) const {
+        *plan = PlanRaggedLaunch(policy_, switches_, num_streams_, num_blocks, blocks_per_stream_host, has_clean);
+        return DescribePlan(policy_, *plan);
     }
-    // Ragged launches the chip holds at once take the pipelined form (DescribeRaggedLaunchWith's rule).  Off by default.
-    void set_ragged_pipelining(bool on) { ragged_pipelining_ = on; }
-    bool ragged_pipelining() const { return ragged_pipelining_; }
-    // Equal-length launches with a clean near-end input that the chip holds at once take the pipelined form (DescribeLaunchWith's rule).
+    // Ragged launches the chip holds at once take the pipelined form (PlanRaggedLaunch's rule).  Off by default.
+    void set_ragged_pipelining(bool on) { switches_.ragged_pipelining = on; }
+    bool ragged_pipelining() const { return switches_.ragged_pipelining; }
+    // Equal-length launches with a clean near-end input that the chip holds at once take the pipelined form (PlanLaunch's rule).
     // Off by default.  Ragged launches with a clean input are not pipelined by either switch.
-    void set_clean_pipelining(bool on) { clean_pipelining_ = on; }
-    bool clean_pipelining() const { return clean_pipelining_; }
+    void set_clean_pipelining(bool on) { switches_.clean_pipelining = on; }
+    bool clean_pipelining() const { return switches_.clean_pipelining; }
     // Whole recordings as sessions: every stream is driven like a fresh WebRtcAecm_* session by
     // n_calls x (BufferFarend, Process) of `frame` samples with a constant msInSndCardBuf
     // (aecm_session_flow.h).  far/near/clean/out: [S][>= n_calls*frame], device (or host) pointers; clean
@@ -178,7 +199,7 @@ public:
     // blobs) before any stream is touched.
     bool ExportStates(int first, int count, void *states, bool device);
     int32_t ImportStates(int first, int count, const void *states, bool device);
-    void set_variant(int v) { variant_ = v; }
+    void set_variant(int v) { switches_.variant = v; }
     // blocks = 0: every launch in the one-stream-per-wave form.  min_streams < 0: launches of more streams than the chip
     // holds waves take the queue form (the default); otherwise launches of more than min_streams streams do (tests).
     void set_queue_chunk(int blocks, int min_streams) {
@@ -192,7 +213,7 @@ public:
     void set_pipelined_min_streams(int n) { policy_.pipelined_min_streams = n > 0 ? n : 0x7fffffff; policy_.pipelined_min_blocks = 1; }
     const LaunchPolicy &launch_policy() const { return policy_; }
     bool set_launch_policy(const LaunchPolicy &p);       // false (nothing changed): not a valid policy, or one for another CU count than the device's
-    int variant() const { return variant_; }
+    int variant() const { return switches_.variant; }
     const StatePtrs &state_ptrs() const { return st_; }      // for kernels launched by the session batch on stream()
 
 private:
@@ -207,14 +228,10 @@ private:
     size_t queue_ctl_bytes_ = 0;
     bool queue_unchecked_ = false;       // a queue launch has been enqueued since the error word was last read
     bool launch_failed_ = false;         // a wave of a queue launch gave up: sticky until Init (CheckQueueError)
-    // ragged (may be null): the plan of a ragged launch and the form DescribeRaggedLaunchWith gave it; num_blocks is then its longest stream
-    // (ragged_form 3: the pipelined form, by *pipe)
-    bool LaunchBlocks(const StatePtrs &st, const IoView &io, int count, int num_blocks, const int32_t *blocks_per_stream_dev,
-                      const RaggedPlan *ragged = nullptr, int ragged_form = 0, const RaggedPipePlan *pipe = nullptr);
-    bool TimedLaunch(const IoView &io, int num_blocks, int first, int count, const int32_t *blocks_per_stream_dev, const RaggedPlan *ragged, int ragged_form,
-                     const RaggedPipePlan *pipe = nullptr);
-    bool ragged_pipelining_ = false;
-    bool clean_pipelining_ = false;
+    // Runs the plan on these state pointers (already offset to the launch's first stream) and this io; decides nothing.
+    bool LaunchBlocks(const StatePtrs &st, const IoView &io, const LaunchPlan &plan);
+    bool TimedLaunch(const IoView &io, int first, const LaunchPlan &plan);
+    LaunchSwitches switches_;
     // The plan's way to the device: a pinned staging buffer (grown on first use) and the event behind its last upload -- the
     // buffer is rewritten only when that copy has run, so ragged launches queue back to back like the others.
     uint32_t *plan_host_ = nullptr;
@@ -222,7 +239,6 @@ private:
     hipEvent_t plan_uploaded_ = nullptr;
     bool plan_upload_pending_ = false;
     bool EnsurePlanStaging(size_t words);
-    bool UploadRaggedPlan(const RaggedPlan &plan, uint32_t *dst_dev) { return UploadPlanWords(plan.words, dst_dev); }
     bool UploadPlanWords(const std::vector<uint32_t> &plan_words, uint32_t *dst_dev);
     bool CheckQueueError();
     bool Drain();
@@ -231,7 +247,6 @@ private:
     int trace_streams_ = 0;              // diagnostics builds (-DAECM_PIPE_TRACE) only
     int num_streams_ = 0;
     bool initialized_ = false;
-    int variant_ = kVariantFast;
     int fs_ = 0;
     hipStream_t stream_ = nullptr;
     StatePtrs st_{nullptr, nullptr, nullptr, nullptr};

@@ -23,17 +23,17 @@ enum KernelVariant : int {
 // Process n_blocks consecutive blocks of streams [0, n_streams) -- one wavefront per stream.
 // blocks_per_stream (device, may be null): stream s processes blocks_per_stream[s] <= n_blocks blocks
 // instead (batches whose streams have different amounts of audio pending).
-// rotation_stream_limit = RotationStreamLimit(CU count of the device the launch runs on): launches of at most that many
-// streams are fully resident from the start and take the kernel variants built for that occupancy.
+// phase_priority (fast variant): the kernel variants for launches of more streams than RotationStreamLimit(CU count of the device the
+// launch runs on); launches of at most that many are fully resident from the start and take the variants built for that occupancy.
 hipError_t LaunchProcessBlocks(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, int variant,
-                               int rotation_stream_limit, hipStream_t stream, const int32_t *blocks_per_stream = nullptr);
+                               bool phase_priority, hipStream_t stream, const int32_t *blocks_per_stream = nullptr);
 int RotationStreamLimit(int compute_units);
 
 // The chunk-queue form of the same launch (aecm_block_kernels.hip): items of chunk_blocks blocks claimed in order by a
 // grid that just fills the chip.  ctl: QueueControlBytes(n_streams) of device memory owned by the engine (cleared by the
 // launch); *err (device, never cleared by a launch) becomes non-zero if a wave gave up waiting for its predecessor.
 size_t QueueControlBytes(int n_streams);
-bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_blocks, int min_streams, bool ragged);
+bool QueueLaunchApplies(int n_streams, int n_blocks, int variant, int chunk_blocks, int min_streams);
 hipError_t LaunchProcessBlocksQueued(const StatePtrs &st, const IoView &io, int n_streams, int n_blocks, int chunk_blocks,
                                      int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
 int ResidentWaves(int compute_units);
