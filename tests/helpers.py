@@ -104,6 +104,74 @@ def adversarial_cases(n_cases=24, n_blocks=1000, seed=7):
                    echo_mode=int(rs.randint(0, 5)), path=path)
 
 
+N_CLEAN_KINDS = 10
+
+
+def hostile_clean(kind, far, near, rs):
+    """A hostile clean near-end input (nearendClean, reference aecm_core_c.cc:432-464) for a far / near pair: unlike a scaled
+    copy of the near end, its spectrum, its Q domain and its overlap block are its own.  rs: the caller's RandomState.
+    0 full-scale noise; 1 +-full-scale square; 2 a constant from {-32768, 32767, 1, -1, 0, 16384}; 3 sparse full-range spikes;
+    4 dither in -3..3; 5 noise whose level jumps per block among {0, 1, 40, 3000, 32767} / 32768 (the clean Q domain steps up
+    and down by its whole range from block to block); 6 a full-scale tone; 7 the near end itself; 8 clip(near * 4), louder
+    than the noisy signal and saturated; 9 all zero whatever the near end does."""
+    n = near.size
+    if kind == 0:
+        return rs.randint(-32768, 32768, size=n).astype(np.int16)
+    if kind == 1:
+        return np.where(rs.randint(0, 2, size=n) == 1, 32767, -32768).astype(np.int16)
+    if kind == 2:
+        return np.full(n, rs.choice([-32768, 32767, 1, -1, 0, 16384]), dtype=np.int16)
+    if kind == 3:
+        x = np.zeros(n, dtype=np.int16)
+        idx = rs.randint(0, n, size=n // 50)
+        x[idx] = rs.randint(-32768, 32768, size=idx.size)
+        return x
+    if kind == 4:
+        return rs.randint(-3, 4, size=n).astype(np.int16)
+    if kind == 5:
+        level = np.repeat(rs.choice([0, 1, 40, 3000, 32767], size=n // 64), 64).astype(np.int64)
+        return ((rs.randint(-32768, 32768, size=n).astype(np.int64) * level) >> 15).astype(np.int16)
+    if kind == 6:
+        return (32767 * np.sin(2 * np.pi * np.arange(n) * rs.randint(1, 60) / 128.0)).astype(np.int16)
+    if kind == 7:
+        return near.copy()
+    if kind == 8:
+        return np.clip(near.astype(np.int32) * 4, -32768, 32767).astype(np.int16)
+    if kind == 9:
+        return np.zeros(n, dtype=np.int16)
+    raise ValueError(kind)
+
+
+def adversarial_clean_cases(n_blocks):
+    """The full product of the ten hostile_clean kinds x {16000, 8000} Hz x two bases, 40 cases, rate-major (the 20 cases of a
+    rate are the streams of one batch).  Base A: a far / near pair of adversarial_cases with its configuration and echo path
+    (the rate is the product's, not the pair's).  Base B: a synth_pair "mixed" pair with a stream_config configuration -- the
+    canceller converges there, so adaptation, store / restore and the NLP are alive under the hostile clean input.
+    Yields dicts like adversarial_cases' plus clean, kind and base ("A" / "B")."""
+    hostile = list(adversarial_cases(n_cases=2 * N_CLEAN_KINDS, n_blocks=n_blocks))
+    for r, fs in enumerate((16000, 8000)):
+        for kind in range(N_CLEAN_KINDS):
+            for base in "AB":
+                k = 2 * kind + r
+                rs = np.random.RandomState(77000 + 4 * kind + 2 * r + (base == "B"))
+                if base == "A":
+                    c = dict(hostile[k], fs=fs)
+                else:
+                    far, near = synth_pair(3100 + k, n_blocks, fs, "mixed")
+                    cng, em = stream_config(k)
+                    c = dict(far=far, near=near, fs=fs, cng=cng, echo_mode=em, path=None)
+                yield dict(c, clean=hostile_clean(kind, c["far"], c["near"], rs), kind=kind, base=base)
+
+
+def process_clean(stream, far, near, clean, first=0, last=None):
+    """Blocks [first, last) of a case through a block-at-a-time checker (OracleStream / RefCoreStream) with a clean input."""
+    last = near.size // 64 if last is None else last
+    if last == first:
+        return np.zeros(0, np.int16)
+    return np.concatenate([stream.process_block_clean(far[b * 64:(b + 1) * 64], near[b * 64:(b + 1) * 64], clean[b * 64:(b + 1) * 64])
+                           for b in range(first, last)])
+
+
 def call_pattern(seed, n_calls, bursts=False):
     """A hostile but deterministic call pattern for session tests: msInSndCardBuf jitters around 40 ms with
     occasional out-of-range / large excursions, and now and then a call comes without a WebRtcAecm_BufferFarend

@@ -6,7 +6,7 @@ import hashlib
 import numpy as np
 import pytest
 
-from helpers import adversarial_cases, describe_digest_diff, golden_files
+from helpers import adversarial_cases, adversarial_clean_cases, describe_digest_diff, golden_files, process_clean
 from oracle import pyoracle
 from webrtc_aecm_amd.synth import PROFILES, synth_pair
 
@@ -170,3 +170,20 @@ def test_oracle_equals_reference_on_adversarial_inputs():
             r.init_echo_path(c["path"])
         assert np.array_equal(o.process(c["far"], c["near"]), r.process(c["far"], c["near"])), it
         assert np.array_equal(o.digest(), r.digest()), it
+
+
+@needs_ref
+def test_oracle_equals_reference_on_hostile_clean_inputs():
+    """The 40 hostile clean near-end inputs of helpers.adversarial_clean_cases, 1 100 blocks each (past CONV_LEN2 = 1 024: all
+    three start-up states): outputs block by block, and the state digests at blocks 192 and 1 100."""
+    for it, c in enumerate(adversarial_clean_cases(1100)):
+        o, r = pyoracle.OracleStream(c["fs"], c["cng"], c["echo_mode"]), pyoracle.RefCoreStream(c["fs"], c["cng"], c["echo_mode"])
+        if c["path"] is not None:
+            o.init_echo_path(c["path"])
+            r.init_echo_path(c["path"])
+        for first, last in ((0, 192), (192, 1100)):
+            a = process_clean(o, c["far"], c["near"], c["clean"], first, last)
+            b = process_clean(r, c["far"], c["near"], c["clean"], first, last)
+            bad = np.nonzero((a != b).reshape(-1, 64).any(axis=1))[0]
+            assert bad.size == 0, (it, c["kind"], c["base"], c["fs"], first + int(bad[0]))
+            assert np.array_equal(o.digest(), r.digest()), (it, c["kind"], c["base"], c["fs"], last, describe_digest_diff(o.digest(), r.digest()))

@@ -13,7 +13,7 @@ import pytest
 
 import pipe_clean_sim
 import webrtc_aecm_amd as aecm
-from helpers import stream_config
+from helpers import adversarial_clean_cases, describe_digest_diff, process_clean, stream_config
 from oracle import pyoracle
 from webrtc_aecm_amd import ffi
 from webrtc_aecm_amd.synth import synth_clean, synth_pair
@@ -163,3 +163,35 @@ def test_one_workgroup_with_a_clean_input_on_the_lane_simulator(deep, order, fs)
                 assert np.array_equal(out[k][(b - at) * 64:(b - at + 1) * 64], exp), (deep, order, fs, k, b)
             assert np.array_equal(digests[k], o.digest()), (deep, order, fs, k, at)
         at += n
+
+
+@pytest.mark.parametrize("fs", [16000, 8000])
+@pytest.mark.parametrize("order", [0, 1], ids=["consumers first", "producers first"])
+@pytest.mark.parametrize("deep", [True, False], ids=["sixteen-wave roles", "six-wave roles"])
+def test_hostile_clean_inputs_on_the_lane_simulator(deep, order, fs):
+    """The 20 cases of helpers.adversarial_clean_cases at this rate, four to a workgroup, through launches of 70 blocks with the
+    clean input, 9 without and 81 with it again: the clean spectrum shares the hand-over's words with the far and near
+    magnitudes (pack_clean_hand_over), so a clean input that is no scaled copy of the near end is what can tell a packing
+    error from a correct one.  Outputs block for block and 24-word digests after every launch equal OracleStream's.  (The
+    workgroup starts from the default echo path: a case's own path is not loaded here.)"""
+    lens = (70, 9, 81)
+    cases = [c for c in adversarial_clean_cases(sum(lens)) if c["fs"] == fs]
+    assert len(cases) == 20
+    for g in range(0, 20, 4):
+        grp = cases[g:g + 4]
+        cfgs = [(c["cng"], c["echo_mode"]) for c in grp]
+        far, near, clean = (np.stack([c[k] for c in grp]) for k in ("far", "near", "clean"))
+        wg = pipe_clean_sim.Workgroup(fs, cfgs)
+        oracles = [pyoracle.OracleStream(fs, *cfg) for cfg in cfgs]
+        at = 0
+        for n, with_clean in zip(lens, (True, False, True)):
+            sl = slice(at * 64, (at + n) * 64)
+            steps, out = wg.launch(far[:, sl], near[:, sl], clean[:, sl] if with_clean else None, deep, order)
+            assert steps == n + (4 if deep else 1)
+            digests = wg.digests()
+            for k, o in enumerate(oracles):
+                exp = process_clean(o, far[k], near[k], clean[k], at, at + n) if with_clean else o.process(far[k][sl], near[k][sl])
+                bad = np.nonzero((out[k] != exp).reshape(-1, 64).any(axis=1))[0]
+                assert bad.size == 0, (g + k, grp[k]["kind"], grp[k]["base"], at + int(bad[0]))
+                assert np.array_equal(digests[k], o.digest()), (g + k, grp[k]["kind"], grp[k]["base"], at, describe_digest_diff(digests[k], o.digest()))
+            at += n

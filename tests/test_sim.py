@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import simlib
-from helpers import adversarial_cases, describe_digest_diff, golden_files, run_burst_fixture
+from helpers import adversarial_cases, adversarial_clean_cases, describe_digest_diff, golden_files, process_clean, run_burst_fixture
 from oracle import pyoracle
 from webrtc_aecm_amd.synth import synth_clean, synth_pair
 
@@ -125,6 +125,24 @@ def test_wave_dsp_adversarial_inputs_and_echo_paths():
             s.init_echo_path(c["path"])
         assert np.array_equal(o.process(c["far"], c["near"]), s.process(c["far"], c["near"])), it
         assert np.array_equal(o.digest(), s.digest()), (it, describe_digest_diff(o.digest(), s.digest()))
+
+
+def test_wave_dsp_hostile_clean_inputs():
+    """The 40 hostile clean near-end inputs of helpers.adversarial_clean_cases through the kernel source on the lane simulator,
+    1 100 blocks each (all three start-up states): outputs block by block and the state digests at blocks 192 and 1 100 equal
+    the oracle's, and none of the checked preconditions may fire."""
+    for it, c in enumerate(adversarial_clean_cases(1100)):
+        o, s = pyoracle.OracleStream(c["fs"], c["cng"], c["echo_mode"]), simlib.SimStream(c["fs"], c["cng"], c["echo_mode"])
+        if c["path"] is not None:
+            o.init_echo_path(c["path"])
+            s.init_echo_path(c["path"])
+        for first, last in ((0, 192), (192, 1100)):
+            sl = slice(first * 64, last * 64)
+            exp = process_clean(o, c["far"], c["near"], c["clean"], first, last)
+            got = s.process(c["far"][sl], c["near"][sl], c["clean"][sl])
+            bad = np.nonzero((got != exp).reshape(-1, 64).any(axis=1))[0]
+            assert bad.size == 0, (it, c["kind"], c["base"], c["fs"], first + int(bad[0]))
+            assert np.array_equal(o.digest(), s.digest()), (it, c["kind"], c["base"], c["fs"], last, describe_digest_diff(o.digest(), s.digest()))
 
 
 def test_echo_path_import_export():

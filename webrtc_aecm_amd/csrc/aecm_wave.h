@@ -896,7 +896,11 @@ struct BlockEngine {
         const int dqq = sext16(clean_q - clean_q_old);
         if constexpr (kQSteady) {
             const I t_a = as_i16(sar(s.near_filt, neg(dqq)));                                 // dqq in [-14, 0]
-            const I t_b = sext16(dfa_clean);                                                  // the reference's (int16_t) of the uint16 magnitude
+            // the reference's (int16_t) of the uint16 magnitude.  No input makes it matter: a bin of the scaled forward transform of
+            // a real block is at most sum(w[n] * 32767) / 128 with the sqrt-Hanning window w (sum w = 81.5), i.e. 20 861 < 32 768, so the
+            // sign extension (here and at t_b of the general path) is the identity on every reachable magnitude and no parity test can
+            // tell it from its absence (profiles/r13_hostile_clean.txt, section 3).
+            const I t_b = sext16(dfa_clean);
             s.near_filt = as_i16(as_i16(sar(sub(t_b, t_a), 4)) + t_a);                        // between t_a and t_b: no narrowing can change it
             return;
         }
