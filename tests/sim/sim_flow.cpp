@@ -126,7 +126,7 @@ extern "C" {
 // detail[2] = ticks spent past the start-up phase, detail[3] = ticks in which the jitter buffer dropped far samples,
 // detail[4] = ticks whose blocks fetched the far end from the far ring directly, detail[5] = replay frames moved to rows,
 // detail[6] = far-end calls made outside ticks (bursts), detail[7] = samples of those the full jitter buffer dropped;
-// detail[0] = 100 + field: FlowStateDefect refused a state the session passed through.
+// detail[0] = 100 + field: FlowStateDefect refused the state a tick left, 200 + field: the state a far-end call outside ticks left.
 int64_t sim_flow_fuzz(uint64_t seed, int fs, int n_ticks, int scenario, uint32_t start_pos, int64_t *detail) {
     Rng rng{seed * 2654435761ull + 12345};
     DeviceSide dev;
@@ -139,6 +139,12 @@ int64_t sim_flow_fuzz(uint64_t seed, int fs, int n_ticks, int scenario, uint32_t
     int64_t far_offered = 0, near_offered = 0, ref_blocks = 0;
     int ms_walk = 40;
     for (int i = 0; i < 8; ++i) detail[i] = 0;
+    // every state a session passes through is one WebRtcAecmSessions_ImportSession accepts
+    const auto state_defect = [&dev]() -> int {
+        int32_t words[kFlowWords] = {0};
+        for (int k = 0; k < kFlowFieldsUsed; ++k) words[k] = dev.regs.v[k];
+        return FlowStateDefect(words);
+    };
     for (int64_t tick = 0; tick < n_ticks; ++tick) {
         int n = fs == 16000 ? 160 : 80, ms = 40, flags = 0;
         switch (scenario) {
@@ -187,6 +193,10 @@ int64_t sim_flow_fuzz(uint64_t seed, int fs, int n_ticks, int scenario, uint32_t
             dev.BufferFarend(fs, extra_len, extra, burst.data());
             for (int c = 0; c < extra; ++c) ref.BufferFarend(burst.data() + (size_t)c * extra_len, (size_t)extra_len);
             detail[6] += extra;
+            if (const int field = state_defect()) {
+                detail[0] = 200 + field;
+                return tick;
+            }
         }
         int64_t far_in[160], near_in[160], out_dev[160], out_ref[160];
         for (int j = 0; j < n; ++j) { far_in[j] = far_offered + j; near_in[j] = (int64_t(1) << 32) + near_offered + j; }
@@ -218,13 +228,9 @@ int64_t sim_flow_fuzz(uint64_t seed, int fs, int n_ticks, int scenario, uint32_t
         detail[5] = dev.spill_ticks;
         detail[7] = dev.burst_dropped;
         int what = 0;
-        {   // every state a session passes through is one WebRtcAecmSessions_ImportSession accepts
-            int32_t words[kFlowWords] = {0};
-            for (int k = 0; k < kFlowFieldsUsed; ++k) words[k] = dev.regs.v[k];
-            if (FlowStateDefect(words) != 0) {
-                detail[0] = 100 + FlowStateDefect(words);
-                return tick;
-            }
+        if (const int field = state_defect()) {
+            detail[0] = 100 + field;
+            return tick;
         }
         if (dfar.size() != rfar.size()) what = 1;
         else if (dfar != rfar) what = 2;

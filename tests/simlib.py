@@ -16,9 +16,9 @@ CSRC = ROOT / "webrtc_aecm_amd" / "csrc"
 SANITIZE = os.environ.get("AECM_SIM_SANITIZE") == "1"
 SIM_SO = ROOT / "tests" / "_build" / ("libaecm_sim_san.so" if SANITIZE else "libaecm_sim.so")
 SAN_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
-_SOURCES = [ROOT / "tests" / "sim" / "sim_lib.cpp", ROOT / "tests" / "sim" / "sim_engine.cpp", ROOT / "tests" / "sim" / "sim_flow.cpp",
-            CSRC / "aecm_host_state.cpp", CSRC / "aecm_session.cpp", CSRC / "aecm_schedule.cpp"]
-_DEPS = _SOURCES + [ROOT / "tests" / "sim" / "wave_sim.h", CSRC / "aecm_wave.h", CSRC / "aecm_ops.h",
+_SOURCES = [ROOT / "tests" / "sim" / "sim_lib.cpp", ROOT / "tests" / "sim" / "sim_roles.cpp", ROOT / "tests" / "sim" / "sim_engine.cpp",
+            ROOT / "tests" / "sim" / "sim_flow.cpp", CSRC / "aecm_host_state.cpp", CSRC / "aecm_session.cpp", CSRC / "aecm_schedule.cpp"]
+_DEPS = _SOURCES + [ROOT / "tests" / "sim" / "wave_sim.h", ROOT / "tests" / "sim" / "sim_stream.h", CSRC / "aecm_wave.h", CSRC / "aecm_ops.h",
                     CSRC / "aecm_state.h", CSRC / "aecm_host_state.h", CSRC / "aecm_tables.h",
                     CSRC / "aecm_session.h", CSRC / "aecm_engine.h", CSRC / "aecm_session_flow.h", CSRC / "aecm_flow_plan.h"]
 _i16p = np.ctypeslib.ndpointer(dtype=np.int16, flags="C_CONTIGUOUS")
@@ -30,7 +30,7 @@ def build():
     if SIM_SO.exists() and all(SIM_SO.stat().st_mtime >= d.stat().st_mtime for d in _DEPS):
         return
     SIM_SO.parent.mkdir(parents=True, exist_ok=True)
-    # one object per source, compiled in parallel (the block DSP template is instantiated in three of them; the sanitizer
+    # one object per source, compiled in parallel (the block DSP template is instantiated in four of them; the sanitizer
     # build of a single g++ call took more than two minutes)
     from concurrent.futures import ThreadPoolExecutor
     obj_dir = SIM_SO.parent / (".obj_san" if SANITIZE else ".obj")
@@ -62,7 +62,7 @@ def lib():
         l.sim_get_echo_path.argtypes = [C.c_void_p, _i16p]
         l.sim_process.argtypes = [C.c_void_p, _i16p, _i16p, C.c_void_p, _i16p, C.c_int]
         l.sim_digest.argtypes = [C.c_void_p, _u32p]
-        l.sim_process_roles.argtypes = [C.c_void_p, _i16p, _i16p, _i16p, C.c_int, C.c_int]
+        l.sim_roles_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.sim_fft128.argtypes = [_i16p, _i16p, C.c_int]
         l.sim_constants.argtypes = [_u32p, _u32p, _u32p]
         l.sim_recordings.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -113,12 +113,9 @@ class SimStream:
         return out
 
     def process_roles(self, far, near, order=0):
-        """The same blocks through the pipelined kernel's role decomposition (tests/sim/sim_lib.cpp: sim_process_roles)."""
+        """The same blocks through the pipelined kernel's role decomposition: a workgroup with this stream in slot 0 and nothing else."""
         far = np.ascontiguousarray(far, dtype=np.int16)
-        near = np.ascontiguousarray(near, dtype=np.int16)
-        out = np.empty_like(near)
-        self.lib.sim_process_roles(self.h, far, near, out, far.size // 64, order)
-        return out
+        return roles_launch([self], [far.size // 64], far[None], np.asarray(near)[None], None, True, order)[1][0]
 
     def digest(self):
         d = np.zeros(24, dtype=np.uint32)
@@ -138,6 +135,48 @@ class SimStream:
             self.lib.sim_free(self.h)
         except Exception:
             pass
+
+
+def roles_launch(streams, lens, far, near, clean=None, deep=True, order=0, sentinel=0x5A5A):
+    """One launch of one workgroup of the pipelined kernels' role split (tests/sim/sim_roles.cpp) -- the sixteen-wave role set
+    (deep) or the six-wave one.  streams: up to four SimStream (None = an empty slot), whose state the launch continues; lens:
+    blocks per slot; far / near / clean: [slots][samples], clean None = a launch without a clean input.  Returns (steps, out --
+    `sentinel` where nothing was written --, counts[4][3] = hand-over slots written, output blocks written, input rows loaded)."""
+    far = np.ascontiguousarray(far, dtype=np.int16)
+    near = np.ascontiguousarray(near, dtype=np.int16)
+    assert far.shape == near.shape and far.shape[0] <= 4 and far.shape[0] == len(streams)
+    handles = (C.c_void_p * 4)(*[s.h if s is not None else None for s in streams])         # (the slots behind the last one given: empty)
+    lens4 = np.zeros(4, dtype=np.int32)
+    lens4[:len(lens)] = lens
+    cptr = None
+    if clean is not None:
+        clean = np.ascontiguousarray(clean, dtype=np.int16)
+        assert clean.shape == near.shape
+        cptr = clean.ctypes.data
+    out = np.full_like(near, sentinel)
+    counts = np.zeros((4, 3), dtype=np.int64)
+    steps = lib().sim_roles_launch(handles, lens4.ctypes.data, 1 if deep else 0, order, far.shape[1], far.ctypes.data, near.ctypes.data, cptr,
+                                   out.ctypes.data, counts.ctypes.data)
+    assert steps >= 0, steps
+    return steps, out, counts
+
+
+class RoleWorkgroup:
+    """Four streams (configs: four (cng_mode, echo_mode) pairs) through launches of the role split; their state lives on from
+    launch to launch."""
+
+    def __init__(self, fs, configs):
+        assert len(configs) == 4
+        self.streams = [SimStream(fs, *c) for c in configs]
+
+    def launch(self, far, near, clean=None, deep=True, order=0, lens=None, sentinel=0x5A5A):
+        """lens None: every slot runs all of far's blocks.  Returns (steps, out); the launch's counters are in self.counts."""
+        steps, out, self.counts = roles_launch(self.streams, [np.shape(far)[1] // 64] * 4 if lens is None else lens, far, near, clean, deep, order,
+                                               sentinel)
+        return steps, out
+
+    def digests(self):
+        return np.stack([s.digest() for s in self.streams])
 
 
 class SimSession:

@@ -11,7 +11,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import pipe_clean_sim
+import simlib
 import webrtc_aecm_amd as aecm
 from helpers import adversarial_clean_cases, describe_digest_diff, process_clean, stream_config
 from oracle import pyoracle
@@ -148,7 +148,7 @@ def test_one_workgroup_with_a_clean_input_on_the_lane_simulator(deep, order, fs)
     pairs = [synth_pair(210 + k, T, fs) for k in range(4)]
     far, near = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
     clean = np.stack([_clean_of(near[k], k, far[k]) for k in range(4)])
-    wg = pipe_clean_sim.Workgroup(fs, cfgs)
+    wg = simlib.RoleWorkgroup(fs, cfgs)
     oracles = [pyoracle.OracleStream(fs, *cfg) for cfg in cfgs]
     at = 0
     for n, with_clean in zip(lens, (True, False, True)):
@@ -181,7 +181,7 @@ def test_hostile_clean_inputs_on_the_lane_simulator(deep, order, fs):
         grp = cases[g:g + 4]
         cfgs = [(c["cng"], c["echo_mode"]) for c in grp]
         far, near, clean = (np.stack([c[k] for c in grp]) for k in ("far", "near", "clean"))
-        wg = pipe_clean_sim.Workgroup(fs, cfgs)
+        wg = simlib.RoleWorkgroup(fs, cfgs)
         oracles = [pyoracle.OracleStream(fs, *cfg) for cfg in cfgs]
         at = 0
         for n, with_clean in zip(lens, (True, False, True)):
@@ -195,3 +195,35 @@ def test_hostile_clean_inputs_on_the_lane_simulator(deep, order, fs):
                 assert bad.size == 0, (g + k, grp[k]["kind"], grp[k]["base"], at + int(bad[0]))
                 assert np.array_equal(digests[k], o.digest()), (g + k, grp[k]["kind"], grp[k]["base"], at, describe_digest_diff(digests[k], o.digest()))
             at += n
+
+
+@pytest.mark.parametrize("fs", [16000, 8000])
+@pytest.mark.parametrize("order", [0, 1], ids=["consumers first", "producers first"])
+@pytest.mark.parametrize("deep", [True, False], ids=["sixteen-wave roles", "six-wave roles"])
+def test_four_lengths_with_a_clean_input_on_the_lane_simulator(deep, order, fs):
+    """Both conditions of the simulator's role split at once: four slots of lengths 0, 1, 23 and 57 AND a clean input (one that
+    is no scaled copy of the near end), in two launches that continue each other, the lengths dealt to other slots in the
+    second.  NO KERNEL HAS THIS FORM YET -- a ragged launch with a clean input is not pipelined -- so this pins down what such a
+    kernel's role split has to compute: outputs up to each stream's own length, the sentinel behind it, and 24-word digests
+    after each launch (c_old of a stream that ended before the workgroup did included) equal OracleStream.process_block_clean."""
+    L, sentinel = 57, 0x5A5A
+    cfgs = [stream_config(s) for s in (0, 3, 6, 9)]
+    pairs = [synth_pair(310 + k, 2 * L, fs) for k in range(4)]
+    far, near = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
+    clean = np.stack([_clean_of(near[k], 1, far[k]) for k in range(4)])
+    wg = simlib.RoleWorkgroup(fs, cfgs)
+    oracles = [pyoracle.OracleStream(fs, *cfg) for cfg in cfgs]
+    at = [0, 0, 0, 0]
+    for lens in ((0, 1, 23, 57), (57, 23, 0, 1)):
+        f, n, c = (np.stack([x[k][at[k] * 64:(at[k] + L) * 64] for k in range(4)]) for x in (far, near, clean))
+        steps, out = wg.launch(f, n, c, deep, order, lens, sentinel)
+        assert steps == max(lens) + (4 if deep else 1)
+        digests = wg.digests()
+        for k, o in enumerate(oracles):
+            for b in range(lens[k]):
+                blk = slice(b * 64, (b + 1) * 64)
+                assert np.array_equal(out[k][blk], o.process_block_clean(f[k][blk], n[k][blk], c[k][blk])), (lens, k, b)
+            assert (out[k][lens[k] * 64:] == sentinel).all(), (lens, k)
+            assert np.array_equal(digests[k], o.digest()), (lens, k, describe_digest_diff(digests[k], o.digest()))
+            assert wg.counts[k].tolist() == [lens[k]] * 3, (lens, k, wg.counts[k])
+            at[k] += lens[k]

@@ -9,7 +9,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
-import ragged_pipe_sim
+import simlib
 import webrtc_aecm_amd as aecm
 from oracle import pyoracle
 from webrtc_aecm_amd import ffi
@@ -202,7 +202,9 @@ def test_one_workgroup_of_four_lengths_on_the_lane_simulator(deep, fs):
     far, near = np.stack([p[0] for p in pairs]), np.stack([p[1] for p in pairs])
     for lens in ([57, 0, 1, 23], [1, 57, 23, 0], [23, 1, 0, 57], [0, 0, 5, 0]):
         for order in (0, 1):
-            steps, out, digests, counts = ragged_pipe_sim.workgroup(far, near, lens, fs, 1, 3, deep, order, sentinel)
+            wg = simlib.RoleWorkgroup(fs, [(1, 3)] * 4)
+            steps, out = wg.launch(far, near, None, deep, order, lens, sentinel)
+            digests, counts = wg.digests(), wg.counts
             assert steps == max(lens) + (4 if deep else 1)
             for k, n in enumerate(lens):
                 o = pyoracle.OracleStream(fs, 1, 3)

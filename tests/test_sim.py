@@ -30,7 +30,7 @@ def test_wave_dsp_equals_oracle(fs):
 def test_role_decomposition_of_the_pipelined_kernel_equals_oracle(order):
     """The pipelined kernel's deepest shape splits a block over five roles with registers and state of their own -- front,
     delay, channel, gain, tail -- one step apart (aecm_block_kernels.hip).  The same split on the lane simulator
-    (sim_process_roles: the same BlockEngine functions, state ownership, slot rings and far-history rules), launches of 1 .. 5 and
+    (tests/sim/sim_roles.cpp: the same BlockEngine functions, state ownership, slot rings and far-history rules), launches of 1 .. 5 and
     several hundred blocks, alternating with the plain engine, fixed delays included: outputs and the complete state against the
     oracle after every launch.  order 0 / 1: consumers first / producers first inside a step -- a role reading what the same step
     writes would make the two differ."""
@@ -348,7 +348,8 @@ def test_device_session_machinery_equals_the_generic_wrapper_on_sample_tags(fs):
     a saturated jitter buffer (16 kHz in 80-sample calls), mixed 80 / 160 / 2 x 80 call shapes, a replay frame that
     outlives its place in the far ring, far-end bursts (k = 0..3 and 30 / 60 / 255 WebRtcAecm_BufferFarend calls between
     two WebRtcAecm_Process calls, overflowing the jitter buffer), and position counters that wrap around 2^32 and 2^31
-    during the run.  Every state passed through must also be one ImportSession's validator accepts."""
+    during the run.  Every state passed through -- after a tick and after far-end calls between ticks -- must also be one
+    ImportSession's validator accepts."""
     assert simlib.lib().sim_flow_tolerance_check() == 0
     saw_blocks = saw_drops = saw_direct = saw_framed = saw_spills = saw_bursts = saw_burst_drops = 0
     for scenario in list(range(11)) + [12, 13, 14]:

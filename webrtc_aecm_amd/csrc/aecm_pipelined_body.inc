@@ -125,6 +125,7 @@
                     E::spectrum(r, fa1, fb1, q1, df);
                 } else {
                     const PipeSlot &slot_in = sh.slots[slot_idx][slot];
+                    // (restates E::unpack_hand_over: through the call the audit build's back waves are scheduled differently)
                     const int x = slot_in.near_x[lane], m = slot_in.mags[lane], sc = slot_in.scalars[lane];
                     xf.mag = zext16(m);
                     xf.mag64 = __builtin_amdgcn_readlane(sc, 0);
@@ -175,6 +176,7 @@
             if (live) {
                 const int lane = W::lane_id();
                 const PipeGainState &g = sh.gain_state[slot];
+                // (restates E::unpack_gain_state: through the call the sixteen-wave kernels are scheduled differently)
                 const int nf = g.near_filt_ctrs[lane];
                 r.b.echo_filt = g.echo_filt[lane];
                 r.b.near_filt = sext16(nf); r.b.low_ctr = lsr(nf, 16) & 7; r.b.high_ctr = lsr(nf, 19) & 7;
@@ -286,6 +288,8 @@
                     } else {
                         typename EF::Spectrum xf, df, cf;
                         EF::front_block(r, x_old[k], far_cur, d_old[k], near_cur, 0, 0, xf, df, cf);
+                        // (restates EF::pack_hand_over, store by store: through the call the stores come after all three words are
+                        // formed, and the compiler then schedules the front waves' loop differently)
                         PipeSlot &slot = sh.slots[slot_idx][ks(k)];
                         slot.near_x[lane] = (df.re & 0xffff) | (int)((unsigned)df.im << 16);
                         slot.mags[lane] = xf.mag | (int)((unsigned)df.mag << 16);
@@ -495,13 +499,8 @@
                         EF::unpack_clean_hand_over({slot.clean_x[lane], slot.mags[lane], slot.clean_mag[lane], slot.scalars[lane]}, xf, df, cf);
                     } else {
                         const PipeSlot &slot = sh.slots[slot_idx][k];
-                        const int x = slot.near_x[lane], m = slot.mags[lane], sc = slot.scalars[lane];
-                        df.re = sext16(x);
-                        df.im = sar(x, 16);
-                        df.mag = lsr(m, 16);
-                        df.re64 = __builtin_amdgcn_readlane(sc, 2);
-                        df.mag64 = __builtin_amdgcn_readlane(sc, 3);
-                        df.q = __builtin_amdgcn_readlane(sc, 4);
+                        typename EF::Spectrum xf;                         // (of the far end this wave reads nothing)
+                        EF::unpack_hand_over({slot.near_x[lane], slot.mags[lane], slot.scalars[lane]}, xf, df);
                     }
                     const PipeGainSlot &gs = sh.gains[blk & 1][k];
                     typename EF::GainInput g;
@@ -524,7 +523,7 @@
             }
             if (live) {                                                   // this wave's part of the state -> the channel wave (which stores the state)
                 const int lane = W::lane_id();
-                PipeGainState &g = sh.gain_state[k];
+                PipeGainState &g = sh.gain_state[k];                      // (restates EF::pack_gain_state, store by store, for the same reason as the front waves' pack)
                 g.echo_filt[lane] = r.b.echo_filt;
                 g.near_filt_ctrs[lane] = zext16(r.b.near_filt) | shl(r.b.low_ctr & 7, 16) | shl(r.b.high_ctr & 7, 19);
                 g.noise_est[lane] = r.b.noise_est;

@@ -1297,6 +1297,59 @@ struct BlockEngine {
         cf.q = W::readlane(h.scalars, 7);
     }
 
+    // The same hand-over without a clean input (PipeSlot, and the simulator's copy): of the far end mag / mag64 / q, of the near end
+    // everything.  near_x: near re | im << 16; mags as above; scalars: lanes 0, 1: far mag64, q; 2, 3, 4: near re64, mag64, q.
+    struct HandOver {
+        vi near_x, mags, scalars;
+    };
+    static AECM_HD HandOver pack_hand_over(const Spectrum &xf, const Spectrum &df) {
+        HandOver h;
+        h.near_x = (df.re & 0xffff) | shl(df.im, 16);
+        h.mags = xf.mag | shl(df.mag, 16);
+        vi sc = vi(0);
+        sc = W::writelane(sc, xf.mag64, 0);
+        sc = W::writelane(sc, xf.q, 1);
+        sc = W::writelane(sc, df.re64, 2);
+        sc = W::writelane(sc, df.mag64, 3);
+        sc = W::writelane(sc, df.q, 4);
+        h.scalars = sc;
+        return h;
+    }
+    static AECM_HD void unpack_hand_over(const HandOver &h, Spectrum &xf, Spectrum &df) {
+        xf.mag = zext16(h.mags);
+        xf.mag64 = W::readlane(h.scalars, 0);
+        xf.q = W::readlane(h.scalars, 1);
+        xf.re = xf.im = vi(0); xf.re64 = 0;
+        df.re = sext16(h.near_x);
+        df.im = sar(h.near_x, 16);
+        df.mag = lsr(h.mags, 16);
+        df.re64 = W::readlane(h.scalars, 2);
+        df.mag64 = W::readlane(h.scalars, 3);
+        df.q = W::readlane(h.scalars, 4);
+    }
+    // The gain role's part of a stream's state on its way to the channel role, which stores the state at the end of a launch
+    // (PipeGainState): near_filt_ctrs is near_filt | low_ctr << 16 | high_ctr << 19, the V_NEARFILT layout.
+    struct GainState {
+        vi echo_filt, near_filt_ctrs, noise_est;
+        int scal[9];          // seed, sup_gain, sup_gain_old, noise_ctr; bin 64: echo_filt, near_filt, noise_est, low_ctr, high_ctr
+    };
+    static AECM_HD GainState pack_gain_state(const Regs &r) {
+        GainState g;
+        g.echo_filt = r.b.echo_filt;
+        g.near_filt_ctrs = zext16(r.b.near_filt) | shl(r.b.low_ctr & 7, 16) | shl(r.b.high_ctr & 7, 19);
+        g.noise_est = r.b.noise_est;
+        g.scal[0] = r.u.seed; g.scal[1] = r.u.sup_gain; g.scal[2] = r.u.sup_gain_old; g.scal[3] = r.u.noise_ctr;
+        g.scal[4] = r.b64.echo_filt; g.scal[5] = r.b64.near_filt; g.scal[6] = r.b64.noise_est; g.scal[7] = r.b64.low_ctr; g.scal[8] = r.b64.high_ctr;
+        return g;
+    }
+    static AECM_HD void unpack_gain_state(const GainState &g, Regs &r) {
+        r.b.echo_filt = g.echo_filt;
+        r.b.near_filt = sext16(g.near_filt_ctrs); r.b.low_ctr = lsr(g.near_filt_ctrs, 16) & 7; r.b.high_ctr = lsr(g.near_filt_ctrs, 19) & 7;
+        r.b.noise_est = g.noise_est;
+        r.u.seed = g.scal[0]; r.u.sup_gain = g.scal[1]; r.u.sup_gain_old = g.scal[2]; r.u.noise_ctr = g.scal[3];
+        r.b64.echo_filt = g.scal[4]; r.b64.near_filt = g.scal[5]; r.b64.noise_est = g.scal[6]; r.b64.low_ctr = g.scal[7]; r.b64.high_ctr = g.scal[8];
+    }
+
     static AECM_HD vi process_block(Regs &r, uint16_t *hist, vi far_new, vi near_new, vi clean_new) {
         update_startup(r.u);
         if (W::kLaneConstsInTable) r.table_index = W::table_index_for_this_block();
