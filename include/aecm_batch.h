@@ -313,8 +313,9 @@ int32_t WebRtcAecmBatch_SetLaunchChunking(AecmBatch *b, int32_t chunk_blocks, in
 int32_t WebRtcAecmBatch_SetLaunchPipelining(AecmBatch *b, int32_t min_streams);
 /* Ragged launches (WebRtcAecmBatch_ProcessBlocksRagged, WebRtcAecmBatch_ProcessRecordingsRagged) that the chip holds at once, pipelined:
  * enable != 0 and such a launch takes the pipelined form above instead of one wavefront per stream when the fast variant is selected,
- * there is no clean near-end input (WebRtcAecmBatch_SetCleanPipelining does not extend to ragged launches: the two switches do not
- * combine yet), the streams that have blocks to run (not the batch's size: 100 live streams of 65 536 qualify) are
+ * there is no clean near-end input (a ragged launch with one is pipelined by a switch of its own,
+ * WebRtcAecmBatch_SetRaggedCleanPipelining, and by nothing else), the streams that have blocks to run (not the batch's size: 100 live
+ * streams of 65 536 qualify) are
  * within [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks.  All lengths equal
  * stays the equal-length launch, and the chunk queue keeps what it takes today.  A workgroup still marches its (up to) four streams in
  * lock step -- every wavefront executes as many barriers as the workgroup's longest stream has blocks -- and a slot whose stream has
@@ -335,12 +336,28 @@ int32_t WebRtcAecmBatch_SetRaggedPipelining(AecmBatch *b, int32_t enable);
  * wavefronts become two; pipe_delay_waves 4 with pipe_gain_waves 0 gives twelve wavefronts, 0x802) -- never a launch error.
  * DescribeLaunch reports these launches with the shape bits + 0x2000.  ProcessRecordings* with a clean input run their blocks
  * through the same launch rule.  Ragged launches with a clean input stay as they are (one wavefront per stream, or the chunk
- * queue), whatever this switch and WebRtcAecmBatch_SetRaggedPipelining say: the two do not combine yet; a ragged call whose lengths
- * are all equal IS the equal-length launch.  out_dev may alias near_clean_dev as for every other form (no input row is read after
+ * queue), whatever this switch and WebRtcAecmBatch_SetRaggedPipelining say: their pipelined form has a switch of its own,
+ * WebRtcAecmBatch_SetRaggedCleanPipelining; a ragged call whose lengths are all equal IS the equal-length launch.  out_dev may
+ * alias near_clean_dev as for every other form (no input row is read after
  * an output row of the same launch has been written).  Per batch; OFF by default, for the reason given above: with it off every
  * launch takes exactly the form it took before the switch existed.  Static checks, and the sweep to run: profiles/r11_clean_pipelined.txt.
  * Results never depend on it.  AECM_BAD_PARAMETER_ERROR for a NULL batch. */
 int32_t WebRtcAecmBatch_SetCleanPipelining(AecmBatch *b, int32_t enable);
+/* Ragged launches WITH a clean near-end input that the chip holds at once, pipelined: enable != 0 and such a launch
+ * (WebRtcAecmBatch_ProcessBlocksRagged, WebRtcAecmBatch_ProcessRecordingsRagged* with a clean input) takes the pipelined form instead of
+ * one wavefront per stream when the fast variant is selected, the chunk queue does not take it, the streams that have blocks to run
+ * are within [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks -- the rule of
+ * WebRtcAecmBatch_SetRaggedPipelining, by the same host-made plan (WebRtcAecmBatch_RaggedPipePlan's placement), in the shapes of
+ * WebRtcAecmBatch_SetCleanPipelining (0x1a02 / 0x002 / 0x000, 0x802 by wish; pipe_* wishes land on the nearest of these, never a
+ * launch error), reported with the shape bits + 0x2000.  A switch of its own because the other two keep their meaning: with this one
+ * off a ragged launch with a clean input takes exactly the form and kernel it took before this switch existed, whatever the other two say,
+ * and this one changes no launch without a clean input and no equal-length launch (all lengths equal IS the equal-length launch, under
+ * WebRtcAecmBatch_SetCleanPipelining's rule).  A stream that ends before its workgroup does leaves its state exactly as after its own
+ * last block; blocks at and beyond a stream's length are neither read nor written, and out_dev may alias near_clean_dev.
+ * Per batch; OFF by default, for the reason given above, although it measured 1.16 to 2.24 times the one-wavefront-per-stream launch at
+ * 256 ... 4 096 streams (profiles/r15_ragged_clean_pipelined.txt, with the static checks).
+ * Results never depend on it.  AECM_BAD_PARAMETER_ERROR for a NULL batch. */
+int32_t WebRtcAecmBatch_SetRaggedCleanPipelining(AecmBatch *b, int32_t enable);
 /* Which form a ProcessBlocks launch of num_blocks blocks over the whole batch takes, with (has_clean_input != 0) or
  * without a clean near-end input (for measurement tools that must name
  * the kernel they time): 0 = one wavefront per stream, kernel variants for launches the chip holds at once; 1 = one
@@ -432,9 +449,18 @@ int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int
 int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
                                                const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
                                                AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks);
+/* WebRtcAecmBatch_DescribeRaggedLaunchEx with the batch's opt-in for ragged launches with a clean input
+ * (WebRtcAecmBatch_SetRaggedCleanPipelining) as one more argument.  ragged_clean_pipelining = 0: exactly that call's answer.  Otherwise
+ * a launch with a clean input that the rule of SetRaggedCleanPipelining takes is described as form 3, shape bits + 0x2000, with the
+ * plan's workgroups and cu_load_evenness_x1000 as above; launches without a clean input are described as before. */
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx2(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                                const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
+                                                int32_t ragged_clean_pipelining, AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks,
+                                                int32_t *max_blocks);
 /* The same for the launch WebRtcAecmBatch_ProcessBlocksRagged would make on THIS batch (blocks_per_stream_host: its num_streams
  * entries): under its launch policy, its kernel variant (a batch on the safe variant is never pipelined) and its
- * WebRtcAecmBatch_SetRaggedPipelining switch -- what the engine itself decides by.  -1 for a NULL batch. */
+ * WebRtcAecmBatch_SetRaggedPipelining and WebRtcAecmBatch_SetRaggedCleanPipelining switches -- what the engine itself decides by.
+ * -1 for a NULL batch. */
 int32_t WebRtcAecmBatch_DescribeRaggedLaunchOf(const AecmBatch *b, const int32_t *blocks_per_stream_host, int32_t has_clean_input,
                                                AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks);
 /* Diagnostics: the plan a ragged pipelined launch runs by, whether or not the launch rule would pick the form.  slot_stream[4 x

@@ -32,6 +32,12 @@ does the interleaving itself, the same way: one child process per library, $AECM
 repetitions inside them is printed next to it, and (c) is called faster than (a) only when their ranges do not overlap.
 
     python tools/bench_ragged.py --pipelined --parent webrtc_aecm_amd/_lib/ab_parent.so [--sizes ...] [--blocks 2048] [--reps 4] [--passes 2]
+
+--pipelined --clean: the same sweep for ragged launches WITH a clean near-end input (WebRtcAecmBatch_SetRaggedCleanPipelining).
+(a), (b) and (c) run the ragged launch with a clean input -- the parent's library, this build with the new switch off, this build
+with it on -- and (d) is this build's ragged launch of the same lengths WITHOUT a clean input with WebRtcAecmBatch_SetRaggedPipelining on:
+what the third transform and the wider hand-over cost.  (b) runs in a child of its own that does exactly what (a)'s child does -- the
+one launch, back to back -- so that the two columns differ in the library alone; (c) and (d) alternate in a third child.
 """
 from __future__ import annotations
 
@@ -103,7 +109,7 @@ def point(S, T, dist, reps, fs):
     batch.close()
 
 
-def pipelined_point(S, T, reps, fs, with_switch):
+def pipelined_point(S, T, reps, fs, with_switch, clean=False, column="parent"):
     """One child: both distributions at one size on the library $AECM_LIB_PATH names (or the shipped one)."""
     import torch
 
@@ -113,13 +119,28 @@ def pipelined_point(S, T, reps, fs, with_switch):
     far, near = synth_on_device(torch, S, T * 64, 1234, device)
     out = torch.empty_like(near)
     ptrs = (far.data_ptr(), near.data_ptr(), out.data_ptr(), far.shape[1], 64)
+    # (--clean) the clean input: 3/4 of the near end, as webrtc_aecm_amd.synth.synth_clean makes it
+    clean_ptr = None
+    if clean:
+        near_clean = ((near.to(torch.int32) * 3) >> 2).to(torch.int16)
+        clean_ptr = near_clean.data_ptr()
+        torch.cuda.synchronize()
     for dist in ("uniform", "one_long"):
         lens = lengths(dist, S, T)
         total = int(lens.sum())
         t_equal = max(1, total // S)
         batch = aecm.AecmBatch(S, fs, cng_mode=1, echo_mode=1, device=0)
         runs = {}
-        if with_switch:
+        if with_switch and clean:
+            def on():
+                batch.set_ragged_clean_pipelining(True)
+                batch.process_ragged_device(*ptrs, T, lens, clean_ptr)
+
+            def equal():                                  # column (d) of the clean sweep: the same lengths without a clean input, pipelined
+                batch.set_ragged_pipelining(True)
+                batch.process_ragged_device(*ptrs, T, lens)
+            runs = {"on": on, "equal": equal}
+        elif with_switch:
             def on():
                 batch.set_ragged_pipelining(True)
                 batch.process_ragged_device(*ptrs, T, lens)
@@ -129,7 +150,7 @@ def pipelined_point(S, T, reps, fs, with_switch):
                 batch.process_ragged_device(*ptrs, T, lens)
             runs = {"off": off, "on": on, "equal": lambda: batch.process_device(*ptrs, t_equal)}
         else:
-            runs = {"parent": lambda: batch.process_ragged_device(*ptrs, T, lens)}
+            runs = {column: lambda: batch.process_ragged_device(*ptrs, T, lens, clean_ptr)}      # (the switches at their defaults: off)
         wall = {k: [] for k in runs}
         for run in runs.values():
             run()
@@ -140,11 +161,14 @@ def pipelined_point(S, T, reps, fs, with_switch):
                 run()
                 batch.synchronize()
                 wall[name].append(time.perf_counter() - t0)
-        useful = {k: (S * t_equal if k == "equal" else total) for k in runs}
+        useful = {k: (S * t_equal if k == "equal" and not clean else total) for k in runs}
         rec = {"streams": S, "blocks": T, "dist": dist, "sum_blocks": total, "frames_per_s": {k: [useful[k] / t for t in wall[k]] for k in runs}}
         if with_switch:
-            batch.set_ragged_pipelining(True)
-            d = batch.describe_ragged_launch(lens)
+            if clean:
+                batch.set_ragged_clean_pipelining(True)
+            else:
+                batch.set_ragged_pipelining(True)
+            d = batch.describe_ragged_launch(lens, clean)
             rec.update(form_on=d["form"], shape_on=d["shape"], workgroups_on=d["workgroups"], evenness_on=d["cu_load_evenness_x1000"])
         print("RESULT " + json.dumps(rec), flush=True)
         batch.close()
@@ -157,11 +181,14 @@ def pipelined_main(a):
     acc = {}
     for p in range(a.passes):
         for S in sizes:
-            for variant in (("parent", "new") if a.parent else ("new",)):
+            # (--clean: column (b) from a child shaped like (a)'s, on this build)
+            for variant in (("parent",) if a.parent else ()) + (("off", "new") if a.clean else ("new",)):
                 env = dict(os.environ)
                 if variant == "parent":
                     env["AECM_LIB_PATH"] = str(Path(a.parent).resolve())
                 cmd = [sys.executable, str(Path(__file__).resolve()), "--pipelined-point", str(S), variant, "--blocks", str(T), "--reps", str(a.reps), "--fs", str(a.fs)]
+                if a.clean:
+                    cmd.append("--clean")
                 try:
                     r = subprocess.run(cmd, capture_output=True, text=True, timeout=a.timeout, env=env)
                 except subprocess.TimeoutExpired:
@@ -178,7 +205,9 @@ def pipelined_main(a):
                         slot["f"].setdefault(k, []).extend(v)
                     slot.update({k: rec[k] for k in ("form_on", "shape_on", "workgroups_on", "evenness_on") if k in rec})
     print(f"T = {T} blocks, {a.passes} interleaved passes x {a.reps} repetitions; M useful frames/s, min .. max over all of them")
-    print(f"{'streams':>7} {'dist':>8} {'(a) parent':>17} {'(b) off':>17} {'(c) on':>17} {'(d) equal':>17}  form/shape/wgs/evenness  verdict")
+    if a.clean:
+        print("every column but (d) with a clean near-end input; (d): the same lengths without one, SetRaggedPipelining on")
+    print(f"{'streams':>7} {'dist':>8} {'(a) parent':>17} {'(b) off':>17} {'(c) on':>17} {'(d) no clean' if a.clean else '(d) equal':>17}  form/shape/wgs/evenness  verdict")
     for (S, dist), slot in sorted(acc.items()):
         f = slot["f"]
         cell = lambda k: f"{min(f[k]) / 1e6:7.1f} ..{max(f[k]) / 1e6:7.1f}" if k in f else f"{'-':>17}"
@@ -201,11 +230,12 @@ def main():
     ap.add_argument("--point", nargs=2, metavar=("STREAMS", "DIST"), help="(internal) run one point in this process")
     ap.add_argument("--pipelined", action="store_true", help="the sweep of the ragged pipelined form (see the module text)")
     ap.add_argument("--parent", help="--pipelined: a library built from the parent commit, for column (a)")
+    ap.add_argument("--clean", action="store_true", help="--pipelined: the sweep with a clean near-end input and WebRtcAecmBatch_SetRaggedCleanPipelining")
     ap.add_argument("--passes", type=int, default=2, help="--pipelined: interleaved passes over the libraries")
     ap.add_argument("--pipelined-point", nargs=2, metavar=("STREAMS", "VARIANT"), help="(internal) one size on one library in this process")
     a = ap.parse_args()
     if a.pipelined_point:
-        pipelined_point(int(a.pipelined_point[0]), a.blocks, a.reps, a.fs, a.pipelined_point[1] == "new")
+        pipelined_point(int(a.pipelined_point[0]), a.blocks, a.reps, a.fs, a.pipelined_point[1] == "new", a.clean, a.pipelined_point[1])
         return 0
     if a.pipelined:
         return pipelined_main(a)

@@ -48,6 +48,11 @@ SESSJIT_CASES = [
 RAGGED_CASES = [
     ("ragged_16k", 48, 200, 16000, 7000),
 ]
+# The same with a clean near-end input (WebRtcAecm_ProcessBlock's nearendClean): the clean rows are
+# tests/test_gpu_pipelined_clean.py: _clean_of of the batch's far / near rows (even streams synth_clean, odd ones a quieter mix)
+RAGGED_CLEAN_CASES = [
+    ("ragged_clean_16k", 48, 200, 16000, 7100),
+]
 SESSBURST_CASES = [
     (15, 3, 16000, 160),
     (16, 3, 8000, 80),
@@ -146,6 +151,26 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", fs=fs, n_blocks=nb, lens=lens, seeds=seeds, cng=np.array([c[0] for c in cfgs]),
                             echo_mode=np.array([c[1] for c in cfgs]), sha256=np.array(hashes), digests=np.stack(digs))
         print("ragged", name, S, nb, fs, int(lens.sum()), "blocks")
+    for name, S, nb, fs, seed0 in RAGGED_CLEAN_CASES:
+        if only and only not in name:
+            continue
+        from helpers import process_clean, synth_streams
+        from test_gpu_pipelined_clean import _clean_of
+        lens = np.random.RandomState(seed0).randint(0, nb + 1, size=S).astype(np.int32)
+        lens[:3] = (0, nb, 1)
+        seeds = np.arange(seed0, seed0 + S)
+        cfgs = [stream_config(s) for s in range(S)]
+        far, near = synth_streams(seeds.tolist(), nb, fs)
+        clean = _clean_of(far, near)
+        hashes, digs = [], []
+        for s in range(S):
+            r = pyoracle.RefCoreStream(fs, *cfgs[s])
+            out = process_clean(r, far[s], near[s], clean[s], 0, int(lens[s]))
+            hashes.append(hashlib.sha256(out.tobytes()).hexdigest())
+            digs.append(r.digest())
+        np.savez_compressed(GOLD / f"{name}.npz", fs=fs, n_blocks=nb, lens=lens, seeds=seeds, cng=np.array([c[0] for c in cfgs]),
+                            echo_mode=np.array([c[1] for c in cfgs]), sha256=np.array(hashes), digests=np.stack(digs))
+        print("ragged clean", name, S, nb, fs, int(lens.sum()), "blocks")
     if only:
         return
     # 60 s reference-CLI-shaped run: hash only

@@ -459,6 +459,16 @@ void aecm_process_pipelined_clean_kernel(StatePtrs st, IoView io, int streams_ba
     constexpr bool kRagged = false, kClean = true;
 #include "aecm_pipelined_body.inc"
 }
+// Ragged launches with a clean input (opt-in per batch, a switch of its own): both of the above at once -- the plan's slots and
+// lengths, the three-signal block.  The shapes that are both ragged and clean shapes: keys 20, 220, 4220, 42240.
+template <int kTail, bool kBalance, bool kRaw = false, int kFront = 2, int kDelay = 0, int kGain = 0>
+__global__ __launch_bounds__(64 * PipeWaves(kTail, kFront, kDelay, kGain))
+__attribute__((amdgpu_waves_per_eu(PipeWavesPerEu(kGain), AECM_MAX_WAVES_PER_EU)))
+void aecm_process_pipelined_ragged_clean_kernel(StatePtrs st, IoView io, int streams_base, int streams_rem, int n_blocks, uint32_t *progress, int n_workgroups,
+                                                 int wgs_per_round, int rot, int prio) {
+    constexpr bool kRagged = true, kClean = true;
+#include "aecm_pipelined_body.inc"
+}
 #undef AECM_PIPE_BARRIER
 
 // Streams a pipelined launch keeps resident at once: workgroups per CU by wave slots (4 SIMDs x 7) and by LDS (160 KB).
@@ -624,7 +634,8 @@ hipError_t LaunchProcessBlocksPipelined(const StatePtrs &st, const IoView &io, i
 
 // The ragged pipelined launch: plan_dev = RaggedPipePlanWords(n_workgroups, n_streams) words the caller has uploaded on `stream` --
 // slot_stream[n_workgroups][4] (-1 = empty slot), then len[n_streams].  The unbalanced shapes only; a shape that asks for the
-// balance is an error here (BuildRaggedPipePlan never makes one).
+// balance is an error here (BuildRaggedPipePlan never makes one).  With a clean input (io.near_clean): the clean shapes only
+// (PipelinedCleanShapeFor's), in aecm_process_pipelined_ragged_clean_kernel.
 size_t RaggedPipePlanWords(int n_workgroups, int n_streams) { return (size_t)n_workgroups * kPipeStreams + (size_t)n_streams; }
 hipError_t LaunchProcessBlocksPipelinedRagged(const StatePtrs &st, const IoView &io, int n_streams, const PipeShape &shape, int n_workgroups,
                                               const uint32_t *plan_dev, hipStream_t stream) {
@@ -635,7 +646,16 @@ hipError_t LaunchProcessBlocksPipelinedRagged(const StatePtrs &st, const IoView 
 #define AECM_LAUNCH_PIPE(T, R, F, D, G) hipLaunchKernelGGL((aecm_process_pipelined_ragged_kernel<T, false, R, F, D, G>), grid, block, sizeof(LdsTables) + sizeof(PipeShared<T, R, D, G>), \
                                                            stream, st, io, n_streams, 0, 0, plan, (int)grid.x, shape.wgs_per_round, shape.rot, shape.prio)
     const int key = shape.gain_waves * 10000 + shape.delay_waves * 1000 + shape.tail_waves * 100 + shape.front_waves * 10 + (shape.raw ? 1 : 0);
-    if (key == 20) AECM_LAUNCH_PIPE(0, false, 2, 0, 0);
+#define AECM_LAUNCH_PIPE_CLEAN(T, F, D, G) hipLaunchKernelGGL((aecm_process_pipelined_ragged_clean_kernel<T, false, false, F, D, G>), grid, block,       \
+                                                              sizeof(LdsTables) + sizeof(PipeShared<T, false, D, G, true>), stream, st, io, n_streams, 0, \
+                                                              0, plan, (int)grid.x, shape.wgs_per_round, shape.rot, shape.prio)
+    if (io.near_clean != nullptr) {
+        if (key == 20) AECM_LAUNCH_PIPE_CLEAN(0, 2, 0, 0);
+        else if (key == 220) AECM_LAUNCH_PIPE_CLEAN(2, 2, 0, 0);
+        else if (key == 4220) AECM_LAUNCH_PIPE_CLEAN(2, 2, 4, 0);
+        else if (key == 42240) AECM_LAUNCH_PIPE_CLEAN(2, 4, 2, 4);
+        else return hipErrorInvalidValue;
+    } else if (key == 20) AECM_LAUNCH_PIPE(0, false, 2, 0, 0);
     else if (key == 220) AECM_LAUNCH_PIPE(2, false, 2, 0, 0);
     else if (key == 221) AECM_LAUNCH_PIPE(2, true, 2, 0, 0);
     else if (key == 241) AECM_LAUNCH_PIPE(2, true, 4, 0, 0);
@@ -643,6 +663,7 @@ hipError_t LaunchProcessBlocksPipelinedRagged(const StatePtrs &st, const IoView 
     else if (key == 42240) AECM_LAUNCH_PIPE(2, false, 4, 2, 4);
     else return hipErrorInvalidValue;
 #undef AECM_LAUNCH_PIPE
+#undef AECM_LAUNCH_PIPE_CLEAN
     return hipGetLastError();
 }
 

@@ -367,6 +367,12 @@ int32_t WebRtcAecmBatch_SetCleanPipelining(AecmBatch *b, int32_t enable) {
     return 0;
 }
 
+int32_t WebRtcAecmBatch_SetRaggedCleanPipelining(AecmBatch *b, int32_t enable) {
+    if (!b) return AECM_BAD_PARAMETER_ERROR;
+    b->engine->set_ragged_clean_pipelining(enable != 0);
+    return 0;
+}
+
 int32_t WebRtcAecmBatch_DescribeLaunch(const AecmBatch *b, int32_t num_blocks, int32_t has_clean_input, int32_t *chunk_blocks) {
     if (!b) return -1;
     return b->engine->DescribeLaunch(num_blocks, has_clean_input != 0, chunk_blocks);
@@ -485,18 +491,26 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, i
     return 0;
 }
 
-int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
-                                               const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
-                                               AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx2(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                                const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
+                                                int32_t ragged_clean_pipelining, AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks,
+                                                int32_t *max_blocks) {
     if (!out || !blocks_per_stream_host) return AECM_NULL_POINTER_ERROR;
     if (num_streams <= 0) return AECM_BAD_PARAMETER_ERROR;
     aecm::LaunchPolicy p;
     int32_t longest = 0;
     if (const int32_t rc = ResolvePolicy(policy, compute_units, &p)) return rc;
     if (const int32_t rc = LongestLength(blocks_per_stream_host, num_streams, &longest)) return rc;
-    const aecm::LaunchSwitches sw{aecm::kVariantFast, ragged_pipelining != 0, false};
+    const aecm::LaunchSwitches sw{aecm::kVariantFast, ragged_pipelining != 0, false, ragged_clean_pipelining != 0};
     const aecm::LaunchPlan plan = aecm::PlanRaggedLaunch(p, sw, num_streams, longest, blocks_per_stream_host, has_clean_input != 0);
     return RaggedDescriptionToAbi(aecm::DescribePlan(p, plan), plan, out, items, sum_blocks, max_blocks);
+}
+
+int32_t WebRtcAecmBatch_DescribeRaggedLaunchEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,
+                                               const int32_t *blocks_per_stream_host, int32_t has_clean_input, int32_t ragged_pipelining,
+                                               AecmLaunchDescription *out, int64_t *items, int64_t *sum_blocks, int32_t *max_blocks) {
+    return WebRtcAecmBatch_DescribeRaggedLaunchEx2(policy, compute_units, num_streams, blocks_per_stream_host, has_clean_input, ragged_pipelining, 0, out,
+                                                   items, sum_blocks, max_blocks);
 }
 
 int32_t WebRtcAecmBatch_DescribeRaggedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams,

@@ -249,7 +249,9 @@ bool BatchEngine::EnsureLaunchControl(size_t need) {
 //                 dispatched first pull ahead, and with items claimed in order those waves simply take more of the work (4 608 streams
 //                 728 -> 830 M frames/s, 6 144: 844 -> 930 M; profiles/r04_experiments.md section 4).  Shorter chunks there: a quarter.
 //   pipelined     launches the chip holds at once: fast variant, every stream the same number of blocks, and no clean input unless the
-//                 batch has opted in (set_clean_pipelining: aecm_process_pipelined_clean_kernel)
+//                 batch has opted in (set_clean_pipelining: aecm_process_pipelined_clean_kernel); ragged launches by the live streams
+//                 and the longest length, on a batch that has opted in (set_ragged_pipelining without a clean input,
+//                 set_ragged_clean_pipelining with one: aecm_process_pipelined_ragged_clean_kernel)
 //   else          one wavefront per stream: by phase priority (form 1) when the launch is more waves than the rotation kernels are built for
 namespace {
 int QueueMinStreams(const LaunchPolicy &p) { return p.queue_min_streams >= 0 ? p.queue_min_streams : p.pipelined_max_streams; }
@@ -267,7 +269,7 @@ int PipeShapeBits(const PipeShape &sh) {
     return sh.tail_waves | (sh.balance ? 0x100 : 0) | (sh.front_waves == 4 ? 0x200 : 0) | (sh.raw ? 0x400 : 0) | (sh.delay_waves ? 0x800 : 0) |
            (sh.gain_waves ? 0x1000 : 0);
 }
-constexpr int kPipeShapeCleanBit = 0x2000;        // the launch runs aecm_process_pipelined_clean_kernel
+constexpr int kPipeShapeCleanBit = 0x2000;        // the launch runs aecm_process_pipelined_clean_kernel (ragged: _ragged_clean_kernel)
 int RoundsX1000(int workgroups, int cus, int workgroups_per_cu) { return (int)((int64_t)1000 * workgroups / ((int64_t)cus * std::max(1, workgroups_per_cu))); }
 // The control buffer a ragged plan needs: the pipelined form's plan alone, else the queue's control words with the plan behind them.
 size_t RaggedControlBytes(const LaunchPlan &plan) {
@@ -466,8 +468,10 @@ LaunchPlan PlanRaggedLaunch(const LaunchPolicy &p, const LaunchSwitches &sw, int
             plan.chunk_blocks = chunk;
         } else if (longest > 0) {
             plan.form = WavePerStreamForm(p, sw.variant, count);
-            if (sw.ragged_pipelining && PipelinedLaunchApplies(p, sw.variant, live, longest, has_clean, false)) {
-                plan.shape = RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe);
+            // (a clean input: by a switch of its own, in the clean shapes -- the other two switches leave such a launch as it is)
+            const bool opted_in = has_clean ? sw.ragged_clean_pipelining : sw.ragged_pipelining;
+            if (opted_in && PipelinedLaunchApplies(p, sw.variant, live, longest, has_clean, has_clean)) {
+                plan.shape = has_clean ? PipelinedCleanShapeFor(live, longest, p.compute_units, p.pipe) : RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe);
                 if (BuildRaggedPipePlan(lens, count, plan.shape, p.compute_units, &plan.pipe)) plan.form = 3;
             }
         }

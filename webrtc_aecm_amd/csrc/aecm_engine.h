@@ -67,7 +67,7 @@ struct RaggedPlan {
 };
 // false: a length outside [0, num_blocks] (the plan is then not usable).
 bool BuildRaggedPlan(const int32_t *blocks_per_stream, int num_streams, int num_blocks, int chunk_blocks, RaggedPlan *plan);
-// The plan of a ragged PIPELINED launch (aecm_process_pipelined_ragged_kernel): which stream sits in which of the four slots
+// The plan of a ragged PIPELINED launch (aecm_process_pipelined_ragged_kernel, _ragged_clean_kernel): which stream sits in which of the four slots
 // of which workgroup.  Pure host logic.  Workgroups i, i + cus, ... share a compute unit (the dispatcher deals them out in turn);
 // a stream stays on its unit for the whole launch, so the launch ends when the unit with the most blocks does.  The live streams
 // (len > 0), longest first, each go to the unit with the fewest blocks so far that still has a free slot (longest processing time
@@ -99,6 +99,7 @@ struct LaunchSwitches {
     int variant = kVariantFast;
     bool ragged_pipelining = false;   // BatchEngine::set_ragged_pipelining: ragged launches the chip holds at once are pipelined
     bool clean_pipelining = false;    // BatchEngine::set_clean_pipelining: equal-length launches WITH a clean input are pipelined too
+    bool ragged_clean_pipelining = false;      // BatchEngine::set_ragged_clean_pipelining: ragged launches WITH a clean input are pipelined too
 };
 // Everything one launch of the block kernels runs by.  PlanLaunch and PlanRaggedLaunch (pure host logic) are the only places that
 // decide it; BatchEngine launches a plan as it stands and DescribePlan reports it, so what is reported is what runs.
@@ -118,8 +119,9 @@ struct LaunchPlan {
 LaunchPlan PlanLaunch(const LaunchPolicy &policy, const LaunchSwitches &sw, int num_streams, int num_blocks, bool has_clean);
 // A ragged launch.  Every length equal: exactly PlanLaunch of that length.  Otherwise the chunk queue when the fast variant is
 // selected, more than queue_min_streams streams are live, the longest stream has at least two chunks and the items fit 31 bits;
-// else -- only with sw.ragged_pipelining -- pipelined when the fast variant is selected, there is no clean input, the LIVE streams
-// are within [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks; else one
+// else -- only with sw.ragged_pipelining, or with a clean input only with sw.ragged_clean_pipelining (then in the shapes of
+// PipelinedCleanShapeFor) -- pipelined when the fast variant is selected, the LIVE streams are within
+// [pipelined_min_streams, pipelined_max_streams] and the longest has at least pipelined_min_blocks blocks; else one
 // wavefront per stream, each with its own block count.
 LaunchPlan PlanRaggedLaunch(const LaunchPolicy &policy, const LaunchSwitches &sw, int num_streams, int num_blocks, const int32_t *blocks_per_stream,
                             bool has_clean);
@@ -170,9 +172,13 @@ public:
     void set_ragged_pipelining(bool on) { switches_.ragged_pipelining = on; }
     bool ragged_pipelining() const { return switches_.ragged_pipelining; }
     // Equal-length launches with a clean near-end input that the chip holds at once take the pipelined form (PlanLaunch's rule).
-    // Off by default.  Ragged launches with a clean input are not pipelined by either switch.
+    // Off by default.  Ragged launches with a clean input are not pipelined by either switch (set_ragged_clean_pipelining, below).
     void set_clean_pipelining(bool on) { switches_.clean_pipelining = on; }
     bool clean_pipelining() const { return switches_.clean_pipelining; }
+    // Ragged launches with a clean near-end input that the chip holds at once take the pipelined form (PlanRaggedLaunch's rule).
+    // Off by default; with it off the other two switches leave such a launch exactly as it is.
+    void set_ragged_clean_pipelining(bool on) { switches_.ragged_clean_pipelining = on; }
+    bool ragged_clean_pipelining() const { return switches_.ragged_clean_pipelining; }
     // Whole recordings as sessions: every stream is driven like a fresh WebRtcAecm_* session by
     // n_calls x (BufferFarend, Process) of `frame` samples with a constant msInSndCardBuf
     // (aecm_session_flow.h).  far/near/clean/out: [S][>= n_calls*frame], device (or host) pointers; clean

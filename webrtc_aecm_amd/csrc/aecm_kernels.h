@@ -91,7 +91,9 @@ hipError_t LaunchProcessBlocksPipelined(const StatePtrs &st, const IoView &io, i
 // The same form for streams of different lengths (aecm_process_pipelined_ragged_kernel: the unbalanced shapes): plan_dev =
 // RaggedPipePlanWords(n_workgroups, n_streams) words uploaded ahead of the launch on the same stream -- slot_stream[n_workgroups][4]
 // (the stream of each of a workgroup's four slots, -1 = empty), then len[n_streams] (aecm_engine.h: RaggedPipePlan).  A slot whose
-// stream has ended keeps the workgroup's barriers and does nothing else; a stream of length 0 has no slot.
+// stream has ended keeps the workgroup's barriers and does nothing else; a stream of length 0 has no slot.  With a clean input
+// (io.near_clean): aecm_process_pipelined_ragged_clean_kernel, in the shapes PipelinedCleanShapeFor gives; any other shape is
+// hipErrorInvalidValue.
 size_t RaggedPipePlanWords(int n_workgroups, int n_streams);
 hipError_t LaunchProcessBlocksPipelinedRagged(const StatePtrs &st, const IoView &io, int n_streams, const PipeShape &shape, int n_workgroups,
                                               const uint32_t *plan_dev, hipStream_t stream);

@@ -1,6 +1,6 @@
 // The text of the pipelined kernels' body (aecm_block_kernels.hip includes it into aecm_process_pipelined_kernel,
-// aecm_process_pipelined_ragged_kernel and aecm_process_pipelined_clean_kernel, behind `constexpr bool kRagged, kClean`; not a
-// header: no guard, no declarations of its own).
+// aecm_process_pipelined_ragged_kernel, aecm_process_pipelined_clean_kernel and aecm_process_pipelined_ragged_clean_kernel, behind
+// `constexpr bool kRagged, kClean`; not a header: no guard, no declarations of its own).
 // In scope: the template arguments kTail, kBalance, kRaw, kFront, kDelay, kGain and the kernel arguments st, io, streams_base,
 // streams_rem, n_blocks, progress, n_workgroups, wgs_per_round, rot, prio.
     constexpr int kFrontBehind = kBalance ? kPipeFrontPrioBehind : AECM_PIPE_FRONT_PRIO;
@@ -16,7 +16,7 @@
     static_assert(kDelay == 0 || (kPipeStreams % kDelay == 0 && !kRaw), "delay waves: in the shapes with formed spectra");
     static_assert(kGain == 0 || (kGain == kPipeStreams && kDelay != 0), "gain waves: one per stream, with delay waves");
     static_assert(!kRagged || !kBalance, "ragged launches: the unbalanced shapes (the balance's slowest-workgroup rule assumes equal work)");
-    static_assert(!kClean || (!kRaw && !kBalance && !kRagged), "clean launches: formed spectra, no balance, equal lengths");
+    static_assert(!kClean || (!kRaw && !kBalance), "clean launches: formed spectra, no balance");
     constexpr int kWaves = PipeWaves(kTail, kFront, kDelay, kGain), kPipeFrontWaves = kFront, kPipeStreamsPerFront = kPipeStreams / kFront;
     constexpr int kLagD = kDelay ? 1 : 0, kLagG = kGain ? 1 : 0;           // steps the delay / gain waves put between the front waves and the rest
     constexpr int kSlots = 2 + kLagD + kLagG;
@@ -31,7 +31,9 @@
     // launches pass the near-end one twice.  c_old, the clean input's last block, shares V_OUTBUF's word with the overlap buffer: the
     // front wave loads its half at the start, and leaves the launch's last clean block in sh.c_last in its last (otherwise empty)
     // step -- before a barrier every wave executes -- for the wave that stores that word.  No input row is read again at the end:
-    // out may alias an input.
+    // out may alias an input.  Ragged and clean together: c_prev, like x_old and d_old, only advances while blk < the slot's own
+    // length, so what a stream that ended before its workgroup did leaves in sh.c_last is the clean block at ITS last block; the
+    // barriers per wave are those of the ragged form (n_blocks = the workgroup's longest slot in every role).
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // This workgroup's streams (PipeSplit, below): streams_base of them, one more in the first streams_rem workgroups -- the
     // dispatcher deals workgroups out to the CUs in turn, so the CUs' loads differ by at most one stream.  A workgroup with fewer
@@ -261,8 +263,8 @@
                     int clean_cur = 0;
                     if constexpr (kClean) {
                         clean_cur = clean_next[k];
-                        if (blk + 1 < n_blocks) {
-                            typename EF::StridedIo sio{io, slot_stream(ks(k)) * io.stream_stride};
+                        if (blk + 1 < (kRagged ? len[k] : n_blocks)) {            // (as the far and near rows above)
+                            typename EF::StridedIo sio{io, (kRagged ? strm[k] : slot_stream(ks(k))) * io.stream_stride};
                             clean_next[k] = sio.clean(r, blk + 1);
                         }
                     }

@@ -50,6 +50,7 @@ BATCH_SYMBOLS = [
     "WebRtcAecmBatch_SetRaggedPipelining", "WebRtcAecmBatch_DescribeRaggedLaunchEx", "WebRtcAecmBatch_RaggedPipePlan",
     "WebRtcAecmBatch_DescribeRaggedLaunchOf",
     "WebRtcAecmBatch_SetCleanPipelining", "WebRtcAecmBatch_DescribeLaunchDetailEx",
+    "WebRtcAecmBatch_SetRaggedCleanPipelining", "WebRtcAecmBatch_DescribeRaggedLaunchEx2",
 ]
 SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_Create", "WebRtcAecmSessions_Free", "WebRtcAecmSessions_Init", "WebRtcAecmSessions_set_config",
@@ -156,6 +157,11 @@ def load():
         lib.WebRtcAecmBatch_SetCleanPipelining.argtypes = [vp, C.c_int32]
         lib.WebRtcAecmBatch_DescribeLaunchDetailEx.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                                C.POINTER(AecmLaunchDescription)]
+    if hasattr(lib, "WebRtcAecmBatch_SetRaggedCleanPipelining"):      # (as above)
+        lib.WebRtcAecmBatch_SetRaggedCleanPipelining.argtypes = [vp, C.c_int32]
+        lib.WebRtcAecmBatch_DescribeRaggedLaunchEx2.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
+                                                                C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                                C.POINTER(C.c_int32)]
     lib.WebRtcAecmBatch_Synchronize.argtypes = [vp]
     lib.WebRtcAecmBatch_GetLastLaunchMs.argtypes = [vp, C.POINTER(C.c_float)]
     lib.WebRtcAecmBatch_GetTimers.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -334,6 +340,11 @@ class AecmBatch:
         (include/aecm_batch.h: WebRtcAecmBatch_SetCleanPipelining; results never depend on it).  Off by default."""
         self._check(self.lib.WebRtcAecmBatch_SetCleanPipelining(self.h, 1 if enable else 0), "SetCleanPipelining")
 
+    def set_ragged_clean_pipelining(self, enable=True):
+        """Ragged launches with a clean near-end input that the chip holds at once take the pipelined form
+        (include/aecm_batch.h: WebRtcAecmBatch_SetRaggedCleanPipelining; results never depend on it).  Off by default."""
+        self._check(self.lib.WebRtcAecmBatch_SetRaggedCleanPipelining(self.h, 1 if enable else 0), "SetRaggedCleanPipelining")
+
     def launch_policy(self) -> AecmLaunchPolicy:
         p = AecmLaunchPolicy()
         self._check(self.lib.WebRtcAecmBatch_GetLaunchPolicy(self.h, C.byref(p)), "WebRtcAecmBatch_GetLaunchPolicy")
@@ -467,7 +478,7 @@ class AecmBatch:
 
     def describe_ragged_launch(self, blocks_per_stream, clean=False) -> dict:
         """describe_ragged_launch (module level) as the engine decides it for this batch: under its launch policy, its kernel
-        variant and its set_ragged_pipelining switch."""
+        variant and its set_ragged_pipelining and set_ragged_clean_pipelining switches."""
         lens = self._lengths(blocks_per_stream)
         d = AecmLaunchDescription()
         items, total, longest = C.c_int64(0), C.c_int64(0), C.c_int32(0)
@@ -805,15 +816,22 @@ def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int
     return d.as_dict()
 
 
-def describe_ragged_launch(blocks_per_stream, compute_units: int = 0, clean: bool = False, policy=None, ragged_pipelining: bool = False) -> dict:
+def describe_ragged_launch(blocks_per_stream, compute_units: int = 0, clean: bool = False, policy=None, ragged_pipelining: bool = False,
+                           ragged_clean_pipelining: bool = False) -> dict:
     """describe_launch_detail for a ragged launch (one block count per stream), without a device: the AecmLaunchDescription
     fields plus items (the chunk queue's (chunk, stream) items; 0 for the other forms), sum_blocks (the useful work) and
-    max_blocks (the critical path).  ragged_pipelining: the answer for a batch that has opted in (AecmBatch.set_ragged_pipelining)."""
+    max_blocks (the critical path).  ragged_pipelining / ragged_clean_pipelining: the answer for a batch that has opted in
+    (AecmBatch.set_ragged_pipelining / set_ragged_clean_pipelining)."""
     lens = np.ascontiguousarray(blocks_per_stream, dtype=np.int32)
     d = AecmLaunchDescription()
     items, total, longest = C.c_int64(0), C.c_int64(0), C.c_int32(0)
     pol = C.byref(policy) if policy is not None else None
-    if ragged_pipelining:
+    if ragged_clean_pipelining:
+        name = "WebRtcAecmBatch_DescribeRaggedLaunchEx2"
+        rc = load().WebRtcAecmBatch_DescribeRaggedLaunchEx2(pol, compute_units, lens.size, lens.ctypes.data, 1 if clean else 0,
+                                                            1 if ragged_pipelining else 0, 1, C.byref(d), C.byref(items), C.byref(total),
+                                                            C.byref(longest))
+    elif ragged_pipelining:
         name = "WebRtcAecmBatch_DescribeRaggedLaunchEx"
         rc = load().WebRtcAecmBatch_DescribeRaggedLaunchEx(pol, compute_units, lens.size, lens.ctypes.data, 1 if clean else 0, 1, C.byref(d),
                                                            C.byref(items), C.byref(total), C.byref(longest))
