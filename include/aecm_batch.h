@@ -196,7 +196,24 @@ enum {
      * in this tick (first half, then second half of its rows) instead of one pair of 160 samples -- sessions with
      * different call sizes in one object (the reference treats the two cadences differently,
      * echo_control_mobile.cc:282-283, 384-385).  codes_host then receives the first non-zero code of the two calls. */
-    AECM_SESSION_SPLIT_CALLS = 2
+    AECM_SESSION_SPLIT_CALLS = 2,
+    /* This session makes NEITHER call in this tick: its reference instance receives no WebRtcAecm_BufferFarend and no
+     * WebRtcAecm_Process in the interval (the call has ended, the slot was never used, the near-end packet is late, the call
+     * is on hold).  Nothing of its state changes, what it has pending stays pending, and when it calls again it continues bit
+     * for bit -- however long the stretch.  The other bits of its flag byte are ignored; its far, near, near_clean,
+     * msInSndCardBuf_host and out entries are not read; codes_host[s] is 0 and takes no part in the "first non-zero code".
+     * The device-pointer forms (TickFlags, TickAsync) never write an idle session's out row; TickFlagsHost, which stages
+     * whole planes, copies every session's input rows to the device (the kernels read the live ones only; no rows at all in a
+     * tick nobody makes) and delivers an idle session's out row as zeros.  The tick's device work is by the
+     * sessions that call: a planning launch over all sessions, and a tick launch of ceil(live / 4) workgroups
+     * (WebRtcAecmSessions_DescribeTickLive).  A tick in which every session is idle launches nothing and returns 0 (the
+     * arguments are checked as always, the object's position advances, done_hip_event is recorded behind wait_hip_event).
+     * far may be NULL when every session is idle or carries AECM_SESSION_NO_FAREND.
+     * A tick whose flags name nobody idle gives what the tick without a flags array gives, and in an object whose sessions
+     * are all in step -- nobody has sat out a tick since the last tick everybody made -- it is that tick: the same launches,
+     * the same kernels.  The first tick everybody makes after idle ticks still takes the planning launch that brings sessions
+     * back in step (then the dense tick kernel); from the next one on the object is as if nobody had ever idled. */
+    AECM_SESSION_IDLE = 4
 };
 int32_t WebRtcAecmSessions_TickFlags(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev,
                                      const int16_t *near_clean_dev, int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples,
@@ -235,6 +252,9 @@ int32_t WebRtcAecmSessions_TickAsync(AecmSessions *s, const int16_t *far_dev, co
  * NULL.  With the two, k = 0, 1, 2, ... far calls per near call and session are expressed as: BufferFarend with
  * calls_host[s] = k_s, then Process.  The Tick* forms remain the one-launch shape of the common k = 1 (TickFlags: k in
  * {0, 1} per session); in TickFlags / TickAsync far may be NULL when every session carries AECM_SESSION_NO_FAREND.
+ * "The far end arrived, the near end is late" is the same pair with AECM_SESSION_IDLE: BufferFarend with calls_host[s] = 1 for those
+ * sessions (0 for the others), AECM_SESSION_IDLE for them in the tick, and their WebRtcAecm_Process when the near end is there
+ * (a later tick with AECM_SESSION_NO_FAREND, or Process).
  * BufferFarend (device pointers) and BufferFarendAsync are enqueued on the object's stream like ticks; BufferFarend and
  * BufferFarendHost wait for it, BufferFarendAsync does not (events as in TickAsync; the far rows must stay untouched
  * until the launch has run). */
@@ -253,6 +273,9 @@ int32_t WebRtcAecmSessions_Synchronize(AecmSessions *s);
 /* AECM_KERNEL_FAST (default) / AECM_KERNEL_SAFE for the object's block engine.  The tick kernel is built on the fast
  * primitives only: with the safe variant selected, ticks return AECM_UNSUPPORTED_FUNCTION_ERROR (and change nothing). */
 int32_t WebRtcAecmSessions_SetKernelVariant(AecmSessions *s, int32_t variant);
+/* Diagnostics (tools/bench_sessions.py --occupancy): on != 0 sends every tick through the live list and the sparse tick kernel,
+ * idle sessions or not, so that the cost of the indirection itself can be measured.  Results do not change. */
+int32_t WebRtcAecmSessions_ForceSparseTicks(AecmSessions *s, int32_t on);
 
 /* Zero-copy host audio.  A caller-owned host buffer is pinned and mapped into the device's address space once
  * (hipHostRegister); *device_alias is then a device pointer that every *_dev argument of this header accepts
@@ -477,6 +500,10 @@ int32_t WebRtcAecmBatch_RaggedPipePlan(const AecmLaunchPolicy *policy, int32_t c
 int32_t WebRtcAecmBatch_RaggedPlan(int32_t num_streams, const int32_t *blocks_per_stream_host, int32_t chunk_blocks, int32_t *order,
                                    int32_t *first_item, int32_t first_item_capacity, int32_t *num_chunks);
 int32_t WebRtcAecmSessions_DescribeTick(int32_t num_sessions, int32_t compute_units, AecmLaunchDescription *out);
+/* The same for a tick of an object of num_sessions sessions in which live_sessions call and the others carry AECM_SESSION_IDLE:
+ * the tick launch's grid and rounds_x1000 are by the live count (0 workgroups when nobody calls); live_sessions == num_sessions
+ * answers exactly as DescribeTick.  AECM_BAD_PARAMETER_ERROR for live_sessions outside [0, num_sessions]. */
+int32_t WebRtcAecmSessions_DescribeTickLive(int32_t num_sessions, int32_t live_sessions, int32_t compute_units, AecmLaunchDescription *out);
 /* The HIP device WebRtcAecm_Create (which has no device argument) puts its sessions on from now on; process-wide, default 0. */
 int32_t WebRtcAecm_SetDefaultDevice(int32_t device_id);
 

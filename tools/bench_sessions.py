@@ -12,6 +12,12 @@ Where the audio lives (--audio):
                    overlap on three HIP streams, ordered by events only (WebRtcAecmSessions_TickAsync's wait / done hooks;
                    reference call shape: main.cc:112-145 -- far and near frames in, one output frame out per 10 ms)
 A tick moves 2 x n x 2 bytes in and n x 2 bytes out per session (n = 160 at 16 kHz): 63 MB per tick of 65 536 sessions.
+
+--occupancy P[,P...]: sparse ticks (AECM_SESSION_IDLE).  For each P a fixed, seeded random set of ceil(P x S) sessions is live and
+the others sit out every tick; device-resident audio, WebRtcAecmSessions_TickAsync with per-session msInSndCardBuf and flags,
+ticks enqueued back to back.  Printed next to the dense tick of the same object size (the same call without a flags array,
+--repeats times: its spread is the yardstick for every difference).  P = 1.0 is a tick forced through the live list and the
+sparse tick kernel with nobody idle (WebRtcAecmSessions_ForceSparseTicks): what the indirection itself costs.
 """
 import argparse
 import json
@@ -34,7 +40,11 @@ def main():
     ap.add_argument("--pinned", action="store_true", help="= --audio host-registered")
     ap.add_argument("--async", dest="asynchronous", action="store_true",
                     help="WebRtcAecmSessions_TickAsync: ticks are enqueued back to back, one synchronisation at the end (host-staged always is)")
+    ap.add_argument("--occupancy", default="", help="P[,P...]: share of the sessions that is live; the others are idle every tick (see above)")
+    ap.add_argument("--repeats", type=int, default=3, help="--occupancy: measurements per column (the median is reported, all are listed)")
     args = ap.parse_args()
+    if args.occupancy:
+        return occupancy_sweep(args)
     if args.host:
         args.audio = "host"
     if args.pinned:
@@ -127,6 +137,61 @@ def main():
                       "ms_per_tick": dt * 1e3, "frames_per_s": S * blocks_per_tick / dt, "realtime_streams_per_gpu": int(S * 0.010 / dt),
                       "MB_over_the_boundary_per_tick": boundary_bytes / 1e6, "GBps_over_the_boundary": boundary_bytes / dt / 1e9,
                       "tick_workgroup_rounds": desc["rounds_x1000"] / 1000.0}))
+
+
+def occupancy_sweep(args):
+    import math
+
+    import numpy as np
+    import torch
+
+    import webrtc_aecm_amd as aecm
+    S, fs = args.streams, args.fs
+    n = fs // 100
+    g = torch.Generator(device="cuda").manual_seed(1)
+    far = (torch.randn((S, n * 8), generator=g, device="cuda") * 3000).clamp_(-32768, 32767).to(torch.int16)
+    near = (far.roll(37, dims=1) // 3 + (torch.randn((S, n * 8), generator=g, device="cuda") * 200).to(torch.int16))
+    out = torch.empty_like(far)
+    ms = np.full(S, 40, dtype=np.int16)
+    cus = aecm.device_info(0)[1]
+
+    def measure(flags, force_sparse):
+        """ms per tick, args.repeats times, on a fresh object that has left its start-up phase under the same flags."""
+        sess = aecm.AecmSessions(S, fs, 1, 1)
+        if force_sparse:
+            assert sess.force_sparse_ticks(True) == 0
+
+        def tick(i):
+            off = (i % 8) * n * 2
+            rc = sess.tick_async(far.data_ptr() + off, near.data_ptr() + off, out.data_ptr(), far.shape[1], n, 40, ms_per_session=ms, flags=flags)
+            assert rc == 0, rc
+        for i in range(40):
+            tick(i)
+        times = []
+        for r in range(args.repeats):
+            assert sess.synchronize() == 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.ticks):
+                tick(40 + i)
+            assert sess.synchronize() == 0
+            times.append((time.perf_counter() - t0) / args.ticks * 1e3)
+        sess.close()
+        return times
+
+    dense = measure(None, False)
+    rows = []
+    for p in [float(x) for x in args.occupancy.split(",")]:
+        live = min(S, math.ceil(p * S))
+        flags = np.full(S, aecm.ffi.SESSION_IDLE, dtype=np.uint8)
+        flags[np.random.default_rng(7).permutation(S)[:live]] = 0
+        times = measure(flags, force_sparse=live == S)
+        rows.append({"occupancy": p, "live": live, "ms_per_tick": float(np.median(times)), "all_ms_per_tick": times,
+                     "tick_workgroup_rounds": aecm.describe_tick_live(S, live, cus)["rounds_x1000"] / 1000.0,
+                     "forced_sparse": live == S})
+    print(json.dumps({"streams": S, "fs": fs, "audio": "device", "async": True, "ticks": args.ticks,
+                      "dense_ms_per_tick": float(np.median(dense)), "dense_all_ms_per_tick": dense,
+                      "dense_tick_workgroup_rounds": aecm.describe_tick(S, cus)["rounds_x1000"] / 1000.0, "sparse": rows}))
 
 
 if __name__ == "__main__":

@@ -133,6 +133,19 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, n_calls=n_calls, fs=fs, frame=frame, ms_seq=ms_seq, far_calls=far_calls, out=out,
                             codes=codes, paths=np.stack(r.event_log), sha256=hashlib.sha256(out.tobytes()).hexdigest())
         print("sessburst", seed, fs, frame, sorted(set(codes.tolist())), int(far_calls.sum()), "far calls for", n_calls, "near calls")
+    # Sparse session ticks (AECM_SESSION_IDLE; tests/sparse_helpers.py: golden_pattern): every session on a reference instance
+    # of its own that in an idle tick is not called.  Arrays only: the recipe's seeds, the flags and msInSndCardBuf of every
+    # tick, the outputs (an idle tick: zeros), the codes and the final echo paths.
+    import sparse_helpers
+    for name, (fs, frame, seed) in sparse_helpers.GOLDEN_CASES.items():
+        if only and only not in name:
+            continue
+        flags, ms = sparse_helpers.golden_pattern(fs, frame, seed)
+        T, S = flags.shape
+        far, near, _ = sparse_helpers.signals(seed, S, T * frame, fs)
+        out, codes, paths = sparse_helpers.drive_reference(lambda: pyoracle.RefSession(fs, 1, 3), fs, flags, ms, np.full(T, frame), far, near)
+        np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, flags=flags, ms=ms, out=out, codes=codes.astype(np.int16), paths=paths)
+        print("sesssparse", fs, frame, "live calls", int(((flags & 4) == 0).sum()), "of", T * S, sorted(set(codes.ravel().tolist())))
     from helpers import stream_config
     for name, S, nb, fs, seed0 in RAGGED_CASES:
         if only and only not in name:

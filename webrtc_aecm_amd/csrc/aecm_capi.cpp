@@ -574,6 +574,13 @@ int32_t WebRtcAecmSessions_DescribeTick(int32_t num_sessions, int32_t compute_un
     return 0;
 }
 
+int32_t WebRtcAecmSessions_DescribeTickLive(int32_t num_sessions, int32_t live_sessions, int32_t compute_units, AecmLaunchDescription *out) {
+    if (!out) return AECM_NULL_POINTER_ERROR;
+    if (num_sessions <= 0 || compute_units <= 0 || live_sessions < 0 || live_sessions > num_sessions) return AECM_BAD_PARAMETER_ERROR;
+    DescriptionToAbi(aecm::DescribeTickLaunchLive(num_sessions, live_sessions, compute_units), out);
+    return 0;
+}
+
 int32_t WebRtcAecm_SetDefaultDevice(int32_t device_id) {
     if (device_id < 0) return AECM_BAD_PARAMETER_ERROR;
     Session::SetDefaultDevice(device_id);
@@ -725,6 +732,12 @@ int32_t WebRtcAecmSessions_ProcessHost(AecmSessions *s, const int16_t *near_host
 }
 
 int32_t WebRtcAecmSessions_Synchronize(AecmSessions *s) { return s ? s->batch->Synchronize() : -1; }
+
+int32_t WebRtcAecmSessions_ForceSparseTicks(AecmSessions *s, int32_t on) {
+    if (!s) return -1;
+    s->batch->ForceSparseTicks(on != 0);
+    return 0;
+}
 
 int32_t WebRtcAecmSessions_SetKernelVariant(AecmSessions *s, int32_t variant) {
     if (!s) return -1;

@@ -492,6 +492,17 @@ LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units) {
     d.rounds_x1000 = RoundsX1000(d.workgroups, cus, d.workgroups_per_cu);
     return d;
 }
+// The same for a tick in which only live_sessions of the object's sessions call (aecm_tick_flow_sparse_kernel): the grid, and
+// with it the rounds, are by the sessions that call; none at all when nobody does.
+LaunchDescription DescribeTickLaunchLive(int num_sessions, int live_sessions, int compute_units) {
+    if (live_sessions >= num_sessions) return DescribeTickLaunch(num_sessions, compute_units);
+    LaunchDescription d = DescribeTickLaunch(live_sessions > 0 ? live_sessions : 1, compute_units);
+    if (live_sessions <= 0) {
+        d.workgroups = 0;
+        d.rounds_x1000 = 0;
+    }
+    return d;
+}
 
 // The plan travels through a pinned buffer of the engine's, so the copy is asynchronous and the caller's (and the plan's) memory is
 // free when this returns; the buffer is reused once the previous upload has run.

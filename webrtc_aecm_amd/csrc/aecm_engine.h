@@ -47,6 +47,7 @@ struct LaunchDescription {
     int detail() const { return form == 2 ? chunk_blocks : form == 3 ? shape : 0; }      // what WebRtcAecmBatch_DescribeLaunch returns beside the form
 };
 LaunchDescription DescribeTickLaunch(int num_sessions, int compute_units);
+LaunchDescription DescribeTickLaunchLive(int num_sessions, int live_sessions, int compute_units);
 
 // A ragged launch: stream s runs len[s] blocks.  Pure host logic (no device), so that it can be tested and used for planning.
 // The streams sorted by length, longest first (stable: equal lengths keep their stream order), make the streams live in chunk c --

@@ -56,7 +56,9 @@ enum FlowField : int {
     F_FF_VALID,                 // the framed-far ring holds the pending frame-stream samples [F_BLK_POS, F_FRM_POS)
     F_OLD_POS0, F_OLD_POS1,     // farendOld[i] (the frame replayed on an underrun) = far stream [F_OLD_POS_i, + 80) ...
     F_OLD_ROW0, F_OLD_ROW1,     // ... unless 1: it has been copied to replay row i (initially: the zeroed row)
+    F_NEAR_LAG,                 // near-end samples the OBJECT has ticked since this session last did (idle ticks, below); 0: in step
     kFlowFieldsUsed,
+    kFlowTickFields = F_NEAR_LAG,   // what FlowTick reads and writes: a tick of sessions that are all in step leaves the lag alone
     kFlowWords = 32
 };
 
@@ -65,8 +67,16 @@ constexpr int kFlowBlock = 64;                      // PART_LEN
 constexpr int kFlowJitterCapacity = 50 * 80;        // kBufSizeSamp = BUF_SIZE_FRAMES * FRAME_LEN (:29-36)
 constexpr int kFlowFarFrameRing = 256;              // ring of the framed far stream on the device (>= 143 + 80, power of two)
 constexpr int kFlowNoFarend = 1, kFlowSplitCalls = 2;   // = SessionBatch::kNoFarend / kSplitCalls
+constexpr int kFlowIdle = 4;                        // = SessionBatch::kIdle: the session makes no call at all in this tick (FlowIdleTick)
 constexpr int kFlowFarRing = 8192;                  // far ring of the device: positions older than this many accepted samples are gone
 constexpr int kFlowOldAge = kFlowFarRing - 5 * kFlowFrame;   // a replay frame this far behind the write position moves to its row
+
+// The near-end rings are indexed by the OBJECT's tick position.  A session that sits out ticks falls behind it by
+// F_NEAR_LAG samples: a multiple of 80 (ticks are 80 or 160 samples), kept modulo kFlowLagPeriod = lcm(80, ring length) --
+// only the lag modulo the ring length places anything, and 2^32 is no multiple of 80, so a free-running counter would
+// stop being a multiple of 80 after 74 hours of 10 ms ticks.
+constexpr int kFlowLagPeriod = 5 * kFlowFarRing;    // 40 960 = lcm(80, 8 192)
+static_assert(kFlowLagPeriod % 80 == 0 && kFlowLagPeriod % kFlowFarRing == 0, "lag period");
 
 struct FlowFarPiece {          // far_in[src, src + count) -> far stream positions [pos, pos + count)
     int32_t src, count;
@@ -148,6 +158,7 @@ AECM_FLOW_HD int FlowStateDefect(const int32_t v[kFlowWords]) {
         if (behind < pending || behind > (uint32_t)(kFlowJitterCapacity + 2 * kFlowFrame + kFlowBlock)) return F_RUN_DELTA + 1;
         if ((uint32_t)v[F_BLK_POS] - (uint32_t)v[F_RUN_POS] > (uint32_t)(4 * kFlowBlock)) return F_RUN_POS + 1;  // FlowTick keeps it at the last tick's first block
     }
+    if (v[F_NEAR_LAG] < 0 || v[F_NEAR_LAG] >= kFlowLagPeriod || v[F_NEAR_LAG] % kFlowFrame != 0) return F_NEAR_LAG + 1;   // whole ticks
     for (int f = kFlowFieldsUsed; f < kFlowWords; ++f)
         if (v[f] != 0) return f + 1;
     return 0;
@@ -283,9 +294,106 @@ AECM_FLOW_HD void FlowStartup(FlowRegs &s, int mult, int n_frames) {
     }
 }
 
+// A tick the session sits out (kFlowIdle): no WebRtcAecm_BufferFarend, no WebRtcAecm_Process -- the reference instance is
+// simply not called, so nothing of its state moves and what is pending stays pending.  On the device the session's rings
+// are not written either (they are per session: however long the stretch, nothing is lost); all that happens is that the
+// object's near position runs ahead of the session by another n samples.
+AECM_FLOW_HD int32_t FlowIdleTick(int32_t lag, int n) { return (int32_t)(((uint32_t)lag + (uint32_t)n) % (uint32_t)kFlowLagPeriod); }
+
+// The first tick a session makes after idle ticks brings it back in step BEFORE FlowTick runs: the only near-end (and clean)
+// samples a later block can still ask for are the pending ones, fewer than one block, [F_BLK_POS, F_FRM_POS) of the frame
+// stream; they sit just behind the session's own position near_pos - lag and move to just behind near_pos, where the tick's
+// samples continue them.  From then on the session is indistinguishable from one that never idled: FlowTick, the plan and
+// the tick kernel know nothing of lags.  (A session in its start-up phase has framed nothing: nothing moves.)
+struct FlowNearMove {          // near ring (and clean ring) positions [src, src + count) -> [dst, dst + count), count < 64
+    int32_t count;
+    uint32_t src, dst;
+};
+AECM_FLOW_HD void FlowResync(FlowRegs &s, uint32_t near_pos, FlowNearMove &m) {
+    const uint32_t pending = (uint32_t)s.v[F_FRM_POS] - (uint32_t)s.v[F_BLK_POS];
+    m.count = s.v[F_NEAR_LAG] != 0 ? (int32_t)pending : 0;
+    m.dst = near_pos - pending;
+    m.src = m.dst - (uint32_t)s.v[F_NEAR_LAG];
+    s.v[F_NEAR_LAG] = 0;
+}
+// The move itself, sample by sample in the order that is right for ranges that overlap in the ring (a lag of 8 240 is a
+// ring distance of 48): the destination lies d = (dst - src) mod ring ahead of the source; with d < count the copy runs
+// backwards, otherwise forwards (then the destination is either clear of the source or behind it).
+template <class T>
+AECM_FLOW_HD void FlowMoveNear(T *ring, uint32_t mask, const FlowNearMove &m) {
+    const uint32_t d = (m.dst - m.src) & mask;
+    if (d == 0) return;
+    if (d < (uint32_t)m.count) {
+        for (int32_t k = m.count - 1; k >= 0; --k) ring[(m.dst + (uint32_t)k) & mask] = ring[(m.src + (uint32_t)k) & mask];
+    } else {
+        for (int32_t k = 0; k < m.count; ++k) ring[(m.dst + (uint32_t)k) & mask] = ring[(m.src + (uint32_t)k) & mask];
+    }
+}
+
+// Which launches a tick of an OBJECT takes (SessionBatch::Enqueue; tests/sim/sim_sparse.cpp drives this very function).
+// The object keeps two things about lags: may_lag -- some session may be behind the object's near position (a session sat
+// out a tick since the last tick everybody made) -- and deferred_lag, the samples of ticks NOBODY made: those launch nothing,
+// so the sessions learn of them from the next planning launch, which adds deferred_lag to every session's lag first.
+//   launch == false  nobody calls: nothing is launched, the object's position moves on
+//   sparse_plan      the planning launch is the one that knows lags and idle lanes (aecm_flow_plan_sparse_kernel); it is
+//                    handed deferred_lag.  false: every session calls and every session is in step -- the launches of an
+//                    object that knows no idle sessions
+//   sparse_tick      the tick launch runs by the live list (somebody sits out, or the diagnostics switch); else the dense
+//                    tick kernel over everybody
+struct FlowObjectLag {
+    int32_t deferred_lag = 0;
+    bool may_lag = false;
+};
+struct FlowTickRoute {
+    bool launch, sparse_plan, sparse_tick;
+    int32_t deferred_lag;       // what the planning launch adds to every lag (sparse_plan)
+};
+inline FlowTickRoute FlowRouteTick(FlowObjectLag &o, int32_t live, int32_t n_sessions, int n, bool force_sparse) {
+    FlowTickRoute r{live > 0, false, false, 0};
+    if (!r.launch) {
+        o.deferred_lag = FlowIdleTick(o.deferred_lag, n);
+        o.may_lag = true;
+        return r;
+    }
+    r.sparse_tick = live < n_sessions || force_sparse;
+    r.sparse_plan = r.sparse_tick || o.may_lag;
+    if (r.sparse_plan) {
+        r.deferred_lag = o.deferred_lag;
+        o.deferred_lag = 0;
+        o.may_lag = live < n_sessions;        // everybody called: everybody is in step again
+    }
+    return r;
+}
+
+// The live list of a tick in which sessions idle: the ids of the sessions that do call, ascending, so that wavefront w of
+// the tick kernel serves session live[w].  Built without atomics, in two halves.  The host half, in the pass over the flags
+// the host makes anyway: bases[b] = live sessions among the first kFlowPlanBlock * b, returns the live count.  The device
+// half, in the planning kernel (kFlowPlanBlock lanes per workgroup, one per session): a live lane's slot is its workgroup's
+// base + the live lanes of the wavefronts before it in the workgroup + the live lanes before it in its wavefront.
+constexpr int kFlowPlanBlock = 256;
+inline int32_t FlowLiveBlockBases(const uint8_t *flags, int32_t n_sessions, uint32_t *bases) {
+    int32_t live = 0;
+    for (int32_t first = 0, b = 0; first < n_sessions; first += kFlowPlanBlock, ++b) {
+        bases[b] = (uint32_t)live;
+        const int32_t end = first + kFlowPlanBlock < n_sessions ? first + kFlowPlanBlock : n_sessions;
+        int32_t idle = 0;
+        for (int32_t s = first; s < end; ++s) idle += (flags[s] >> 2) & 1;
+        live += (end - first) - idle;
+    }
+    return live;
+}
+static_assert(kFlowIdle == 4, "FlowLiveBlockBases counts bit 2");
+// wave_counts[w] = live lanes of wavefront w of the workgroup, ballot = the live lanes of this lane's wavefront.
+AECM_FLOW_HD uint32_t FlowLiveSlot(uint32_t block_base, const uint32_t wave_counts[kFlowPlanBlock / 64], int wave, uint64_t ballot, int lane) {
+    uint32_t slot = block_base;
+    for (int w = 0; w < kFlowPlanBlock / 64; ++w) slot += w < wave ? wave_counts[w] : 0u;
+    const uint64_t below = ballot & ((uint64_t(1) << lane) - 1u);
+    return slot + (uint32_t)__builtin_popcountll(below);
+}
+
 // One tick: [WebRtcAecm_BufferFarend] + WebRtcAecm_Process of n samples (80 or 160), or two such pairs of 80 samples
 // (kFlowSplitCalls, n = 160).  ms = the caller's msInSndCardBuf, near_pos = near-ring position of the tick's first
-// near-end sample.  Advances s and fills the plan.
+// near-end sample.  Advances s and fills the plan.  The session is in step (F_NEAR_LAG == 0; FlowResync first otherwise).
 AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32_t near_pos, FlowPlan &p) {
     const int mult = fs == 16000 ? 2 : 1;
     const bool split = (flags & kFlowSplitCalls) != 0 && n == 2 * kFlowFrame;

@@ -156,10 +156,26 @@ struct TickFlowIo {
     int16_t *far_frames;               // [S][kFlowFarFrameRing]
     int16_t *far_old;                  // [S][2 * 80]
     const int16_t *ms_per_session;     // [S] or null: everybody gets `ms`
-    const uint8_t *flags_per_session;  // [S] or null: everybody gets `flags` (kFlowNoFarend | kFlowSplitCalls)
+    const uint8_t *flags_per_session;  // [S] or null: everybody gets `flags` (kFlowNoFarend | kFlowSplitCalls; kFlowIdle per session, sparse launch only)
     int32_t ms, flags, fs;
 };
 hipError_t LaunchTickFlow(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, int n_streams, hipStream_t stream);
+// A tick in which sessions sit out (fio.flags_per_session carries kFlowIdle for them), or the first ticks after such a one
+// (sessions may still lag behind the object's near position: aecm_flow_plan.h, F_NEAR_LAG):
+//   aecm_flow_plan_sparse_kernel   one lane per session over ALL sessions: an idle lane counts its lag, a live one brings its
+//                                  session back in step and plans; with `live` set it also writes the live sessions' ids,
+//                                  ascending, to that list (block_base: FlowLiveBlockBases of the tick's flags)
+//   aecm_tick_flow_sparse_kernel   wavefront w serves session live[w]: ceil(live_count / 4) workgroups; none for live_count 0
+// live == nullptr: nobody idles in this tick -- the tick launch is the dense aecm_tick_flow_kernel over everybody.
+struct TickSparseIo {
+    int16_t *near_ring, *clean_ring;   // [S][ring_len]; clean_ring may be null
+    int64_t ring_len;
+    uint32_t *live;                    // [S] device list the planning kernel fills, or null
+    const uint32_t *block_base;        // [ceil(S / kFlowPlanBlock)] live sessions before each planning workgroup (with live)
+    int32_t deferred_lag;              // added to every session's lag first: the ticks nobody made (no launch told the sessions)
+};
+hipError_t LaunchTickFlowSparse(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int live_count,
+                                hipStream_t stream);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront

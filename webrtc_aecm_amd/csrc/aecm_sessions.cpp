@@ -27,14 +27,19 @@ SessionBatch *SessionBatch::Create(int num_streams, int device_id) {
                     AECM_HIP_OK(hipMalloc((void **)&b->flow_state_, S * kFlowFieldsUsed * sizeof(int32_t))) &&
                     AECM_HIP_OK(hipMalloc((void **)&b->flow_plans_, S * kFlowPlanWords * sizeof(int32_t))) &&
                     AECM_HIP_OK(hipMalloc((void **)&b->far_frames_, S * kFlowFarFrameRing * 2)) &&
+                    AECM_HIP_OK(hipMalloc((void **)&b->live_dev_, S * sizeof(uint32_t))) &&
                     // (the per-session msInSndCardBuf / flags slots: pinned host arrays the planning kernel reads in place, below)
                     AECM_HIP_OK(hipMalloc((void **)&b->far_old_, S * 2 * kFlowFrame * 2));
     bool slots = ok;
+    const size_t plan_blocks = (S + kFlowPlanBlock - 1) / kFlowPlanBlock;
+    b->live_bases_.assign(plan_blocks, 0u);
     for (int k = 0; k < kArgSlots && slots; ++k)
         slots = AECM_HIP_OK(hipHostMalloc((void **)&b->ms_host_[k], S * sizeof(int16_t), hipHostMallocMapped)) &&
                 AECM_HIP_OK(hipHostMalloc((void **)&b->flags_host_[k], S, hipHostMallocMapped)) &&
+                AECM_HIP_OK(hipHostMalloc((void **)&b->bases_host_[k], plan_blocks * sizeof(uint32_t), hipHostMallocMapped)) &&
                 AECM_HIP_OK(hipHostGetDevicePointer((void **)&b->ms_dev_[k], b->ms_host_[k], 0)) &&
                 AECM_HIP_OK(hipHostGetDevicePointer((void **)&b->flags_dev_[k], b->flags_host_[k], 0)) &&
+                AECM_HIP_OK(hipHostGetDevicePointer((void **)&b->bases_dev_[k], b->bases_host_[k], 0)) &&
                 AECM_HIP_OK(hipEventCreateWithFlags(&b->slot_read_[k], hipEventDisableTiming));
     if (!slots) {
         delete b;
@@ -55,7 +60,9 @@ SessionBatch::~SessionBatch() {
     (void)hipFree(flow_plans_);
     (void)hipFree(far_frames_);
     (void)hipFree(far_old_);
+    (void)hipFree(live_dev_);
     for (int k = 0; k < kArgSlots; ++k) {
+        if (bases_host_[k]) (void)hipHostFree(bases_host_[k]);
         if (ms_host_[k]) (void)hipHostFree(ms_host_[k]);
         if (flags_host_[k]) (void)hipHostFree(flags_host_[k]);
         if (slot_read_[k]) (void)hipEventDestroy(slot_read_[k]);
@@ -78,6 +85,7 @@ int32_t SessionBatch::Init(int32_t samp_freq) {
         (clean_ring_ && !AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, engine_->stream()))) || !ResetFlowRows(0, S))
         return AECM_UNSPECIFIED_ERROR;
     near_pos_ = 0;
+    lag_ = FlowObjectLag();
     fs_ = samp_freq;
     poisoned_ = false;
     return 0;
@@ -232,7 +240,7 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     if (far == nullptr) {                 // only a tick in which nobody makes a WebRtcAecm_BufferFarend call needs no far rows
         bool nobody = flags_per_session ? true : (flags & kNoFarend) != 0;
         if (flags_per_session && fs_ != 0)
-            for (int s = 0; s < engine_->num_streams() && nobody; ++s) nobody = (flags_per_session[s] & kNoFarend) != 0;
+            for (int s = 0; s < engine_->num_streams() && nobody; ++s) nobody = (flags_per_session[s] & (kNoFarend | kIdle)) != 0;
         if (!nobody) return AECM_NULL_POINTER_ERROR;
     }
     if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
@@ -247,12 +255,33 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     const int S = engine_->num_streams();
     hipStream_t st = engine_->stream();
     if (!EventUsable(wait_event) || !EventUsable(done_event)) return AECM_BAD_PARAMETER_ERROR;
-    if (n != 160) {
-        uint8_t any = flags_per_session ? 0 : (uint8_t)flags;
-        if (flags_per_session)
-            for (int s = 0; s < S; ++s) any |= flags_per_session[s];
-        if (any & kSplitCalls) return AECM_BAD_PARAMETER_ERROR;                           // two 80-sample calls need 160 samples
+    // Who calls in this tick (kIdle: neither call; the other bits of an idle session's byte mean nothing).  One pass over the
+    // flags: the live count, and per planning workgroup the live sessions before it (what the device needs for the live list).
+    int live = S;
+    uint8_t any = flags_per_session ? 0 : (uint8_t)flags;
+    if (flags_per_session) {
+        live = FlowLiveBlockBases(flags_per_session, S, live_bases_.data());
+        if (n != 160)
+            for (int s = 0; s < S; ++s) any |= (flags_per_session[s] & kIdle) ? 0 : flags_per_session[s];
     }
+    if (n != 160 && (any & kSplitCalls)) return AECM_BAD_PARAMETER_ERROR;                 // two 80-sample calls need 160 samples
+    const auto idle = [&](int s) { return flags_per_session && (flags_per_session[s] & kIdle) != 0; };
+    if (live == 0) {
+        // Nobody calls: nothing is launched.  The object's position moves on all the same; the sessions learn of it with the
+        // next tick somebody makes (aecm_flow_plan.h: FlowRouteTick).
+        if (wait_event && !AECM_HIP_OK(hipStreamWaitEvent(st, static_cast<hipEvent_t>(wait_event), 0))) {
+            (void)hipGetLastError();
+            return AECM_BAD_PARAMETER_ERROR;
+        }
+        near_pos_ += n;
+        (void)FlowRouteTick(lag_, 0, S, n, force_sparse_);
+        if (codes) memset(codes, 0, (size_t)S * sizeof(int32_t));
+        if (host_pointers)
+            for (int s = 0; s < S; ++s) memset(out + (size_t)s * stride, 0, (size_t)n * 2);
+        if (done_event && !AECM_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(done_event), st))) return Fail();
+        return 0;
+    }
+    const bool sparse_tick = live < S || force_sparse_;      // (as FlowRouteTick will say below, once the tick is certain to be enqueued)
     if (clean && !clean_ring_) {
         const size_t bytes = (size_t)S * kRing * 2;
         if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
@@ -265,7 +294,7 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     auto fail = [&]() -> int32_t { return Fail(); };
     // this tick's argument slot
     bool slot_ok;
-    const int slot = AcquireArgSlot(ms_per_session || flags_per_session, &slot_ok);
+    const int slot = AcquireArgSlot(ms_per_session || flags_per_session || sparse_tick, &slot_ok);
     if (!slot_ok) return fail();
     auto code_of = [](int16_t v) -> int32_t { return (v < 0 || v > 500) ? AECM_BAD_PARAMETER_WARNING : 0; };
     int32_t first_rc = 0;
@@ -277,7 +306,7 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         }
         if (lo < 0 || hi > 500) {
             for (int s = 0; s < S; ++s) {
-                const int32_t rc = code_of(ms_per_session[s]);
+                const int32_t rc = idle(s) ? 0 : code_of(ms_per_session[s]);      // an idle session makes no call: no code
                 if (codes) codes[s] = rc;
                 if (rc != 0 && first_rc == 0) first_rc = rc;
             }
@@ -288,10 +317,15 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     } else {
         first_rc = code_of(ms);
         if (codes)
-            for (int s = 0; s < S; ++s) codes[s] = first_rc;
+            for (int s = 0; s < S; ++s) codes[s] = idle(s) ? 0 : first_rc;
     }
     if (flags_per_session) {
         memcpy(flags_host_[slot], flags_per_session, (size_t)S);
+    }
+    if (sparse_tick) {
+        if (!flags_per_session)
+            for (size_t b = 0; b < live_bases_.size(); ++b) live_bases_[b] = (uint32_t)(b * kFlowPlanBlock);
+        memcpy(bases_host_[slot], live_bases_.data(), live_bases_.size() * sizeof(uint32_t));
     }
     // without far rows (nobody buffers a far frame in this tick) the kernel's far row pointer is never used for a sample that
     // counts; it still has to be an address: the near rows
@@ -317,6 +351,8 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         dnear = d;
         dout = io_dev_ + 2 * plane;
         if (clean) dclean = c;
+        // whole planes travel back: the rows of sessions that sit out, which no kernel writes, as zeros
+        if (live < S && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * n * 2, st))) return fail();
     }
     TickIo tio{dfar, dnear, dclean, dout, dstride, n, far_ring_, near_ring_, clean_ring_, out_ring_, kRing, near_pos_};
     TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, ms_per_session ? ms_dev_[slot] : nullptr,
@@ -325,10 +361,18 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         (void)hipGetLastError();
         return AECM_BAD_PARAMETER_ERROR;      // nothing of this tick has been enqueued (device pointers: no staging copies): no poison
     }
-    const bool ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
+    bool ok;
+    const FlowTickRoute route = FlowRouteTick(lag_, live, S, n, force_sparse_);
+    if (!route.sparse_plan) {
+        ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
+    } else {
+        const TickSparseIo sp{near_ring_, clean_ring_, kRing, route.sparse_tick ? live_dev_ : nullptr, route.sparse_tick ? bases_dev_[slot] : nullptr,
+                              route.deferred_lag};
+        ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, sp, S, live, st));
+    }
     near_pos_ += n;
     if (!ok) return fail();
-    if (ms_per_session || flags_per_session) {            // both launches of the tick are behind this event; only the first reads the slot
+    if (ms_per_session || flags_per_session || sparse_tick) {            // both launches of the tick are behind this event; only the first reads the slot
         if (!AECM_HIP_OK(hipEventRecord(slot_read_[slot], st))) return fail();
         slot_busy_[slot] = true;
     }
@@ -390,11 +434,15 @@ int32_t SessionBatch::ExportSession(int session, void *buf) {
     };
     bool ok = AECM_HIP_OK(hipMemcpy2D(flow, sizeof(int32_t), flow_state_ + session, (size_t)S * sizeof(int32_t), sizeof(int32_t), kFlowFieldsUsed,
                                       hipMemcpyDeviceToHost));
+    // The session's own near position: the object's, less what the session has sat out (its lag on the device + the all-idle
+    // ticks not yet added to it).  The snapshot itself is in step -- lag 0, as every snapshot before there were idle ticks.
+    const uint32_t own_near_pos = (uint32_t)near_pos_ - (uint32_t)flow[F_NEAR_LAG] - (uint32_t)lag_.deferred_lag;
+    flow[F_NEAR_LAG] = 0;
     memcpy(p + at.flow, flow, sizeof flow);
     ok = ok && AECM_HIP_OK(hipMemcpy(p + at.far, far_ring_ + (size_t)session * kRing, kRing * 2, hipMemcpyDeviceToHost)) &&
          tail(out_ring_ + (size_t)session * kRing, (uint32_t)flow[F_BLK_POS], kOutTail, p + at.out) &&
-         tail(near_ring_ + (size_t)session * kRing, (uint32_t)near_pos_, kNearTail, p + at.near);
-    if (ok && clean_ring_) ok = tail(clean_ring_ + (size_t)session * kRing, (uint32_t)near_pos_, kNearTail, p + at.clean);
+         tail(near_ring_ + (size_t)session * kRing, own_near_pos, kNearTail, p + at.near);
+    if (ok && clean_ring_) ok = tail(clean_ring_ + (size_t)session * kRing, own_near_pos, kNearTail, p + at.clean);
     else memset(p + at.clean, 0, kNearTail * 2);
     ok = ok && AECM_HIP_OK(hipMemcpy(p + at.frames, far_frames_ + (size_t)session * kFlowFarFrameRing, kFlowFarFrameRing * 2, hipMemcpyDeviceToHost)) &&
          AECM_HIP_OK(hipMemcpy(p + at.old, far_old_ + (size_t)session * 2 * kFlowFrame, 2 * kFlowFrame * 2, hipMemcpyDeviceToHost));
@@ -438,6 +486,10 @@ int32_t SessionBatch::ImportSession(int session, const void *buf) {
     }
     // (ImportState validates the blob once more and is the first thing that writes)
     if (const int32_t rc = engine_->ImportState(session, p + at.state)) return rc;
+    // The session arrives in step with this object: its tail goes behind the object's near position, its lag is 0 -- behind
+    // the position the device takes for the object's while all-idle ticks are still to be added to the lags, that is.
+    flow[F_NEAR_LAG] = 0;
+    const uint32_t own_near_pos = (uint32_t)near_pos_ - (uint32_t)lag_.deferred_lag;
     std::vector<int16_t> row(kRing, 0);
     auto place_tail = [&](int16_t *ring_row, uint32_t end_pos, int n, const uint8_t *src, bool zero_rest) -> bool {
         if (!zero_rest && !AECM_HIP_OK(hipMemcpy(row.data(), ring_row, kRing * 2, hipMemcpyDeviceToHost))) return false;
@@ -451,8 +503,8 @@ int32_t SessionBatch::ImportSession(int session, const void *buf) {
                                       hipMemcpyHostToDevice)) &&
               AECM_HIP_OK(hipMemcpy(far_ring_ + (size_t)session * kRing, p + at.far, kRing * 2, hipMemcpyHostToDevice)) &&
               place_tail(out_ring_ + (size_t)session * kRing, (uint32_t)flow[F_BLK_POS], kOutTail, p + at.out, true) &&
-              place_tail(near_ring_ + (size_t)session * kRing, (uint32_t)near_pos_, kNearTail, p + at.near, false);
-    if (ok && clean_ring_) ok = place_tail(clean_ring_ + (size_t)session * kRing, (uint32_t)near_pos_, kNearTail, p + at.clean, false);
+              place_tail(near_ring_ + (size_t)session * kRing, own_near_pos, kNearTail, p + at.near, false);
+    if (ok && clean_ring_) ok = place_tail(clean_ring_ + (size_t)session * kRing, own_near_pos, kNearTail, p + at.clean, false);
     ok = ok && AECM_HIP_OK(hipMemcpy(far_frames_ + (size_t)session * kFlowFarFrameRing, p + at.frames, kFlowFarFrameRing * 2, hipMemcpyHostToDevice)) &&
          AECM_HIP_OK(hipMemcpy(far_old_ + (size_t)session * 2 * kFlowFrame, p + at.old, 2 * kFlowFrame * 2, hipMemcpyHostToDevice));
     return ok ? 0 : Fail();           // a session half written is not a session: the object is poisoned

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include <memory>
+#include <vector>
 
 #include "aecm_engine.h"
 #include "aecm_kernels.h"
@@ -46,8 +47,12 @@ public:
     //     bit 1 (kSplitCalls, 160-sample ticks only) = this session makes TWO BufferFarend + Process call pairs of 80
     //     samples in this tick instead of one of 160 (the reference treats the two cadences differently:
     //     echo_control_mobile.cc:282-283, 384-385).
-    //   flags: the same bits for every session when flags_per_session is null.
-    //   far may be null when no session makes a BufferFarend call in this tick (kNoFarend for everybody).
+    //     bit 2 (kIdle) = this session makes NO call in this tick (a reference instance that is not called: nothing of it
+    //     changes, what is pending stays pending); its other bits and its far / near / clean / ms / out entries mean nothing,
+    //     its code is 0, its out row is not written (host pointers: zeros).  The tick's device work is by the sessions that call;
+    //     a tick nobody makes launches nothing.
+    //   flags: the same bits for every session when flags_per_session is null (kNoFarend / kSplitCalls).
+    //   far may be null when no session makes a BufferFarend call in this tick (kNoFarend or kIdle for everybody).
     int32_t Tick(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
                  int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers, int flags = 0);
     // The same tick, enqueued on the object's stream without waiting for it (device pointers, or host memory the device
@@ -65,7 +70,10 @@ public:
     int32_t BufferFarend(const int16_t *far, int64_t stream_stride, size_t n, int32_t calls, const uint8_t *calls_per_session, bool host_pointers,
                          bool wait, void *wait_event, void *done_event);
     int32_t Synchronize();
-    static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls;
+    static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle;
+    // Diagnostics (tools/bench_sessions.py): every tick through the live list and the sparse tick kernel, idle sessions or
+    // not -- what the indirection itself costs.
+    void ForceSparseTicks(bool on) { force_sparse_ = on; }
 
     // Snapshot of ONE live session (checkpoint; migration into another object, on another GPU): everything the reference
     // keeps per instance -- AecMobile's wrapper members and jitter buffer (echo_control_mobile.cc:42-79), the core's frame
@@ -75,7 +83,9 @@ public:
     //   (indexed by the session's own far-stream positions) | the last kOutTail block-output samples before F_BLK_POS |
     //   the last kNearTail near-end (and clean near-end) samples ticked (the only ones a later block can still ask for:
     //   fewer than one block is ever pending) | framed-far ring | the two replay rows.
-    // The near-end rings are indexed by the OBJECT's tick position, so their tails are re-placed at the importing object's.
+    // The near-end rings are indexed by the OBJECT's tick position, so their tails are re-placed at the importing object's
+    // (and cut at the session's own position, which lies behind the object's while the session sits out ticks: kIdle; the
+    // snapshot itself is always in step, lag word 0, and the session arrives in step with the importing object).
     // ImportSession validates everything FlowTick / the tick kernel turn into a count or an index (aecm_flow_plan.h:
     // FlowStateDefect) and the block-stream blob like ImportState does; a refused blob changes nothing.  The session's rate
     // must be the object's.  Both calls wait for the ticks enqueued so far.
@@ -97,6 +107,12 @@ private:
     // (AECM_UNSPECIFIED_ERROR) until Init.
     bool poisoned_ = false;
     int64_t near_pos_ = 0;                     // near-end samples ticked so far = ring position of the next tick's first one
+    // Sessions that sat out ticks lag behind near_pos_ (aecm_flow_plan.h: F_NEAR_LAG) until their next call; what the object
+    // itself keeps about that, and which launches a tick takes by it: FlowObjectLag / FlowRouteTick.
+    FlowObjectLag lag_;
+    bool force_sparse_ = false;
+    uint32_t *live_dev_ = nullptr;             // [S] the tick's live sessions, ascending (written by the planning launch)
+    std::vector<uint32_t> live_bases_;         // [ceil(S / kFlowPlanBlock)] FlowLiveBlockBases of the tick's flags
     int16_t *far_ring_ = nullptr, *near_ring_ = nullptr, *out_ring_ = nullptr;   // [S][kRing]
     int16_t *clean_ring_ = nullptr;            // [S][kRing], allocated by the first tick that carries a clean near-end
     int16_t *io_dev_ = nullptr;                // [4][S][160] staging when the caller passes host pointers
@@ -110,6 +126,7 @@ private:
     static constexpr int kArgSlots = 2;
     int16_t *ms_host_[kArgSlots] = {nullptr, nullptr}, *ms_dev_[kArgSlots] = {nullptr, nullptr};          // [S] each
     uint8_t *flags_host_[kArgSlots] = {nullptr, nullptr}, *flags_dev_[kArgSlots] = {nullptr, nullptr};    // [S] each
+    uint32_t *bases_host_[kArgSlots] = {nullptr, nullptr}, *bases_dev_[kArgSlots] = {nullptr, nullptr};    // [ceil(S / 256)] each
     hipEvent_t slot_read_[kArgSlots] = {nullptr, nullptr};
     bool slot_busy_[kArgSlots] = {false, false};
     int slot_ = 0;

@@ -61,9 +61,11 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_SetKernelVariant", "WebRtcAecmSessions_session_size_bytes", "WebRtcAecmSessions_ExportSession",
     "WebRtcAecmSessions_ImportSession", "WebRtcAecmSessions_BufferFarend", "WebRtcAecmSessions_BufferFarendHost",
     "WebRtcAecmSessions_BufferFarendAsync", "WebRtcAecmSessions_Process", "WebRtcAecmSessions_ProcessHost", "WebRtcAecmSessions_DescribeTick",
+    "WebRtcAecmSessions_DescribeTickLive", "WebRtcAecmSessions_ForceSparseTicks",
 ]
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
+SESSION_IDLE = 4
 
 
 class AecmConfig(C.Structure):
@@ -188,6 +190,8 @@ def load():
     lib.WebRtcAecmBatch_DescribeLaunchDetail.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                          C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmSessions_DescribeTick.argtypes = [C.c_int32, C.c_int32, C.POINTER(AecmLaunchDescription)]
+    lib.WebRtcAecmSessions_DescribeTickLive.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(AecmLaunchDescription)]
+    lib.WebRtcAecmSessions_ForceSparseTicks.argtypes = [vp, C.c_int32]
     lib.WebRtcAecm_SetDefaultDevice.argtypes = [C.c_int32]
     lib.WebRtcAecmSessions_Create.restype = vp
     lib.WebRtcAecmSessions_Create.argtypes = [C.c_int32, C.c_int32]
@@ -599,8 +603,9 @@ class AecmSessions:
         return self.lib.WebRtcAecmSessions_Tick(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, ms)
 
     def tick_host_per_session(self, far, near, ms_per_session, clean=None, flags=None):
-        """far/near(/clean): [S, n] int16; ms_per_session: S msInSndCardBuf values; flags: S uint8 (SESSION_NO_FAREND)
-        or None.  Returns (code, out, codes[S])."""
+        """far/near(/clean): [S, n] int16; ms_per_session: S msInSndCardBuf values; flags: S uint8 (SESSION_NO_FAREND,
+        SESSION_SPLIT_CALLS, SESSION_IDLE) or None.  Returns (code, out, codes[S]); the out row of a session that carries
+        SESSION_IDLE is zeros, its code 0."""
         far, near, clean, cptr = self._rows(far, near, clean)
         ms = np.ascontiguousarray(ms_per_session, dtype=np.int16)
         if ms.shape != (self.num_streams,):
@@ -715,6 +720,22 @@ class AecmSessions:
             flp = flags.ctypes.data
         return self.lib.WebRtcAecmSessions_TickAsync(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, ms, msp, flp, None,
                                                      wait_event, done_event)
+
+    def tick_device_flags(self, far_ptr, near_ptr, out_ptr, stream_stride, n, ms_per_session, flags, clean_ptr=None):
+        """WebRtcAecmSessions_TickFlags (device pointers).  Returns (code, codes[S]); the out row of a session that carries
+        SESSION_IDLE is not written."""
+        ms = np.ascontiguousarray(ms_per_session, dtype=np.int16)
+        fl = np.ascontiguousarray(flags, dtype=np.uint8)
+        if ms.shape != (self.num_streams,) or fl.shape != (self.num_streams,):
+            raise ValueError("ms_per_session and flags must have one entry per session")
+        codes = np.zeros(self.num_streams, dtype=np.int32)
+        rc = self.lib.WebRtcAecmSessions_TickFlags(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, ms.ctypes.data,
+                                                   fl.ctypes.data, codes.ctypes.data)
+        return rc, codes
+
+    def force_sparse_ticks(self, on: bool = True) -> int:
+        """Diagnostics: every tick through the live list and the sparse tick kernel (WebRtcAecmSessions_ForceSparseTicks)."""
+        return self.lib.WebRtcAecmSessions_ForceSparseTicks(self.h, 1 if on else 0)
 
     def synchronize(self):
         return self.lib.WebRtcAecmSessions_Synchronize(self.h)
@@ -876,6 +897,15 @@ def describe_tick(num_sessions: int, compute_units: int) -> dict:
     rc = load().WebRtcAecmSessions_DescribeTick(num_sessions, compute_units, C.byref(d))
     if rc != 0:
         raise AecmError(rc, "WebRtcAecmSessions_DescribeTick")
+    return d.as_dict()
+
+
+def describe_tick_live(num_sessions: int, live_sessions: int, compute_units: int) -> dict:
+    """WebRtcAecmSessions_DescribeTickLive: the tick launch of an object of num_sessions sessions of which live_sessions call."""
+    d = AecmLaunchDescription()
+    rc = load().WebRtcAecmSessions_DescribeTickLive(num_sessions, live_sessions, compute_units, C.byref(d))
+    if rc != 0:
+        raise AecmError(rc, "WebRtcAecmSessions_DescribeTickLive")
     return d.as_dict()
 
 
