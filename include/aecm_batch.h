@@ -215,6 +215,18 @@ enum {
      * back in step (then the dense tick kernel); from the next one on the object is as if nobody had ever idled. */
     AECM_SESSION_IDLE = 4
 };
+enum {
+    /* 160-sample ticks only: this session makes ONE WebRtcAecm_BufferFarend + WebRtcAecm_Process call pair of 80 samples in this
+     * tick, on the first half of its rows (10 ms of an 8 kHz call next to 10 ms of 16 kHz calls).  The second half of its far /
+     * near / near_clean rows never influences anything; out[s][80..160) is not written by the device-pointer forms and comes back
+     * as zeros from TickFlagsHost.  With a tick of 80 samples, or together with AECM_SESSION_SPLIT_CALLS:
+     * AECM_BAD_PARAMETER_ERROR, nothing changed.  Ignored in an idle session's byte like every other bit.
+     * A tick in which a session makes a half call, and every tick of an object that holds a session of another rate than its
+     * own (below: WebRtcAecmSessions_InitRates), takes the planning launch that knows per-session rates and call sizes; the tick
+     * launch is the one it would be anyway.  An object whose sessions all run at its own rate and make no half calls takes
+     * exactly the launches it takes without this flag. */
+    AECM_SESSION_HALF_CALL = 8
+};
 int32_t WebRtcAecmSessions_TickFlags(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev,
                                      const int16_t *near_clean_dev, int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples,
                                      const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host);
@@ -309,6 +321,26 @@ int32_t WebRtcAecmSessions_GetEchoPath(AecmSessions *s, int32_t session, void *e
 size_t WebRtcAecmSessions_session_size_bytes(void);
 int32_t WebRtcAecmSessions_ExportSession(AecmSessions *s, int32_t session, void *snapshot, size_t size_bytes);
 int32_t WebRtcAecmSessions_ImportSession(AecmSessions *s, int32_t session, const void *snapshot, size_t size_bytes);
+
+/* Sessions of both sampling rates in ONE object -- one object per clock, not per rate: narrowband (8 kHz, 10 ms = 80 samples)
+ * and wideband (16 kHz, 10 ms = 160 samples) calls tick together, a 160-sample tick with AECM_SESSION_HALF_CALL for the
+ * sessions whose 10 ms are 80 samples.  Every session runs at its own rate wherever the reference looks at an instance's rate
+ * (echo_control_mobile.cc:142-191, 236-283, 384-387, 534-594; the core's wideband branch): in Tick*, BufferFarend* and
+ * Process* alike.  The call size of BufferFarend* and Process* stays one value per call for the whole object.
+ * ExportSession writes the session's own rate into the snapshot; ImportSession of an object whose own rate that is takes it
+ * (a call moves between uniform and mixed objects in both directions).
+ *
+ * InitRates: as WebRtcAecmSessions_Init(s, sampFreq); then every session k with rates_host[k] != sampFreq (S entries, each 8000
+ * or 16000; AECM_BAD_PARAMETER_ERROR and nothing changed otherwise) is a fresh WebRtcAecm_Init(inst_k, rates_host[k]).
+ * sampFreq stays the object's own rate: what InitSession and ImportSession mean by "the same rate".
+ * InitSessionRate: InitSession at a rate of the caller's choice, WebRtcAecm_Init(inst_s, sampFreq).  A launch on the object's
+ * stream, ordered before the next tick like InitSession.
+ * ImportSessionAnyRate: ImportSession that also takes a snapshot of the other rate (header and core state must agree on it);
+ * the slot then runs at the snapshot's rate.  Everything ImportSession refuses for another reason is refused here too. */
+int32_t WebRtcAecmSessions_InitRates(AecmSessions *s, int32_t sampFreq, const int32_t *rates_host);
+int32_t WebRtcAecmSessions_InitSessionRate(AecmSessions *s, int32_t session, int32_t sampFreq);
+int32_t WebRtcAecmSessions_GetSessionRate(AecmSessions *s, int32_t session, int32_t *sampFreq);
+int32_t WebRtcAecmSessions_ImportSessionAnyRate(AecmSessions *s, int32_t session, const void *snapshot, size_t size_bytes);
 
 /* AECM_KERNEL_FAST (default) or AECM_KERNEL_SAFE cross-lane primitives. */
 int32_t WebRtcAecmBatch_SetKernelVariant(AecmBatch *b, int32_t variant);

@@ -18,6 +18,13 @@ the others sit out every tick; device-resident audio, WebRtcAecmSessions_TickAsy
 ticks enqueued back to back.  Printed next to the dense tick of the same object size (the same call without a flags array,
 --repeats times: its spread is the yardstick for every difference).  P = 1.0 is a tick forced through the live list and the
 sparse tick kernel with nobody idle (WebRtcAecmSessions_ForceSparseTicks): what the indirection itself costs.
+
+--mixed P[,P...]: one object per clock, not per rate.  For each P an object of rate 16 000 in which a fixed, seeded random P % of the
+sessions are 8 kHz sessions (WebRtcAecmSessions_InitRates) that make a half call (AECM_SESSION_HALF_CALL: 10 ms = 80 samples) in
+every 160-sample tick, the rest 16 kHz / 160; device-resident audio, TickAsync with per-session msInSndCardBuf and flags.  Printed
+next to (a) the all-16 kHz object of the same size without a flags array -- and once more with the arrays the mixed rows pass, flags
+that name nothing --, and (d) what a user without mixed objects does for the
+50 % case: two objects of S / 2 sessions, one 8 kHz / 80 and one 16 kHz / 160, ticked back to back.  --repeats times each.
 """
 import argparse
 import json
@@ -41,10 +48,13 @@ def main():
     ap.add_argument("--async", dest="asynchronous", action="store_true",
                     help="WebRtcAecmSessions_TickAsync: ticks are enqueued back to back, one synchronisation at the end (host-staged always is)")
     ap.add_argument("--occupancy", default="", help="P[,P...]: share of the sessions that is live; the others are idle every tick (see above)")
-    ap.add_argument("--repeats", type=int, default=3, help="--occupancy: measurements per column (the median is reported, all are listed)")
+    ap.add_argument("--mixed", default="", help="P[,P...]: per cent of the sessions that are 8 kHz half-call sessions in a 16 kHz object (see above)")
+    ap.add_argument("--repeats", type=int, default=3, help="--occupancy / --mixed: measurements per column (the median is reported, all are listed)")
     args = ap.parse_args()
     if args.occupancy:
         return occupancy_sweep(args)
+    if args.mixed:
+        return mixed_sweep(args)
     if args.host:
         args.audio = "host"
     if args.pinned:
@@ -192,6 +202,62 @@ def occupancy_sweep(args):
     print(json.dumps({"streams": S, "fs": fs, "audio": "device", "async": True, "ticks": args.ticks,
                       "dense_ms_per_tick": float(np.median(dense)), "dense_all_ms_per_tick": dense,
                       "dense_tick_workgroup_rounds": aecm.describe_tick(S, cus)["rounds_x1000"] / 1000.0, "sparse": rows}))
+
+
+def mixed_sweep(args):
+    import numpy as np
+    import torch
+
+    import webrtc_aecm_amd as aecm
+    S, n = args.streams, 160
+    g = torch.Generator(device="cuda").manual_seed(1)
+    far = (torch.randn((S, n * 8), generator=g, device="cuda") * 3000).clamp_(-32768, 32767).to(torch.int16)
+    near = (far.roll(37, dims=1) // 3 + (torch.randn((S, n * 8), generator=g, device="cuda") * 200).to(torch.int16))
+    out = torch.empty_like(far)
+
+    def measure(objects):
+        """ms per tick of the clock, args.repeats times: objects = [(sessions, first row, samples per tick, ms or None, flags or None)],
+        ticked back to back, each past its start-up phase under the same arguments."""
+        def tick(i):
+            for sess, row, k, ms, flags in objects:
+                off = row * far.shape[1] * 2 + (i % 8) * k * 2
+                rc = sess.tick_async(far.data_ptr() + off, near.data_ptr() + off, out.data_ptr() + row * far.shape[1] * 2, far.shape[1], k, 40,
+                                     ms_per_session=ms, flags=flags)
+                assert rc == 0, rc
+        for i in range(40):
+            tick(i)
+        times = []
+        for r in range(args.repeats):
+            for o in objects:
+                assert o[0].synchronize() == 0
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(args.ticks):
+                tick(40 + i)
+            for o in objects:
+                assert o[0].synchronize() == 0
+            times.append((time.perf_counter() - t0) / args.ticks * 1e3)
+        for o in objects:
+            o[0].close()
+        return times
+
+    row = lambda name, times, **kw: dict(case=name, ms_per_tick=float(np.median(times)), all_ms_per_tick=times, **kw)
+    rows = [row("uniform 16 kHz / 160, no flags", measure([(aecm.AecmSessions(S, 16000, 1, 1), 0, 160, None, None)]))]
+    # the same uniform object handed the arrays the mixed rows hand over (msInSndCardBuf per session, flags that name nothing): what
+    # the host's passes over them and the two pinned copies cost -- the launches are those of the row above
+    rows.append(row("uniform 16 kHz / 160, ms and flags arrays", measure([(aecm.AecmSessions(S, 16000, 1, 1), 0, 160, np.full(S, 40, dtype=np.int16),
+                                                                          np.zeros(S, dtype=np.uint8))])))
+    for p in [float(x) for x in args.mixed.split(",")]:
+        narrow = np.zeros(S, dtype=bool)
+        narrow[np.random.default_rng(7).permutation(S)[:int(round(p / 100 * S))]] = True
+        rates = np.where(narrow, 8000, 16000).astype(np.int32)
+        flags = np.where(narrow, aecm.ffi.SESSION_HALF_CALL, 0).astype(np.uint8)
+        sess = aecm.AecmSessions(S, 16000, 1, 1, rates=rates)
+        rows.append(row(f"mixed {p:g} % 8 kHz half calls", measure([(sess, 0, 160, np.full(S, 40, dtype=np.int16), flags)]), narrowband=int(narrow.sum())))
+    half = S // 2
+    rows.append(row("two objects of S / 2: 8 kHz / 80 + 16 kHz / 160", measure([(aecm.AecmSessions(half, 8000, 1, 1), 0, 80, None, None),
+                                                                               (aecm.AecmSessions(S - half, 16000, 1, 1), half, 160, None, None)])))
+    print(json.dumps({"streams": S, "audio": "device", "async": True, "ticks": args.ticks, "rows": rows}))
 
 
 if __name__ == "__main__":

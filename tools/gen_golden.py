@@ -146,6 +146,27 @@ def main():
         out, codes, paths = sparse_helpers.drive_reference(lambda: pyoracle.RefSession(fs, 1, 3), fs, flags, ms, np.full(T, frame), far, near)
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, flags=flags, ms=ms, out=out, codes=codes.astype(np.int16), paths=paths)
         print("sesssparse", fs, frame, "live calls", int(((flags & 4) == 0).sum()), "of", T * S, sorted(set(codes.ravel().tolist())))
+    # Objects of mixed rates and call sizes (WebRtcAecmSessions_InitRates, AECM_SESSION_HALF_CALL; tests/mixed_helpers.py: the mixed
+    # run): every session on a reference instance of its own, initialised at ITS rate and called with ITS sizes.  Arrays only:
+    # the seed, the per-session rates, flags, msInSndCardBuf and burst calls of every tick, outputs, codes, final echo paths --
+    # once without and once with a clean input (the clean rows: synth_clean of the near rows).
+    import mixed_helpers as mh
+    for name, (seed, idle_p, with_bursts) in mh.GOLDEN_CASES.items():
+        if only and only not in name:
+            continue
+        flags, ms = mh.mixed_pattern(seed, idle_p=idle_p)
+        T, S = flags.shape
+        bursts = mh.burst_pattern(seed) if with_bursts else np.zeros((T, S), np.uint8)
+        burst_far = mh.burst_signals(seed)
+        far, near, clean = mh.signals(seed, mh.RATES, T * 160, with_clean=True)
+        make = lambda fs: pyoracle.RefSession(fs, 1, 3)
+        res = {}
+        for key, c in (("", None), ("_clean", clean)):
+            out, codes, paths, _, active = mh.drive_reference(make, mh.RATES, flags, ms, 160, far, near, c, bursts, burst_far)
+            res.update({"out" + key: out, "codes" + key: codes.astype(np.int16), "paths" + key: paths, "active_from" + key: active.astype(np.int16)})
+        np.savez_compressed(GOLD / f"{name}.npz", seed=seed, object_fs=mh.OBJECT_FS, rates=mh.RATES, flags=flags, ms=ms, bursts=bursts, **res)
+        print("sessmixed", name, "half calls", int((((flags & 8) != 0) & ((flags & 4) == 0)).sum()), "active from", res["active_from"].tolist(),
+              sorted(set(res["codes"].ravel().tolist())))
     from helpers import stream_config
     for name, S, nb, fs, seed0 in RAGGED_CASES:
         if only and only not in name:

@@ -625,6 +625,23 @@ int32_t WebRtcAecmSessions_ImportSession(AecmSessions *s, int32_t session, const
     return s->batch->ImportSession(session, snapshot);
 }
 
+int32_t WebRtcAecmSessions_ImportSessionAnyRate(AecmSessions *s, int32_t session, const void *snapshot, size_t size_bytes) {
+    if (!s) return -1;
+    if (!snapshot) return AECM_NULL_POINTER_ERROR;
+    if (size_bytes != aecm::SessionBatch::kSessionBytes) return AECM_BAD_PARAMETER_ERROR;
+    return s->batch->ImportSession(session, snapshot, true);
+}
+
+int32_t WebRtcAecmSessions_InitRates(AecmSessions *s, int32_t sampFreq, const int32_t *rates_host) { return s ? s->batch->InitRates(sampFreq, rates_host) : -1; }
+
+int32_t WebRtcAecmSessions_InitSessionRate(AecmSessions *s, int32_t session, int32_t sampFreq) {
+    return s ? s->batch->InitSessionRate(session, sampFreq) : -1;
+}
+
+int32_t WebRtcAecmSessions_GetSessionRate(AecmSessions *s, int32_t session, int32_t *sampFreq) {
+    return s ? s->batch->GetSessionRate(session, sampFreq) : -1;
+}
+
 int32_t WebRtcAecmSessions_set_config_session(AecmSessions *s, int32_t session, AecmConfig config) {
     return s ? s->batch->SetConfigSession(session, config.cngMode, config.echoMode) : -1;
 }

@@ -85,6 +85,8 @@ BatchEngine *BatchEngine::Create(int num_streams, int device_id) {
               AECM_HIP_OK(hipMalloc((void **)&e->st_.hist, S * kHistWordsPerStream * sizeof(uint16_t))) &&
               AECM_HIP_OK(hipMalloc((void **)&e->image_vec_dev_, kVecWordsPerStream * sizeof(uint32_t))) &&
               AECM_HIP_OK(hipMalloc((void **)&e->image_scal_dev_, kNumScal * sizeof(int32_t))) &&
+              AECM_HIP_OK(hipMalloc((void **)&e->other_vec_dev_, kVecWordsPerStream * sizeof(uint32_t))) &&
+              AECM_HIP_OK(hipMalloc((void **)&e->other_scal_dev_, kNumScal * sizeof(int32_t))) &&
               AECM_HIP_OK(hipMalloc((void **)&e->consts_dev_, kConstBlobWords * sizeof(uint32_t))) &&
               true;                                   // the timing events are created on first use (ProcessBlocks)
     if (ok) {
@@ -118,6 +120,9 @@ BatchEngine::~BatchEngine() {
     (void)hipFree(st_.hist);
     (void)hipFree(image_vec_dev_);
     (void)hipFree(image_scal_dev_);
+    (void)hipFree(other_vec_dev_);
+    (void)hipFree(other_scal_dev_);
+    (void)hipFree(select_dev_);
     (void)hipFree(consts_dev_);
     (void)hipFree(queue_ctl_);
     (void)hipFree(queue_err_);
@@ -134,9 +139,12 @@ BatchEngine::~BatchEngine() {
 }
 
 bool BatchEngine::Init(int fs) {
-    StreamImage img;
-    if (!BuildInitImage(fs, &img)) return false;
+    StreamImage img, other;
+    if (!BuildInitImage(fs, &img) || !BuildInitImage(fs == 8000 ? 16000 : 8000, &other)) return false;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
+    if (!AECM_HIP_OK(hipMemcpyAsync(other_vec_dev_, other.vec.data(), other.vec.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream_)) ||
+        !AECM_HIP_OK(hipMemcpyAsync(other_scal_dev_, other.scal.data(), other.scal.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream_)))
+        return false;
     if (!AECM_HIP_OK(hipMemcpyAsync(image_vec_dev_, img.vec.data(), img.vec.size() * sizeof(uint32_t),
                                     hipMemcpyHostToDevice, stream_)))
         return false;
@@ -149,7 +157,7 @@ bool BatchEngine::Init(int fs) {
     if (queue_err_ && !AECM_HIP_OK(hipMemsetAsync(queue_err_, 0, sizeof(uint32_t), stream_))) return false;
     queue_unchecked_ = false;
     launch_failed_ = false;
-    if (!AECM_HIP_OK(hipStreamSynchronize(stream_))) return false;   // img goes out of scope
+    if (!AECM_HIP_OK(hipStreamSynchronize(stream_))) return false;   // img and other go out of scope
     initialized_ = true;
     fs_ = fs;
     mixed_rates_ = false;
@@ -161,6 +169,28 @@ bool BatchEngine::InitStreams(int first, int count) {
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
     // image_*_dev_ still hold the initial image of the last Init
     return AECM_HIP_OK(LaunchBroadcastImage(st_, image_vec_dev_, image_scal_dev_, first, count, stream_));
+}
+
+bool BatchEngine::InitStreamsAtRate(int first, int count, int fs) {
+    if (fs == fs_) return InitStreams(first, count);
+    if (!initialized_ || (fs != 8000 && fs != 16000) || first < 0 || count < 0 || first + count > num_streams_) return false;
+    if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
+    if (count > 0) mixed_rates_ = true;
+    return AECM_HIP_OK(LaunchBroadcastImage(st_, other_vec_dev_, other_scal_dev_, first, count, stream_));
+}
+
+bool BatchEngine::InitStreamsOfOtherRate(const int32_t *rates_host) {
+    if (!initialized_) return false;
+    std::vector<uint8_t> select((size_t)num_streams_);
+    bool any = false;
+    for (int s = 0; s < num_streams_; ++s) any |= (select[(size_t)s] = rates_host[s] != fs_) != 0;
+    if (!any) return true;
+    if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
+    if (!select_dev_ && !AECM_HIP_OK(hipMalloc((void **)&select_dev_, (size_t)num_streams_))) { select_dev_ = nullptr; return false; }
+    mixed_rates_ = true;
+    return AECM_HIP_OK(hipMemcpyAsync(select_dev_, select.data(), select.size(), hipMemcpyHostToDevice, stream_)) &&
+           AECM_HIP_OK(LaunchBroadcastImageSelect(st_, other_vec_dev_, other_scal_dev_, select_dev_, num_streams_, stream_)) &&
+           AECM_HIP_OK(hipStreamSynchronize(stream_));      // select goes out of scope
 }
 
 // Stream-ordered, no synchronisation: the next launch on the engine's stream sees the new values.

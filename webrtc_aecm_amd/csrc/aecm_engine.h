@@ -144,6 +144,11 @@ public:
     // Re-initialise streams [first, first + count) only (same rate as the last Init; default config): WebRtcAecm_InitCore
     // + default set_config for those streams, asynchronous on stream().
     bool InitStreams(int first, int count);
+    // The same at a rate of the caller's choice (8000 / 16000: Init keeps the initial image of both rates on the device), and
+    // for the streams with rates_host[s] != fs() among all of them (one launch; rates_host: num_streams() entries, validated
+    // by the caller).  Streams of another rate than fs() make the engine one of mixed rates (ImportState).
+    bool InitStreamsAtRate(int first, int count, int fs);
+    bool InitStreamsOfOtherRate(const int32_t *rates_host);
     bool SetConfig(int cng_mode, int echo_mode, int first, int count);
     bool SetCngMode(int cng_mode, int first, int count);
     bool Control(int fixed_delay, int nlp_flag, int first, int count);
@@ -260,6 +265,9 @@ private:
     uint32_t *consts_dev_ = nullptr;     // kernel constants blob (aecm_state.h)
     uint32_t *image_vec_dev_ = nullptr;
     int32_t *image_scal_dev_ = nullptr;
+    uint32_t *other_vec_dev_ = nullptr;   // the initial image of the rate that is not fs_ (InitStreamsAtRate)
+    int32_t *other_scal_dev_ = nullptr;
+    uint8_t *select_dev_ = nullptr;       // [num_streams_] InitStreamsOfOtherRate's selection
     // Launch timing: a small ring of HIP event pairs recorded around every block-kernel launch on stream_.
     // ProcessBlocks only harvests pairs that have already completed (hipEventQuery) and waits for the oldest
     // one only when the ring is full, so launches queue back to back; the getters harvest everything.

@@ -68,6 +68,7 @@ constexpr int kFlowJitterCapacity = 50 * 80;        // kBufSizeSamp = BUF_SIZE_F
 constexpr int kFlowFarFrameRing = 256;              // ring of the framed far stream on the device (>= 143 + 80, power of two)
 constexpr int kFlowNoFarend = 1, kFlowSplitCalls = 2;   // = SessionBatch::kNoFarend / kSplitCalls
 constexpr int kFlowIdle = 4;                        // = SessionBatch::kIdle: the session makes no call at all in this tick (FlowIdleTick)
+constexpr int kFlowHalfCall = 8;                    // = SessionBatch::kHalfCall: one call pair of 80 samples in a 160-sample tick (FlowTickMixed)
 constexpr int kFlowFarRing = 8192;                  // far ring of the device: positions older than this many accepted samples are gone
 constexpr int kFlowOldAge = kFlowFarRing - 5 * kFlowFrame;   // a replay frame this far behind the write position moves to its row
 
@@ -365,6 +366,27 @@ inline FlowTickRoute FlowRouteTick(FlowObjectLag &o, int32_t live, int32_t n_ses
     return r;
 }
 
+// The same decision for an object that knows half calls (kFlowHalfCall) and sessions of another rate than its own.  Without
+// either -- half_calls: some session that calls in this tick makes a half call; other_rates: the object holds a session of
+// another rate -- it IS FlowRouteTick, and *mixed_plan is false: the launches of an object that knows neither.  Otherwise the
+// planning launch is the one that knows per-session rates, call sizes and lags (aecm_flow_plan_mixed_kernel; it does all the
+// sparse planning kernel does, so sparse_plan is true and it is handed deferred_lag), and a half call leaves its session 80
+// samples behind the object's near position: the object is out of step whoever else called.
+inline FlowTickRoute FlowRouteTickMixed(FlowObjectLag &o, int32_t live, int32_t n_sessions, int n, bool force_sparse, bool half_calls,
+                                        bool other_rates, bool *mixed_plan) {
+    FlowTickRoute r = FlowRouteTick(o, live, n_sessions, n, force_sparse);
+    *mixed_plan = r.launch && (half_calls || other_rates);
+    if (*mixed_plan) {
+        if (!r.sparse_plan) {                     // (everybody calls, everybody in step: nothing was deferred)
+            r.sparse_plan = true;
+            r.deferred_lag = o.deferred_lag;
+            o.deferred_lag = 0;
+        }
+        if (half_calls) o.may_lag = true;
+    }
+    return r;
+}
+
 // The live list of a tick in which sessions idle: the ids of the sessions that do call, ascending, so that wavefront w of
 // the tick kernel serves session live[w].  Built without atomics, in two halves.  The host half, in the pass over the flags
 // the host makes anyway: bases[b] = live sessions among the first kFlowPlanBlock * b, returns the live count.  The device
@@ -501,6 +523,45 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
             s.v[F_FF_VALID] = 1;
         }
     }
+}
+
+// One tick of a session of an object of mixed rates and call sizes (aecm_flow_plan_mixed_kernel): fs is the SESSION's rate;
+// with kFlowHalfCall (n = 160) the session makes one call pair of 80 samples on the first half of its rows -- the plan says one
+// call, one frame -- and the 80 samples of the tick it did not consume are 80 samples the object's near position runs ahead
+// of it: its lag, exactly as if it had sat out half a tick (FlowResync at its next call).  The tick kernel still appends all
+// of the tick's near-end samples at the object's position; the second half lands ahead of the session's own position, where
+// the next call's resync and append overwrite it before any block asks for it (tests/sim/sim_mixed.cpp).
+AECM_FLOW_HD void FlowTickMixed(FlowRegs &s, int fs, int n, int ms, int flags, uint32_t near_pos, FlowPlan &p) {
+    const bool half = (flags & kFlowHalfCall) != 0 && n == 2 * kFlowFrame;
+    FlowTick(s, fs, half ? kFlowFrame : n, ms, flags & (kFlowNoFarend | kFlowSplitCalls), near_pos, p);
+    if (half) s.v[F_NEAR_LAG] = FlowIdleTick(s.v[F_NEAR_LAG], kFlowFrame);
+}
+
+// The host's pass over a tick's flags (SessionBatch::Enqueue): FlowLiveBlockBases, and in the same pass what the sessions that
+// call ask for -- *any = the OR of their bytes, *half_and_split = some session carries kFlowHalfCall and kFlowSplitCalls together.
+inline int32_t FlowScanFlags(const uint8_t *flags, int32_t n_sessions, uint32_t *bases, uint8_t *any, bool *half_and_split) {
+    int32_t live = 0;
+    uint32_t any_bits = 0, both = 0;
+    for (int32_t first = 0, b = 0; first < n_sessions; first += kFlowPlanBlock, ++b) {
+        bases[b] = (uint32_t)live;
+        const int32_t end = first + kFlowPlanBlock < n_sessions ? first + kFlowPlanBlock : n_sessions;
+        int32_t idle = 0;
+        for (int32_t s = first; s < end; ++s) {
+            const uint32_t f = flags[s], is_idle = (f >> 2) & 1u, mine = f & (is_idle - 1u);     // an idle session's bits mean nothing
+            idle += (int32_t)is_idle;
+            any_bits |= mine;
+            both |= mine & (mine >> 2);                                                          // bit 1: split (2) and half (8) together
+        }
+        live += (end - first) - idle;
+    }
+    *any = (uint8_t)any_bits;
+    *half_and_split = (both & (uint32_t)kFlowSplitCalls) != 0;
+    return live;
+}
+static_assert(kFlowHalfCall >> 2 == kFlowSplitCalls, "FlowScanFlags lines the two bits up");
+// What a tick's flags may ask for: two calls of 80, or one call of 80 out of 160, need a tick of 160 samples, and exclude each other.
+inline bool FlowTickFlagsValid(int n, uint8_t any, bool half_and_split) {
+    return !(n != 2 * kFlowFrame && (any & (kFlowSplitCalls | kFlowHalfCall)) != 0) && !half_and_split;
 }
 
 // The plan as the kFlowPlanWords int32 the two kernels exchange.

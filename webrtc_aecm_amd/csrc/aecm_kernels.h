@@ -103,6 +103,10 @@ hipError_t LaunchProcessBlocksPipelinedRagged(const StatePtrs &st, const IoView 
 hipError_t LaunchBroadcastImage(const StatePtrs &st, const uint32_t *image_vec, const int32_t *image_scal,
                                 int first, int count, hipStream_t stream);
 
+// The same image into the streams s of [0, count) with select_dev[s] != 0 (device array), one launch.
+hipError_t LaunchBroadcastImageSelect(const StatePtrs &st, const uint32_t *image_vec, const int32_t *image_scal, const uint8_t *select_dev, int count,
+                                      hipStream_t stream);
+
 // Overwrite a few scalar fields (field ids from ScalField) of streams [first, first + count).  The fields travel as a
 // kernel argument: no staging copy, nothing for the host to wait for.
 constexpr int kMaxPatchFields = 16;
@@ -174,16 +178,20 @@ struct TickSparseIo {
     const uint32_t *block_base;        // [ceil(S / kFlowPlanBlock)] live sessions before each planning workgroup (with live)
     int32_t deferred_lag;              // added to every session's lag first: the ticks nobody made (no launch told the sessions)
 };
+// mixed_plan: the planning launch is aecm_flow_plan_mixed_kernel instead -- the same, with every session at its OWN rate (the
+// core state's S_MULT, not fio.fs) and kFlowHalfCall in the flags: one call pair of 80 samples in a 160-sample tick, after which
+// the session lags 80 samples (aecm_flow_plan.h: FlowTickMixed).  The tick launch is the same either way.
 hipError_t LaunchTickFlowSparse(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int live_count,
-                                hipStream_t stream);
+                                hipStream_t stream, bool mixed_plan = false);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront
 // per session.  Session s makes clamp(calls_per_session[s] - call_base, 0, max_calls) calls of io.n samples (max_calls each
 // when calls_per_session is null) on io.far_in[s][c * io.n .. + io.n): delay compensation when past the start-up phase, then
-// what fits into the jitter buffer goes to the far ring.  Of io only far_in / io_stride / n / far_ring / ring_len are used.
-hipError_t LaunchBufferFarend(const TickIo &io, const TickFlowIo &fio, const uint8_t *calls_per_session, int call_base, int max_calls, int n_streams,
-                              hipStream_t stream);
+// what fits into the jitter buffer goes to the far ring.  Of io only far_in / io_stride / n / far_ring / ring_len are used; every
+// session at its own rate (st.scal: S_MULT), not fio.fs.
+hipError_t LaunchBufferFarend(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const uint8_t *calls_per_session, int call_base, int max_calls,
+                              int n_streams, hipStream_t stream);
 // WebRtcAecm_Init of the wrapper side of sessions [first, first + count): wrapper state as after Init (aecm_flow_plan.h:
 // FlowFieldStartsAtOne), far / output rings, framed-far ring and replay rows reading as never written (zero).  Only the
 // ring pointers, ring_len and the state / far_frames / far_old pointers of io / fio are used.

@@ -38,16 +38,34 @@ hipError_t ReadCheckCounters(uint64_t counters[2], bool reset) {
 
 // ---- state maintenance ---------------------------------------------------------------------------
 
-__global__ void aecm_broadcast_image_kernel(StatePtrs st, const uint32_t *image_vec, const int32_t *image_scal,
-                                            int first, int count) {
-    const int64_t s = (int64_t)first + blockIdx.x;
-    if (blockIdx.x >= (unsigned)count) return;
+// One stream image (vec, scal) into stream s, far-spectrum history cleared: the work of one workgroup.
+__device__ __forceinline__ void WriteStreamImage(const StatePtrs &st, int64_t s, const uint32_t *image_vec, const int32_t *image_scal) {
     uint32_t *vec = st.vec + s * (int64_t)kVecWordsPerStream;
     for (int i = threadIdx.x; i < (int)kVecWordsPerStream; i += blockDim.x) vec[i] = image_vec[i];
     int32_t *scal = st.scal + s * (int64_t)kNumScal;
     for (int i = threadIdx.x; i < kNumScal; i += blockDim.x) scal[i] = image_scal[i];
     uint32_t *hist = reinterpret_cast<uint32_t *>(st.hist + s * (int64_t)kHistWordsPerStream);
     for (int i = threadIdx.x; i < (int)kHistWordsPerStream / 2; i += blockDim.x) hist[i] = 0u;
+}
+
+__global__ void aecm_broadcast_image_kernel(StatePtrs st, const uint32_t *image_vec, const int32_t *image_scal,
+                                            int first, int count) {
+    if (blockIdx.x >= (unsigned)count) return;
+    WriteStreamImage(st, (int64_t)first + blockIdx.x, image_vec, image_scal);
+}
+
+// The same for the streams select[s] != 0 among [0, count): WebRtcAecm_Init at another rate than the object's for some of
+// its sessions, in one launch over all of them (WebRtcAecmSessions_InitRates).
+__global__ void aecm_broadcast_image_select_kernel(StatePtrs st, const uint32_t *image_vec, const int32_t *image_scal, const uint8_t *select, int count) {
+    if (blockIdx.x >= (unsigned)count || !select[blockIdx.x]) return;
+    WriteStreamImage(st, (int64_t)blockIdx.x, image_vec, image_scal);
+}
+
+hipError_t LaunchBroadcastImageSelect(const StatePtrs &st, const uint32_t *image_vec, const int32_t *image_scal, const uint8_t *select_dev, int count,
+                                      hipStream_t stream) {
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(aecm_broadcast_image_select_kernel, dim3(count), dim3(256), 0, stream, st, image_vec, image_scal, select_dev, count);
+    return hipGetLastError();
 }
 
 hipError_t LaunchBroadcastImage(const StatePtrs &st, const uint32_t *image_vec, const int32_t *image_scal, int first,
@@ -275,6 +293,57 @@ void aecm_flow_plan_sparse_kernel(TickFlowIo fio, TickSparseIo sp, int n, unsign
     for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
 
+// The planning launch of a tick of an object of mixed rates / call sizes (aecm_flow_plan.h: FlowRouteTickMixed): the object holds
+// sessions of both rates, or a session makes a half call (kFlowHalfCall) in this tick.  Everything the sparse planning kernel
+// above does -- its text once more, so that THAT kernel stays, instruction for instruction, the kernel it was (the reason
+// aecm_tick_flow_body.inc gives for the tick kernels) -- except that the lane takes its session's rate from the core state
+// (scal = StatePtrs::scal, S_MULT: what the block engine itself goes by) instead of the object's, and plans with
+// FlowTickMixed: a half call is one call pair of 80 samples that leaves the session 80 samples behind.
+__device__ __forceinline__ void FlowPlanMixedBody(const TickFlowIo &fio, const TickSparseIo &sp, const int32_t *scal, int n, unsigned near_pos,
+                                                   int n_streams, uint32_t *wave_counts) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    const bool in_range = s < n_streams;
+    const int flags = !in_range ? kFlowIdle : fio.flags_per_session ? (int)fio.flags_per_session[s] : fio.flags;
+    const bool live = (flags & kFlowIdle) == 0;
+    if (sp.live) {                                                  // (uniform: a kernel argument)
+        const uint64_t ballot = __ballot(live);
+        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+        if (lane == 0) wave_counts[wave] = (uint32_t)__builtin_popcountll(ballot);
+        __syncthreads();
+        const uint32_t slot = FlowLiveSlot(sp.block_base[blockIdx.x], wave_counts, wave, ballot, lane);
+        if (live && slot < (uint32_t)n_streams) sp.live[slot] = (uint32_t)s;      // (the list holds n_streams entries)
+    }
+    if (!in_range) return;
+    int32_t *lag = fio.state + (size_t)F_NEAR_LAG * n_streams + s;
+    if (!live) {
+        *lag = FlowIdleTick(FlowIdleTick(*lag, sp.deferred_lag), n);
+        return;
+    }
+    FlowRegs r;
+    for (int k = 0; k < kFlowFieldsUsed; ++k) r.v[k] = fio.state[(size_t)k * n_streams + s];
+    r.v[F_NEAR_LAG] = FlowIdleTick(r.v[F_NEAR_LAG], sp.deferred_lag);
+    if (r.v[F_NEAR_LAG] != 0) {
+        FlowNearMove m;
+        FlowResync(r, near_pos, m);
+        const uint32_t mask = (uint32_t)sp.ring_len - 1u;
+        FlowMoveNear(sp.near_ring + (size_t)s * sp.ring_len, mask, m);
+        if (sp.clean_ring) FlowMoveNear(sp.clean_ring + (size_t)s * sp.ring_len, mask, m);
+    }
+    const int ms = fio.ms_per_session ? (int)fio.ms_per_session[s] : fio.ms;
+    FlowPlan p;
+    FlowTickMixed(r, scal[(size_t)s * kNumScal + S_MULT] == 2 ? 16000 : 8000, n, ms, flags, near_pos, p);
+    for (int k = 0; k < kFlowFieldsUsed; ++k) fio.state[(size_t)k * n_streams + s] = r.v[k];
+    int32_t w[kFlowPlanWords];
+    FlowPackPlan(p, w);
+    int4 *dst = reinterpret_cast<int4 *>(fio.plans + (size_t)s * kFlowPlanWords);
+    for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+}
+__global__ __launch_bounds__(256)
+void aecm_flow_plan_mixed_kernel(TickFlowIo fio, TickSparseIo sp, const int32_t *__restrict__ scal, int n, unsigned near_pos, int n_streams) {
+    __shared__ uint32_t wave_counts[kFlowPlanBlock / 64];
+    FlowPlanMixedBody(fio, sp, scal, n, near_pos, n_streams, wave_counts);
+}
+
 // Sessions per workgroup of the tick kernel.  A workgroup's waves are placed together, n / 4 per SIMD: with the 7 waves
 // per SIMD the kernel is built for (below), 8-wave workgroups can only ever fill 6 of the 7 slots, 4-wave workgroups all
 // of them -- at the price of one 20 KB table fill (from L2) per 4 sessions instead of per 8.  Measured, 65 536 sessions,
@@ -341,11 +410,14 @@ hipError_t LaunchTickFlow(const StatePtrs &st, const TickIo &io, const TickFlowI
 }
 
 hipError_t LaunchTickFlowSparse(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int live_count,
-                                hipStream_t stream) {
+                                hipStream_t stream, bool mixed_plan) {
     if (n_streams <= 0) return hipSuccess;
     if (live_count < 0 || live_count > n_streams || (sp.live && !sp.block_base)) return hipErrorInvalidValue;
     // the planning launch runs over ALL sessions (the idle ones count their lag); the tick launch over the live ones only
-    hipLaunchKernelGGL(aecm_flow_plan_sparse_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, fio, sp, io.n, (unsigned)io.near_pos, n_streams);
+    if (mixed_plan)
+        hipLaunchKernelGGL(aecm_flow_plan_mixed_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, fio, sp, st.scal, io.n, (unsigned)io.near_pos, n_streams);
+    else
+        hipLaunchKernelGGL(aecm_flow_plan_sparse_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, fio, sp, io.n, (unsigned)io.near_pos, n_streams);
     const dim3 block(64 * kTickFlowWaves);
     const size_t lds = sizeof(LdsTables);
     if (!sp.live) {                        // nobody idles in this tick (some had, before): everybody is live, the dense tick kernel
@@ -366,7 +438,8 @@ hipError_t LaunchTickFlowSparse(const StatePtrs &st, const TickIo &io, const Tic
 // clamp(calls_per_session[s] - call_base, 0, max_calls) calls (everybody max_calls without the array) on the samples
 // far_in[s][c * n .. + n), c = 0, 1, ...
 __global__ __launch_bounds__(256)
-void aecm_buffer_farend_kernel(TickIo io, TickFlowIo fio, const uint8_t *calls_per_session, int call_base, int max_calls, int n_streams) {
+void aecm_buffer_farend_kernel(TickIo io, TickFlowIo fio, const int32_t *__restrict__ scal, const uint8_t *calls_per_session, int call_base, int max_calls,
+                               int n_streams) {
     const int64_t s = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     if (s >= n_streams) return;
     const int lane = threadIdx.x & 63;
@@ -376,7 +449,8 @@ void aecm_buffer_farend_kernel(TickIo io, TickFlowIo fio, const uint8_t *calls_p
     if (calls <= 0) return;
     FlowRegs r;
     FlowBurstReads([&](int f) { r.v[f] = __builtin_amdgcn_readfirstlane(fio.state[(size_t)f * n_streams + s]); });
-    const int mask = (int)io.ring_len - 1, n = io.n, mult = fio.fs == 16000 ? 2 : 1;
+    // the session's own rate: the core state's (what the block engine goes by)
+    const int mask = (int)io.ring_len - 1, n = io.n, mult = __builtin_amdgcn_readfirstlane(scal[s * kNumScal + S_MULT]) == 2 ? 2 : 1;
     int16_t *fr = io.far_ring + s * io.ring_len, *old = fio.far_old + s * (2 * kFlowFrame);
     const int16_t *fin = io.far_in + s * io.io_stride;
     FlowBurst b;
@@ -400,10 +474,11 @@ void aecm_buffer_farend_kernel(TickIo io, TickFlowIo fio, const uint8_t *calls_p
     if (lane == 0) FlowBurstWrites([&](int f) { fio.state[(size_t)f * n_streams + s] = r.v[f]; });
 }
 
-hipError_t LaunchBufferFarend(const TickIo &io, const TickFlowIo &fio, const uint8_t *calls_per_session, int call_base, int max_calls, int n_streams,
-                              hipStream_t stream) {
+hipError_t LaunchBufferFarend(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const uint8_t *calls_per_session, int call_base, int max_calls,
+                              int n_streams, hipStream_t stream) {
     if (n_streams <= 0 || max_calls <= 0) return hipSuccess;
-    hipLaunchKernelGGL(aecm_buffer_farend_kernel, dim3((n_streams + 3) / 4), dim3(256), 0, stream, io, fio, calls_per_session, call_base, max_calls, n_streams);
+    hipLaunchKernelGGL(aecm_buffer_farend_kernel, dim3((n_streams + 3) / 4), dim3(256), 0, stream, io, fio, st.scal, calls_per_session, call_base, max_calls,
+                       n_streams);
     return hipGetLastError();
 }
 

@@ -87,7 +87,33 @@ int32_t SessionBatch::Init(int32_t samp_freq) {
     near_pos_ = 0;
     lag_ = FlowObjectLag();
     fs_ = samp_freq;
+    rates_.assign((size_t)S, samp_freq);
+    other_rates_ = 0;
     poisoned_ = false;
+    return 0;
+}
+
+int32_t SessionBatch::InitRates(int32_t samp_freq, const int32_t *rates) {
+    if (rates == nullptr) return AECM_NULL_POINTER_ERROR;
+    if (samp_freq != 8000 && samp_freq != 16000) return AECM_BAD_PARAMETER_ERROR;
+    const int S = engine_->num_streams();
+    for (int s = 0; s < S; ++s)
+        if (rates[s] != 8000 && rates[s] != 16000) return AECM_BAD_PARAMETER_ERROR;
+    if (int32_t rc = Init(samp_freq)) return rc;
+    if (!engine_->InitStreamsOfOtherRate(rates)) { fs_ = 0; return AECM_UNSPECIFIED_ERROR; }      // (the wrapper state knows no rate)
+    for (int s = 0; s < S; ++s) SetRate(s, rates[s]);
+    return 0;
+}
+
+void SessionBatch::SetRate(int session, int32_t fs) {
+    other_rates_ += (fs != fs_) - (rates_[(size_t)session] != fs_);
+    rates_[(size_t)session] = fs;
+}
+
+int32_t SessionBatch::GetSessionRate(int session, int32_t *samp_freq) const {
+    if (samp_freq == nullptr) return AECM_NULL_POINTER_ERROR;
+    if (int32_t rc = CheckSession(session)) return rc;
+    *samp_freq = rates_[(size_t)session];
     return 0;
 }
 
@@ -101,11 +127,16 @@ int32_t SessionBatch::CheckSession(int session) const {
 // WebRtcAecm_Init of ONE session (same sampling rate as the batch): fresh core state, fresh wrapper state, and rings
 // that read as never written (a fresh jitter buffer's read pointer can be moved back over never-written memory, the
 // output ring is stuffed from it: ring_buffer.c:75-82).
-int32_t SessionBatch::InitSession(int session) {
-    if (int32_t rc = CheckSession(session)) return rc;
+int32_t SessionBatch::InitSession(int session) { return InitSessionRate(session, fs_); }
+
+// The same at a rate of the caller's choice; the slot then runs at that rate (InitSession: back at the object's own).
+int32_t SessionBatch::InitSessionRate(int session, int32_t samp_freq) {
+    if (int32_t rc = CheckSession(session)) return rc;              // (an uninitialised object: fs_ == 0 never gets further)
+    if (samp_freq != 8000 && samp_freq != 16000) return AECM_BAD_PARAMETER_ERROR;
     // two launches, ordered before the next tick on the object's stream: no synchronisation with the host
-    const bool ok = AECM_HIP_OK(hipSetDevice(device_)) && engine_->InitStreams(session, 1) && ResetFlowRows(session, 1);
+    const bool ok = AECM_HIP_OK(hipSetDevice(device_)) && engine_->InitStreamsAtRate(session, 1, samp_freq) && ResetFlowRows(session, 1);
     if (!ok) { poisoned_ = true; return AECM_UNSPECIFIED_ERROR; }
+    SetRate(session, samp_freq);
     return 0;
 }
 
@@ -210,7 +241,7 @@ int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_
         bool ok = true;
         if (!host_pointers) {
             TickIo tio{far, nullptr, nullptr, nullptr, stride, n, far_ring_, nullptr, nullptr, nullptr, kRing, 0};
-            ok = AECM_HIP_OK(LaunchBufferFarend(tio, fio, calls_dev, 0, calls, S, st));
+            ok = AECM_HIP_OK(LaunchBufferFarend(engine_->state_ptrs(), tio, fio, calls_dev, 0, calls, S, st));
         } else {
             // host audio: staged through the ticks' device rows, as many calls per round as they hold
             const int per_round = (4 * 160) / n;
@@ -219,7 +250,7 @@ int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_
                 const size_t width = (size_t)round * n * 2;
                 ok = AECM_HIP_OK(hipMemcpy2DAsync(io_dev_, width, far + (size_t)base * n, (size_t)stride * 2, width, S, hipMemcpyHostToDevice, st));
                 TickIo tio{io_dev_, nullptr, nullptr, nullptr, (int64_t)round * n, n, far_ring_, nullptr, nullptr, nullptr, kRing, 0};
-                ok = ok && AECM_HIP_OK(LaunchBufferFarend(tio, fio, calls_dev, base, round, S, st));
+                ok = ok && AECM_HIP_OK(LaunchBufferFarend(engine_->state_ptrs(), tio, fio, calls_dev, base, round, S, st));
             }
         }
         if (!ok) return Fail();
@@ -259,12 +290,10 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     // flags: the live count, and per planning workgroup the live sessions before it (what the device needs for the live list).
     int live = S;
     uint8_t any = flags_per_session ? 0 : (uint8_t)flags;
-    if (flags_per_session) {
-        live = FlowLiveBlockBases(flags_per_session, S, live_bases_.data());
-        if (n != 160)
-            for (int s = 0; s < S; ++s) any |= (flags_per_session[s] & kIdle) ? 0 : flags_per_session[s];
-    }
-    if (n != 160 && (any & kSplitCalls)) return AECM_BAD_PARAMETER_ERROR;                 // two 80-sample calls need 160 samples
+    bool half_and_split = false;
+    if (flags_per_session) live = FlowScanFlags(flags_per_session, S, live_bases_.data(), &any, &half_and_split);
+    if (!FlowTickFlagsValid(n, any, half_and_split)) return AECM_BAD_PARAMETER_ERROR;     // two 80-sample calls, or 80 of 160, need 160 samples
+    const bool half_calls = flags_per_session && (any & kHalfCall) != 0;                  // some session that calls makes a half call
     const auto idle = [&](int s) { return flags_per_session && (flags_per_session[s] & kIdle) != 0; };
     if (live == 0) {
         // Nobody calls: nothing is launched.  The object's position moves on all the same; the sessions learn of it with the
@@ -352,23 +381,25 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         dout = io_dev_ + 2 * plane;
         if (clean) dclean = c;
         // whole planes travel back: the rows of sessions that sit out, which no kernel writes, as zeros
-        if (live < S && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * n * 2, st))) return fail();
+        // (and the second halves of the rows of sessions that make a half call)
+        if ((live < S || half_calls) && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * n * 2, st))) return fail();
     }
     TickIo tio{dfar, dnear, dclean, dout, dstride, n, far_ring_, near_ring_, clean_ring_, out_ring_, kRing, near_pos_};
     TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, ms_per_session ? ms_dev_[slot] : nullptr,
-                   flags_per_session ? flags_dev_[slot] : nullptr, ms, flags & (kNoFarend | kSplitCalls), fs_};
+                   flags_per_session ? flags_dev_[slot] : nullptr, ms, flags & (kNoFarend | kSplitCalls), fs_};      // (fs: the object's; mixed planning goes by the session's)
     if (wait_event && !AECM_HIP_OK(hipStreamWaitEvent(st, static_cast<hipEvent_t>(wait_event), 0))) {
         (void)hipGetLastError();
         return AECM_BAD_PARAMETER_ERROR;      // nothing of this tick has been enqueued (device pointers: no staging copies): no poison
     }
     bool ok;
-    const FlowTickRoute route = FlowRouteTick(lag_, live, S, n, force_sparse_);
+    bool mixed_plan;
+    const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, n, force_sparse_, half_calls, other_rates_ > 0, &mixed_plan);
     if (!route.sparse_plan) {
         ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
     } else {
         const TickSparseIo sp{near_ring_, clean_ring_, kRing, route.sparse_tick ? live_dev_ : nullptr, route.sparse_tick ? bases_dev_[slot] : nullptr,
                               route.deferred_lag};
-        ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, sp, S, live, st));
+        ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, sp, S, live, st, mixed_plan));
     }
     near_pos_ += n;
     if (!ok) return fail();
@@ -420,7 +451,7 @@ int32_t SessionBatch::ExportSession(int session, void *buf) {
     const int S = engine_->num_streams();
     const SessionOffsets at;
     uint8_t *p = static_cast<uint8_t *>(buf);
-    const SessionSnapshotHeader h{kSessionMagic, kSessionVersion, (uint32_t)fs_, clean_ring_ ? 1u : 0u, (uint32_t)kFlowWords, (uint32_t)kRing,
+    const SessionSnapshotHeader h{kSessionMagic, kSessionVersion, (uint32_t)rates_[(size_t)session], clean_ring_ ? 1u : 0u, (uint32_t)kFlowWords, (uint32_t)kRing,
                                   (uint32_t)kOutTail, (uint32_t)kNearTail};
     memcpy(p, &h, sizeof h);
     if (!engine_->ExportState(session, p + at.state)) return Fail();
@@ -449,14 +480,14 @@ int32_t SessionBatch::ExportSession(int session, void *buf) {
     return ok ? 0 : Fail();
 }
 
-int32_t SessionBatch::ImportSession(int session, const void *buf) {
+int32_t SessionBatch::ImportSession(int session, const void *buf, bool any_rate) {
     if (buf == nullptr) return AECM_NULL_POINTER_ERROR;
     if (int32_t rc = CheckSession(session)) return rc;
     const SessionOffsets at;
     const uint8_t *p = static_cast<const uint8_t *>(buf);
     SessionSnapshotHeader h;
     memcpy(&h, p, sizeof h);
-    if (h.magic != kSessionMagic || h.version != kSessionVersion || h.fs != (uint32_t)fs_ || h.has_clean > 1u || h.flow_words != (uint32_t)kFlowWords ||
+    if (h.magic != kSessionMagic || h.version != kSessionVersion || (any_rate ? h.fs != 8000u && h.fs != 16000u : h.fs != (uint32_t)fs_) || h.has_clean > 1u || h.flow_words != (uint32_t)kFlowWords ||
         h.far_ring != (uint32_t)kRing || h.out_tail != (uint32_t)kOutTail || h.near_tail != (uint32_t)kNearTail)
         return AECM_BAD_PARAMETER_ERROR;
     int32_t flow[kFlowWords];
@@ -486,6 +517,7 @@ int32_t SessionBatch::ImportSession(int session, const void *buf) {
     }
     // (ImportState validates the blob once more and is the first thing that writes)
     if (const int32_t rc = engine_->ImportState(session, p + at.state)) return rc;
+    SetRate(session, (int32_t)h.fs);
     // The session arrives in step with this object: its tail goes behind the object's near position, its lag is 0 -- behind
     // the position the device takes for the object's while all-idle ticks are still to be added to the lags, that is.
     flow[F_NEAR_LAG] = 0;

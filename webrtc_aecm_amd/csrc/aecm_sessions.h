@@ -27,6 +27,13 @@ public:
     BatchEngine *engine() { return engine_.get(); }
 
     int32_t Init(int32_t samp_freq);
+    // Sessions of both rates in one object.  samp_freq stays the OBJECT's rate (what InitSession and ImportSession mean by "the
+    // same rate"); every session runs at its own: on the device that is its core state's S_MULT (what the block engine, the
+    // mixed planning kernel and the burst kernel read), the host keeps a mirror for argument checks, snapshot headers and the
+    // launch routing (FlowRouteTickMixed: an object that holds a session of another rate plans every tick per session).
+    int32_t InitRates(int32_t samp_freq, const int32_t *rates);          // Init, then WebRtcAecm_Init(inst_k, rates[k]) where rates[k] differs: one launch
+    int32_t InitSessionRate(int session, int32_t samp_freq);             // InitSession at that rate
+    int32_t GetSessionRate(int session, int32_t *samp_freq) const;
     int32_t SetConfig(int16_t cng_mode, int16_t echo_mode);
     // Per-session control (a media server recycling one slot while the others keep running), reference
     // echo_control_mobile.cc:142-191 (WebRtcAecm_Init), :410-479 (set_config), :481-532 (Init/GetEchoPath).
@@ -70,7 +77,10 @@ public:
     int32_t BufferFarend(const int16_t *far, int64_t stream_stride, size_t n, int32_t calls, const uint8_t *calls_per_session, bool host_pointers,
                          bool wait, void *wait_event, void *done_event);
     int32_t Synchronize();
-    static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle;
+    //     bit 3 (kHalfCall, 160-sample ticks only, not with kSplitCalls) = this session makes ONE call pair of 80 samples, on the
+    //     first half of its rows; out[s][80..160) is not written (host pointers: zeros).  Its near-end position then lies 80
+    //     samples behind the object's: F_NEAR_LAG, as after half an idle tick (aecm_flow_plan.h: FlowTickMixed).
+    static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle, kHalfCall = kFlowHalfCall;
     // Diagnostics (tools/bench_sessions.py): every tick through the live list and the sparse tick kernel, idle sessions or
     // not -- what the indirection itself costs.
     void ForceSparseTicks(bool on) { force_sparse_ = on; }
@@ -94,7 +104,8 @@ public:
     static constexpr size_t kSessionBytes = kSessionHeaderBytes + BatchEngine::kStateBytes + kFlowWords * 4 + kFlowFarRing * 2 + kOutTail * 2 +
                                             2 * kNearTail * 2 + kFlowFarFrameRing * 2 + 2 * kFlowFrame * 2;
     int32_t ExportSession(int session, void *buf);
-    int32_t ImportSession(int session, const void *buf);
+    // any_rate: a snapshot of the other rate is taken too (ImportSessionAnyRate); the slot then runs at the snapshot's rate.
+    int32_t ImportSession(int session, const void *buf, bool any_rate = false);
 
 private:
     SessionBatch() {}
@@ -103,6 +114,9 @@ private:
     static constexpr int64_t kRing = kFlowFarRing;   // >= 4000 (jitter buffer) + a tick + the window a replayed frame may age in
     std::unique_ptr<BatchEngine> engine_;
     int fs_ = 0;                               // 0: not initialised
+    std::vector<int32_t> rates_;               // [S] every session's own rate (mirror of the core states' S_MULT)
+    int other_rates_ = 0;                      // sessions whose rate is not fs_
+    void SetRate(int session, int32_t fs);
     // A tick that failed on the device leaves the rings and the wrapper state out of step: every later call is refused
     // (AECM_UNSPECIFIED_ERROR) until Init.
     bool poisoned_ = false;

@@ -62,10 +62,13 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_ImportSession", "WebRtcAecmSessions_BufferFarend", "WebRtcAecmSessions_BufferFarendHost",
     "WebRtcAecmSessions_BufferFarendAsync", "WebRtcAecmSessions_Process", "WebRtcAecmSessions_ProcessHost", "WebRtcAecmSessions_DescribeTick",
     "WebRtcAecmSessions_DescribeTickLive", "WebRtcAecmSessions_ForceSparseTicks",
+    "WebRtcAecmSessions_InitRates", "WebRtcAecmSessions_InitSessionRate", "WebRtcAecmSessions_GetSessionRate",
+    "WebRtcAecmSessions_ImportSessionAnyRate",
 ]
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
 SESSION_IDLE = 4
+SESSION_HALF_CALL = 8
 
 
 class AecmConfig(C.Structure):
@@ -192,6 +195,10 @@ def load():
     lib.WebRtcAecmSessions_DescribeTick.argtypes = [C.c_int32, C.c_int32, C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmSessions_DescribeTickLive.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmSessions_ForceSparseTicks.argtypes = [vp, C.c_int32]
+    lib.WebRtcAecmSessions_InitRates.argtypes = [vp, C.c_int32, vp]
+    lib.WebRtcAecmSessions_InitSessionRate.argtypes = [vp, C.c_int32, C.c_int32]
+    lib.WebRtcAecmSessions_GetSessionRate.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.WebRtcAecmSessions_ImportSessionAnyRate.argtypes = [vp, C.c_int32, vp, C.c_size_t]
     lib.WebRtcAecm_SetDefaultDevice.argtypes = [C.c_int32]
     lib.WebRtcAecmSessions_Create.restype = vp
     lib.WebRtcAecmSessions_Create.argtypes = [C.c_int32, C.c_int32]
@@ -560,17 +567,18 @@ class AecmBatch:
 
 
 class AecmSessions:
-    """S streaming sessions with a common call cadence (include/aecm_batch.h, WebRtcAecmSessions_*)."""
+    """S streaming sessions on a common clock (include/aecm_batch.h, WebRtcAecmSessions_*).  rates: None (every session at fs), or
+    one rate per session (8000 / 16000; fs stays the object's own rate: WebRtcAecmSessions_InitRates)."""
 
-    def __init__(self, num_streams: int, fs: int = 16000, cng_mode: int = 1, echo_mode: int = 3, device: int = 0):
+    def __init__(self, num_streams: int, fs: int = 16000, cng_mode: int = 1, echo_mode: int = 3, device: int = 0, rates=None):
         self.lib = load()
         self.num_streams = num_streams
         self.h = self.lib.WebRtcAecmSessions_Create(num_streams, device)
         if not self.h:
             raise RuntimeError("WebRtcAecmSessions_Create failed: the HIP engine needs a usable MI355X (no CPU fallback exists)")
-        rc = self.lib.WebRtcAecmSessions_Init(self.h, fs)
+        rc = self.lib.WebRtcAecmSessions_Init(self.h, fs) if rates is None else self.init_rates(fs, rates)
         if rc != 0:
-            raise AecmError(rc, "WebRtcAecmSessions_Init")
+            raise AecmError(rc, "WebRtcAecmSessions_Init" if rates is None else "WebRtcAecmSessions_InitRates")
         rc = self.lib.WebRtcAecmSessions_set_config(self.h, AecmConfig(cng_mode, echo_mode))
         if rc != 0:
             raise AecmError(rc, "WebRtcAecmSessions_set_config")
@@ -604,8 +612,8 @@ class AecmSessions:
 
     def tick_host_per_session(self, far, near, ms_per_session, clean=None, flags=None):
         """far/near(/clean): [S, n] int16; ms_per_session: S msInSndCardBuf values; flags: S uint8 (SESSION_NO_FAREND,
-        SESSION_SPLIT_CALLS, SESSION_IDLE) or None.  Returns (code, out, codes[S]); the out row of a session that carries
-        SESSION_IDLE is zeros, its code 0."""
+        SESSION_SPLIT_CALLS, SESSION_IDLE, SESSION_HALF_CALL) or None.  Returns (code, out, codes[S]); the out row of a session
+        that carries SESSION_IDLE is zeros, its code 0; so is the second half of the row of one that carries SESSION_HALF_CALL."""
         far, near, clean, cptr = self._rows(far, near, clean)
         ms = np.ascontiguousarray(ms_per_session, dtype=np.int16)
         if ms.shape != (self.num_streams,):
@@ -679,6 +687,26 @@ class AecmSessions:
 
     def init_session(self, session: int) -> int:
         return self.lib.WebRtcAecmSessions_InitSession(self.h, session)
+
+    def init_rates(self, fs: int, rates) -> int:
+        """WebRtcAecmSessions_InitRates: Init(fs), then session k a fresh instance at rates[k] where that differs (config: the
+        default, as after WebRtcAecm_Init)."""
+        rates = np.ascontiguousarray(rates, dtype=np.int32)
+        if rates.shape != (self.num_streams,):
+            raise ValueError("rates must have one entry per session")
+        return self.lib.WebRtcAecmSessions_InitRates(self.h, fs, rates.ctypes.data)
+
+    def init_session_rate(self, session: int, fs: int) -> int:
+        return self.lib.WebRtcAecmSessions_InitSessionRate(self.h, session, fs)
+
+    def get_session_rate(self, session: int):
+        """(code, the session's own sampling rate)."""
+        fs = C.c_int32(0)
+        rc = self.lib.WebRtcAecmSessions_GetSessionRate(self.h, session, C.byref(fs))
+        return rc, fs.value
+
+    def import_session_any_rate(self, session: int, snapshot: bytes) -> int:
+        return self.lib.WebRtcAecmSessions_ImportSessionAnyRate(self.h, session, snapshot, len(snapshot))
 
     def set_config_session(self, session: int, cng_mode: int, echo_mode: int) -> int:
         return self.lib.WebRtcAecmSessions_set_config_session(self.h, session, AecmConfig(cng_mode, echo_mode))
