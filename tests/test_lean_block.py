@@ -1,0 +1,172 @@
+"""The lean block loop (aecm_wave.h: AECM_LEAN_BLOCK) on the lane simulator: the kernel source built with the lean forms on and
+off, both against the oracle in output samples and the 24-word state digest -- the bench signal, a double-talk and a silent
+stream, and the hostile inputs of the simulator tests (full scale, runs of -32768, silence, level steps).  The simulator
+libraries are built here, next to tests/_build/libaecm_sim.so, from the same sources with -DAECM_LEAN_POLICY_DEFAULT=0/1."""
+import ctypes as C
+import subprocess
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+import pytest
+
+import simlib
+from helpers import adversarial_cases, describe_digest_diff
+from oracle import pyoracle
+
+_i16p = np.ctypeslib.ndpointer(dtype=np.int16, flags="C_CONTIGUOUS")
+_u32p = np.ctypeslib.ndpointer(dtype=np.uint32, flags="C_CONTIGUOUS")
+_i64p = np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS")
+_SOURCES = [simlib.ROOT / "tests" / "sim" / "sim_lib.cpp", simlib.ROOT / "tests" / "sim" / "sim_lean.cpp", simlib.CSRC / "aecm_host_state.cpp"]
+_libs = {}
+# decisions counted by AECM_LEAN_COUNT (aecm_wave.h, process_binary)
+DECISIONS = {0: "valley above the minimum spread", 1: "min_prob above its lower limit (the test the lean form drops)",
+             2: "a new delay estimate is stored", 3: "step size: the quotient is below 8 (the early return's two ways in)"}
+# (The clamp of the candidate -- all 100 means at their maximum -- is the parent's own select, moved into the store; no signal
+# here or in the parent's tests reaches it, and it is no branch of the lean form's.)
+
+
+# bench.py's content profiles (its PROFILES table: far-end envelope levels, near-end talk levels, envelope segment), restated with
+# numpy so that the CPU suite has the bench signal without a GPU: white noise x a piecewise-constant envelope, smoothed, and a
+# sparse four-tap echo of it plus near-end talk bursts.
+BENCH_PROFILES = {"recipe": ([15., 60., 500., 3000., 9000., 20000.], [0., 0., 0., 2000., 8000.], 6400),
+                  "double_talk": ([2000., 30000.], [60000.], 128),
+                  "silent": ([0.], [0.], 6400)}
+
+
+def bench_pair(seed, n_blocks, profile="recipe"):
+    levels, talk, seg = BENCH_PROFILES[profile]
+    rs = np.random.RandomState(9000 + seed)
+    n = n_blocks * 64
+    nseg = n // seg + 2
+    env = np.repeat(np.asarray(levels)[rs.randint(0, len(levels), nseg)], seg)[:n]
+    x = rs.standard_normal(n) * env * 0.58
+    x[1:-1] = (x[:-2] + 2 * x[1:-1] + x[2:]) * 0.25
+    x = np.round(np.clip(x, -32768, 32767))
+    echo = np.zeros(n)
+    for d, gain in ((100, 0.5), (180, -0.3), (333, 0.2), (600, 0.1)):
+        echo[d:] += gain * x[:-d]
+    tenv = np.repeat(np.asarray(talk)[rs.randint(0, len(talk), nseg)], seg)[:n]
+    y = echo + rs.standard_normal(n) * tenv * 0.3
+    return x.astype(np.int16), np.round(np.clip(y, -32768, 32767)).astype(np.int16)
+
+
+def _lean_lib(lean):
+    """tests/_build/libaecm_sim_lean{0,1}.so: BlockEngine<SimWave, .> with the lean forms off / on, with decision counters."""
+    if lean in _libs:
+        return _libs[lean]
+    so = simlib.SIM_SO.parent / f"libaecm_sim_lean{lean}.so"
+    deps = _SOURCES + [simlib.ROOT / "tests" / "sim" / "wave_sim.h", simlib.CSRC / "aecm_wave.h", simlib.CSRC / "aecm_ops.h", simlib.CSRC / "aecm_state.h"]
+    if not so.exists() or any(so.stat().st_mtime < d.stat().st_mtime for d in deps):
+        so.parent.mkdir(parents=True, exist_ok=True)
+        obj_dir = so.parent / f".obj_lean{lean}"
+        obj_dir.mkdir(exist_ok=True)
+        flags = ["-O2", "-std=c++17", "-fwrapv", "-fPIC", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include", f"-I{simlib.CSRC}",
+                 f"-I{simlib.ROOT / 'tests' / 'sim'}", f"-DAECM_LEAN_POLICY_DEFAULT={lean}", "-DAECM_LEAN_COUNTERS"]
+
+        def compile_one(src):
+            obj = obj_dir / (Path(src).name + ".o")
+            subprocess.check_call(["g++", *flags, "-c", str(src), "-o", str(obj)])
+            return str(obj)
+        with ThreadPoolExecutor(max_workers=len(_SOURCES)) as ex:
+            objs = list(ex.map(compile_one, _SOURCES))
+        subprocess.check_call(["g++", "-shared", *objs, "-o", str(so)])
+    l = C.CDLL(str(so))
+    l.sim_create.restype = C.c_void_p
+    l.sim_create.argtypes = [C.c_int, C.c_int, C.c_int]
+    l.sim_free.argtypes = [C.c_void_p]
+    l.sim_set_echo_path.argtypes = [C.c_void_p, _i16p]
+    l.sim_process.argtypes = [C.c_void_p, _i16p, _i16p, C.c_void_p, _i16p, C.c_int]
+    l.sim_digest.argtypes = [C.c_void_p, _u32p]
+    l.sim_lean_counters.argtypes = [_i64p, C.c_int]
+    _libs[lean] = l
+    return l
+
+
+def _counters(l, reset=False):
+    c = np.zeros((8, 2), dtype=np.int64)
+    l.sim_lean_counters(c.reshape(-1), 1 if reset else 0)
+    return c
+
+
+def _run(l, fs, cng, em, far, near, path=None, launches=1):
+    h = l.sim_create(fs, cng, em)
+    assert h
+    try:
+        if path is not None:
+            l.sim_set_echo_path(h, np.ascontiguousarray(path, dtype=np.int16))
+        far, near = np.ascontiguousarray(far, dtype=np.int16), np.ascontiguousarray(near, dtype=np.int16)
+        out = np.empty_like(near)
+        n = near.size // 64
+        step = -(-n // launches)
+        for b in range(0, n, step):            # several launches: the state goes through store_state / load_state in between
+            e = min(n, b + step)
+            l.sim_process(h, far[b * 64:e * 64], near[b * 64:e * 64], None, out[b * 64:e * 64], e - b)
+        d = np.zeros(24, dtype=np.uint32)
+        l.sim_digest(h, d)
+        return out, d
+    finally:
+        l.sim_free(h)
+
+
+def _signal_cases():
+    """(name, fs, cng, echo_mode, far, near, echo path): 4 x 1 100 blocks of the bench signal (echo mode 1, as bench.py runs it; past the
+    1 024 blocks of start-up, where the step size is first computed), one double-talk and one silent stream, the second rate, and the hostile inputs of tests/test_sim.py."""
+    cases = []
+    for seed in range(4):
+        cases.append((f"recipe{seed}", 16000, 1, 1, *bench_pair(seed, 1100), None))
+    cases.append(("double_talk", 16000, 1, 1, *bench_pair(4, 1100, "double_talk"), None))
+    cases.append(("silent", 16000, 1, 1, *bench_pair(5, 400, "silent"), None))
+    cases.append(("recipe8k", 8000, 1, 3, *bench_pair(6, 400), None))
+    rs = np.random.RandomState(3)
+    n = 300 * 64
+    level = np.repeat(rs.choice([0, 1, 40, 3000, 32767], size=n // 64), 64).astype(np.int64)
+    steps = ((rs.randint(-32768, 32768, size=n).astype(np.int64) * level) >> 15).astype(np.int16)
+    runs = rs.randint(-32768, 32768, n).astype(np.int16)
+    runs[(np.arange(n) // 640) % 2 == 0] = -32768
+    hostile = [("zeros", np.zeros(n, np.int16), np.zeros(n, np.int16)),
+               ("all_min", np.full(n, -32768, np.int16), np.full(n, -32768, np.int16)),
+               ("full_scale_square", np.where(rs.randint(0, 2, n) == 1, 32767, -32768).astype(np.int16), rs.randint(-32768, 32768, n).astype(np.int16)),
+               ("silent_near", rs.randint(-32768, 32768, n).astype(np.int16), np.zeros(n, np.int16)),
+               ("runs_of_min", runs, np.roll(runs, 700)),
+               ("level_steps", steps, np.roll(steps, 130))]
+    for name, far, near in hostile:
+        cases.append((name, 16000, 1, 3, far, near, None))
+    for it, c in enumerate(adversarial_cases(n_cases=6, n_blocks=300)):
+        cases.append((f"adversarial{it}", c["fs"], c["cng"], c["echo_mode"], c["far"], c["near"], c["path"]))
+    return cases
+
+
+@pytest.fixture(scope="module")
+def oracle_results():
+    res = {}
+    for name, fs, cng, em, far, near, path in _signal_cases():
+        o = pyoracle.OracleStream(fs, cng, em)
+        if path is not None:
+            o.init_echo_path(path)
+        res[name] = (o.process(far, near), o.digest())
+    return res
+
+
+@pytest.mark.parametrize("lean", [0, 1])
+def test_lean_forms_on_and_off_equal_the_oracle(lean, oracle_results):
+    l = _lean_lib(lean)
+    _counters(l, reset=True)
+    for i, (name, fs, cng, em, far, near, path) in enumerate(_signal_cases()):
+        out, digest = _run(l, fs, cng, em, far, near, path, launches=1 + i % 3)
+        exp_out, exp_digest = oracle_results[name]
+        assert np.array_equal(out, exp_out), (lean, name, int(np.nonzero(out != exp_out)[0][0]) // 64)
+        assert np.array_equal(digest, exp_digest), (lean, name, describe_digest_diff(exp_digest, digest))
+    c = _counters(l)
+    if lean == 0:
+        assert not c.any(), "the parent's forms count nothing: the lean forms were compiled into the library built without them"
+    else:
+        for k, what in DECISIONS.items():
+            assert c[k, 0] > 0 and c[k, 1] > 0, f"decision {k} ({what}) went one way only: not taken {c[k, 0]}, taken {c[k, 1]}"
+
+
+def test_the_default_simulator_keeps_the_parents_forms():
+    """tests/_build/libaecm_sim.so (every other simulator test) is built without the switch: it must not have taken the lean forms."""
+    from webrtc_aecm_amd import build as B
+    text = (B.CSRC / "aecm_wave.h").read_text()
+    assert "#define AECM_LEAN_POLICY_DEFAULT 0" in text

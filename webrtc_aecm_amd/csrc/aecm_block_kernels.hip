@@ -172,7 +172,8 @@ __attribute__((amdgpu_waves_per_eu(AECM_WAVES_PER_EU, AECM_MAX_WAVES_PER_EU)))
 void aecm_process_queue_kernel(StatePtrs st, IoView io, int n_streams, int n_blocks, int chunk_blocks, int n_chunks, uint32_t *ctl,
                                uint32_t *err) {
     FillLdsTables<64 * kWavesPerWorkgroup>(st.consts);
-    using E = BlockEngine<Gfx950Wave<true, true, false, true>, kHasClean>;
+    // without a clean input this is the headline kernel: it and its ragged twin below take the lean block loop (BlockEngine::kLeanItems)
+    using E = BlockEngine<Gfx950Wave<true, true, false, true, !kHasClean>, kHasClean>;
     const uint32_t n_items = (uint32_t)n_streams * (uint32_t)n_chunks;
     uint32_t *done = ctl + kQueueCtlWords;
     for (;;) {
@@ -215,7 +216,9 @@ __global__ __launch_bounds__(64 * kWavesPerWorkgroup)
 __attribute__((amdgpu_waves_per_eu(AECM_WAVES_PER_EU, AECM_MAX_WAVES_PER_EU)))
 void aecm_process_ragged_queue_kernel(StatePtrs st, IoView io, int n_streams, uint32_t n_items, int chunk_blocks, uint32_t *ctl, uint32_t *err) {
     FillLdsTables<64 * kWavesPerWorkgroup>(st.consts);
-    using E = BlockEngine<Gfx950Wave<true, true, false, true>, kHasClean>;
+    // the same engine instantiation as aecm_process_queue_kernel's, as it always was (the compiler's inlining of the block loop
+    // into either kernel depends on the two sharing it): without a clean input the ragged queue takes the lean block loop too
+    using E = BlockEngine<Gfx950Wave<true, true, false, true, !kHasClean>, kHasClean>;
     uint32_t *done = ctl + kQueueCtlWords;
     const uint32_t *len = done + n_streams, *order = len + n_streams, *first_item = order + n_streams;      // written by the host before the launch
     uint32_t chunk = 0, chunk_first = 0;                                      // the cursor: first_item[chunk] <= every later claim of this wave

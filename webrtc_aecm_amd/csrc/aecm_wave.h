@@ -74,6 +74,29 @@
 #ifndef AECM_IFFT_GROUPED_SCALE_TESTS_CLEAN
 #define AECM_IFFT_GROUPED_SCALE_TESTS_CLEAN 2
 #endif
+// The lean block loop: forms of the scalar-heavy phases that issue fewer instructions per block (profiles/r18_experiments.md
+// has each item's estimate and measurement).  A bit mask, one bit per item, so that tools/ab_build.py can build any subset:
+//   1  delay estimator: the scalar tail of process_binary without its redundant test and its boolean masks
+//   2  suppression gain / far-energy filters: narrowings that are the identity dropped
+//   8  suppression gain, NLP average, step size: more narrowings that are the identity (each argued where it is dropped)
+//   4  comfort noise of bin 64: its table entry rides in lane 0 of the vector gather (bin 0 gets no comfort noise)
+// A kernel family takes them when its wave policy says so (W::kLean) AND it is not a W::kTight policy (the tick kernels, pinned
+// by tests/golden/tick_dense_fingerprints.json) AND it has no clean input: BlockEngine::kLeanItems.  No state, Regs or Uniform
+// member changes with the switch.  Policies without a kLean member (the lane simulator) follow AECM_LEAN_POLICY_DEFAULT.
+#ifndef AECM_LEAN_BLOCK
+#define AECM_LEAN_BLOCK 15
+#endif
+#ifndef AECM_LEAN_POLICY_DEFAULT
+#define AECM_LEAN_POLICY_DEFAULT 0
+#endif
+// Host builds with -DAECM_LEAN_COUNTERS (the lane simulator of tests/test_lean_block.py) count how often each data-dependent
+// decision of the lean forms goes either way: g_aecm_lean_counters[decision][outcome].  Nothing in every other build.
+#if defined(AECM_LEAN_COUNTERS) && !defined(__HIP_DEVICE_COMPILE__)
+extern "C" long long g_aecm_lean_counters[8][2];
+#define AECM_LEAN_COUNT(id, c) ((void)++g_aecm_lean_counters[id][(c) ? 1 : 0])
+#else
+#define AECM_LEAN_COUNT(id, c) ((void)0)
+#endif
 #if defined(__GNUC__)
 #define AECM_UNLIKELY(c) __builtin_expect(!!(c), 0)
 #define AECM_LIKELY(c) __builtin_expect(!!(c), 1)
@@ -134,10 +157,20 @@ struct Uniform {
     int reserved = 0;
 };
 
+// W::kLean where the policy has one, AECM_LEAN_POLICY_DEFAULT otherwise.
+template <class...> using lean_void_t = void;
+template <class W, class = void> struct PolicyLean { static constexpr bool value = AECM_LEAN_POLICY_DEFAULT != 0; };
+template <class W> struct PolicyLean<W, lean_void_t<decltype(W::kLean)>> { static constexpr bool value = W::kLean; };
+
 template <class W, bool kHasClean>
 struct BlockEngine {
     using vi = typename W::vi;
     using vb = typename W::vb;
+
+    // The lean block loop (AECM_LEAN_BLOCK): which items this instantiation takes.
+    static constexpr int kLeanItems = (!W::kTight && !kHasClean && PolicyLean<W>::value) ? (AECM_LEAN_BLOCK) : 0;
+    static constexpr bool kLeanDelayTail = (kLeanItems & 1) != 0, kLeanNarrowings = (kLeanItems & 2) != 0,
+                          kLeanNoise64 = (kLeanItems & 4) != 0, kLeanNarrowings2 = (kLeanItems & 8) != 0;
 
     // Joint scaling tests of the inverse transform (fft128): per kernel family, because the duplicated stage bodies cost
     // registers.
@@ -602,12 +635,16 @@ struct BlockEngine {
         vb nz0 = r.bh0 != 0, nz1 = r.bh1 != 0;                                     // far_bit_counts > 0
         // :623-626; combined on the scalar side (a ballot of the or-ed conditions makes the compiler turn the mask into
         // an integer per lane and compare it again)
-        bool any_far = (W::ballot(nz0) | (W::ballot(nz1) & ((uint64_t(1) << (kHistory - 64)) - 1))) != 0;
+        bool any_far = false;
+        if constexpr (!kLeanDelayTail) any_far = (W::ballot(nz0) | (W::ballot(nz1) & ((uint64_t(1) << (kHistory - 64)) - 1))) != 0;
         // The 100 means are Q9 values <= 32 << 9 = 2^14 and their update (:550-564, delay_estimator.cc:690-702) never
         // leaves 16 bits: slots t and t + 64 are advanced together as the two halves of one word (r.m01, the layout of the
         // V_M01 state word), with packed 16-bit instructions.  Upper halves of lanes >= 36 (no slot) stay 0: their far
         // bit count is masked to 0, which freezes them.
         const vi fb = popc(r.bh0) | shl(sel(valid1, popc(r.bh1), vi(0)), 16);                     // far_bit_counts
+        // lean: the far bit counts are non-zero exactly where a history word with a slot has a bit set -- one compare and one
+        // 64-bit test instead of two compares, a mask, an or and a test
+        if constexpr (kLeanDelayTail) any_far = W::ballot(fb != 0) != 0;
         const vi bc = pk_shl_b16(popc(r.bh0 ^ vi(near_word)) | shl(popc(r.bh1 ^ vi(near_word)), 16), vi(0x00090009));   // Q9
         const vi factor = pk_sub_i16(vi(0x000d000d), pk_lshr_b16(pk_mul_lo_u16(fb, vi(0x00030003)), vi(0x00040004)));   // 13 - (3 fb >> 4), 7..13
         const vi diff = pk_sub_i16(bc, r.m01);                                                    // |.| <= 2^14
@@ -620,6 +657,27 @@ struct BlockEngine {
         vi key1 = sel(valid1, shl(m1, 7) | (r.lane + 64), vi(0x7fffffff));
         int kmin, worst;
         W::reduce_min_max(imin(key0, key1), imax(m0, m1), kmin, worst);
+        if constexpr (kLeanDelayTail) {
+            // The same tail with less of it on the way through.  best is a minimum, the candidate is only formed where it is
+            // stored, and "min_prob > kProbLowerLimit" (:593) needs no test: thr >= kProbLowerLimit, so a
+            // min_prob at or below the limit is at or below thr and the minimum leaves it alone.
+            const int raw_best = kmin >> 7;
+            const int best = imin(raw_best, kMaxBitCountsQ9);
+            worst = imax(0, worst);
+            const int valley = worst - best;
+            const int lowered = imin(u.min_prob, imax(best + kProbOffset, kProbLowerLimit));  // :593-606
+            AECM_LEAN_COUNT(0, valley > kProbMinSpread);
+            if (valley > kProbMinSpread) AECM_LEAN_COUNT(1, u.min_prob > kProbLowerLimit);    // the test that went: both ways, same result
+            u.min_prob = valley > kProbMinSpread ? lowered : u.min_prob;
+            u.last_prob = add(u.last_prob, 1);                                       // :609
+            const bool valid = (valley > kProbOffset) & (best < imax(u.min_prob, u.last_prob));
+            AECM_LEAN_COUNT(2, any_far && valid);
+            if (any_far && valid) {                                                  // :643-661
+                u.last_delay = raw_best >= kMaxBitCountsQ9 ? -1 : (kmin & 127);
+                if (best < u.last_prob) u.last_prob = best;
+            }
+            return u.last_delay;
+        }
         int best = kmin >> 7, candidate = kmin & 127;
         if (best >= kMaxBitCountsQ9) { best = kMaxBitCountsQ9; candidate = -1; }
         worst = imax(0, worst);
@@ -644,7 +702,10 @@ struct BlockEngine {
     // where a branch costs more than the few instructions it skips.
     static AECM_HD int asym_filt(int old, int in, int step_pos, int step_neg) {      // :588-605
         const int d = in - old;                                                       // old, in are int16
-        const int up = sext16(old + sar(d, step_pos)), down = sext16(old - sar(-d, step_neg));
+        // lean: no narrowing.  The one of up / down that is taken lies between old and in (a shift moves d towards 0 and never
+        // past it), both of them int16: the reference's (int16_t) is the identity on it.
+        const int up = kLeanNarrowings ? old + sar(d, step_pos) : sext16(old + sar(d, step_pos));
+        const int down = kLeanNarrowings ? old - sar(-d, step_neg) : sext16(old - sar(-d, step_neg));
         const int filtered = d < 0 ? down : up;                                       // "old > in" is d < 0; d == 0: both are old
         // old == 32767 or old == -32768 (the initial values): for an int16 old, old + 32767 lies in [-1, 65534] and is above
         // 65533 as an unsigned number exactly for those two (one compare, no mask)
@@ -692,8 +753,14 @@ struct BlockEngine {
             u.fe_max = asym_filt(u.fe_max, u.far_log, inc_max, dec_max);
             u.fe_maxmin = sext16(u.fe_max - u.fe_min);
             int t16 = sext16(2560 - u.fe_min);
+            if constexpr (kLeanNarrowings2) {
+                // a positive int16 times 230 >> 9 is at most 14 719, plus 230: neither narrowing can change it, and a clamp at 0
+                // stands for the test (0 * 230 >> 9 == 0)
+                t16 = sar(imax(t16, 0) * kFarEnergyVadRegion, 9) + kFarEnergyVadRegion;
+            } else {
             t16 = t16 > 0 ? sext16(sar(t16 * kFarEnergyVadRegion, 9)) : 0;
             t16 = sext16(t16 + kFarEnergyVadRegion);
+            }
             if ((u.startup == 0) | (u.vad_cnt > 1024)) {
                 u.fe_vad = sext16(u.fe_min + t16);
             } else if (u.fe_vad > u.far_log) {
@@ -739,6 +806,7 @@ struct BlockEngine {
                 int q;
                 if (AECM_LIKELY(num >= 0 && den >= kMuDiff)) {
                     int rem = num;
+                    if constexpr (kLeanNarrowings2) AECM_LEAN_COUNT(3, rem < 8 * den);
                     q = 8;
                     if (rem < 8 * den) {
                         q = 0;
@@ -748,6 +816,8 @@ struct BlockEngine {
                         // comparison, the compiler turns the uniform boolean into an integer on the vector unit.
                         q += 1 + W::pin_uniform(sar(rem - den, 31));
                     }
+                    // lean: 0 <= q <= 8 here, so MU_MIN - 1 - q is in [1, 9]: no narrowing, no clamp to MU_MAX
+                    if constexpr (kLeanNarrowings2) return kMuMin - 1 - q;
                 } else {
                     q = sext16(divi(num, den));
                 }
@@ -857,14 +927,18 @@ struct BlockEngine {
         if (AECM_STEADY_NEVER(!cur_vad)) {
             sup = 0;
         } else {
-            int dE = sext16(iabs(sext16(near0 - stored0)));
+            // lean: near0 and stored0 are this block's log_energy_q8 values, inside [-10112, 9087] for every Q domain a valid state
+            // holds (aecm_state_check.h: <= 14): their difference and its magnitude are int16 without a narrowing
+            int dE = kLeanNarrowings ? iabs(near0 - stored0) : sext16(iabs(sext16(near0 - stored0)));
             if (dE < kEnergyDevTol) {
+                // lean: an int16 factor times a count of at most 200, plus 100, over 200: the quotient is an int16 as it stands
                 if (dE < kSupgainEpcDt) {
                     int t32 = u.sg_dab * dE + (kSupgainEpcDt >> 1);
-                    sup = sext16(u.sg_a - sext16(divi(t32, kSupgainEpcDt)));
+                    sup = kLeanNarrowings2 ? sext16(u.sg_a - divi(t32, kSupgainEpcDt)) : sext16(u.sg_a - sext16(divi(t32, kSupgainEpcDt)));
                 } else {
                     int t32 = u.sg_dbd * (kEnergyDevTol - dE) + ((kEnergyDevTol - kSupgainEpcDt) >> 1);
-                    sup = sext16(u.sg_d + sext16(divi(t32, kEnergyDevTol - kSupgainEpcDt)));
+                    sup = kLeanNarrowings2 ? sext16(u.sg_d + divi(t32, kEnergyDevTol - kSupgainEpcDt))
+                                           : sext16(u.sg_d + sext16(divi(t32, kEnergyDevTol - kSupgainEpcDt)));
                 }
             } else {
                 sup = u.sg_d;
@@ -872,7 +946,9 @@ struct BlockEngine {
         }
         int t16 = sup > u.sup_gain_old ? sup : u.sup_gain_old;
         u.sup_gain_old = sup;
-        u.sup_gain = sext16(u.sup_gain + sext16(sar(t16 - u.sup_gain, 4)));
+        // lean: supGain moves a sixteenth of the way towards t16, both int16 (supGain in [0, 32767]): it stays between them
+        if constexpr (kLeanNarrowings2) u.sup_gain = u.sup_gain + sar(t16 - u.sup_gain, 4);
+        else u.sup_gain = sext16(u.sup_gain + sext16(sar(t16 - u.sup_gain, 4)));
         return u.sup_gain;
     }
 
@@ -977,7 +1053,8 @@ struct BlockEngine {
     // increment below 2^11) can fire, which leaves one select between the tracking step down and the 1/2048 step up.
     // kSilent: the caller has established that the gain of every bin is ONE_Q14: the noise amplitude (ONE_Q14 - hnl) * est is 0
     // whatever the estimate (:142-147), so only the estimator moves and u_re, u_im are left alone.
-    template <class I, bool kTracking = false, bool kSilent = false>
+    // kNoLookup: without the phase table -- p_re is the amplitude times 8 and p_im the table index; comfort_noise does the rest.
+    template <class I, bool kTracking = false, bool kSilent = false, bool kNoLookup = false>
     static AECM_HD void noise_bin(BinState<I> &s, I dfa, I hnl, I rnd, I gate, int shift_n, int min_track, I &p_re, I &p_im) {
         I in = shl(dfa, shift_n);                                                             // :81-127
         auto lt = in < s.noise_est;
@@ -1017,16 +1094,24 @@ struct BlockEngine {
         // :153-156  uReal = (noise * cos) >> 13, uImag = (-noise * sin) >> 13 (|cos|, |sin| <= 2^13): with the amplitude times 8
         // (< 2^18) they are the upper halves of the two products, where a packed add takes them from (comfort_noise)
         const I n8 = shl(n16, 3);
+        if constexpr (kNoLookup) { p_re = n8; p_im = idx; return; }
         p_re = mul24(n8, W::cos360(idx));
         p_im = mul24(opaque_v(neg(n8)), W::sin360(idx));                  // opaque: a plain negation, not one redone in 24 bits
     }
+
+    // cos360 of lane 0's index as a wave-uniform value: the policy's own way where it has one (the device reads the table word out
+    // of lane 0 and narrows it on the scalar unit), else the lane vector's element.
+    template <class P>
+    static AECM_HD auto cos360_lane0(const vi &idx, const vi &, int) -> decltype(P::cos360_lane0(idx)) { return P::cos360_lane0(idx); }
+    template <class P>
+    static AECM_HD int cos360_lane0(const vi &, const vi &c, long) { return P::readlane(c, 0); }
 
     // ComfortNoise of the block (:52-164, called at :702-705) added to the suppressed spectrum (e = re | im << 16 of bins 0..63;
     // e_re64, e_im64).  kSilent: every gain is ONE_Q14, see noise_bin.
     template <bool kSilent>
     static AECM_HD void comfort_noise(Regs &r, const Spectrum &clean, vi hnl, int hnl64, vi &e, int &e_re64, int &e_im64) {
         Uniform &u = r.u;
-        int shift_n = sext16(15 - u.dfa_clean_q);
+        int shift_n = kLeanNarrowings2 ? 15 - u.dfa_clean_q : sext16(15 - u.dfa_clean_q);   // lean: a Q domain is 0 .. 14 (aecm_state_check.h)
         int min_track = 9;
         if (AECM_STEADY_NEVER(u.noise_ctr < 100)) { u.noise_ctr = sext16(u.noise_ctr + 1); min_track = 6; }
         // LCG jump-ahead: lane t gets the t-th of this block's 64 draws
@@ -1043,14 +1128,30 @@ struct BlockEngine {
         // every estimate at or above 2^11: the short form of the update (see noise_bin)
         const vi gate = lane_const<LC_NOT_BIN0>(r);                                    // 0 in lane 0, all ones elsewhere
         const bool tracking = kNoiseTrackingFastPath && (W::ballot(r.b.noise_est > vi(2047)) == ~0ull) & (r.b64.noise_est > 2047);
+        constexpr bool kShared = kLeanNoise64 && !kSilent;       // bin 64's table entry comes with the lanes' (below)
         if (AECM_STEADY_ALWAYS(AECM_LIKELY(tracking))) {
-            noise_bin<vi, true, kSilent>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
-            noise_bin<int, true, kSilent>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
+            noise_bin<vi, true, kSilent, kShared>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
+            noise_bin<int, true, kSilent, kShared>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
         } else {
-            noise_bin<vi, false, kSilent>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
-            noise_bin<int, false, kSilent>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
+            noise_bin<vi, false, kSilent, kShared>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
+            noise_bin<int, false, kSilent, kShared>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
         }
         if constexpr (kSilent) return;
+        if constexpr (kShared) {
+            // Bin 0 gets no comfort noise (its amplitude is masked to 0, noise_bin), so whatever lane 0 reads from the phase table
+            // is multiplied by 0: it reads bin 64's entry, which then leaves the vector unit with one v_readlane -- instead of a
+            // table read of its own (address move, LDS read) and a multiply, shift and saturating add on the vector unit.
+            const vi n8 = p_re, idx = W::writelane(p_im, p_im64, 0);
+            const vi c = W::cos360(idx);
+            p_re = mul24(n8, c);
+            p_im = mul24(opaque_v(neg(n8)), W::sin360(idx));
+            p_re64 = mul(p_re64, cos360_lane0<W>(idx, c, 0));       // < 2^18 times <= 2^13: exact
+            // the saturating add on the scalar unit: fused, it is a 16-bit v_add with clamp (a move in, a mask out: three vector slots)
+            e = pk_add_sat_i16(e, pack_hi16(p_re, p_im));
+            e_re64 = sat16(W::pin_uniform(e_re64 + sar(p_re64, 16)));
+            e_im64 = sat16(e_im64);
+            return;
+        }
         // :160-163  efw = AddSatW16(efw, u), real and imaginary part in one packed saturating add; bin 64: uImag = 0 (:158)
         e = pk_add_sat_i16(e, pack_hi16(p_re, p_im));
         e_re64 = sat16(e_re64 + sar(p_re64, 16));
@@ -1532,7 +1633,7 @@ struct BlockEngine {
             hnl = as_i16(sar(mul24(hnl, hnl), 14));
             hnl64 = sext16(sar(mul(hnl64, hnl64), 14));
             int avg = W::reduce_add(hnl & lane_const<LC_NLP_AVG_BAND>(r));          // bins 4..24
-            avg = sext16(divi(avg, 21));
+            avg = kLeanNarrowings2 ? divi(avg, 21) : sext16(divi(avg, 21));      // lean: the mean of 21 gains <= 2^14 is one
             // bins 24..63 are clamped to the average: 0 <= avg < 2^15, so for the bins below 24 avg | 0x7fff0000 is above every gain
             hnl = imin(hnl, vi(avg) | lane_const<LC_NLP_LOW_BINS>(r));
             if (hnl64 > avg) hnl64 = avg;

@@ -95,10 +95,13 @@ extern "C" __device__ int aecm_llvm_amdgcn_writelane(int value, int lane, int ol
 // launch (the chunk-queue kernel, aecm_block_kernels.hip): every access to it is a relaxed agent-scope atomic -- on gfx950
 // a plain global_load / global_store with the sc1 bit, which is served at the level all eight XCDs share instead of the
 // CU's L1 or the XCD's L2 -- and the scalars travel as one lane vector instead of through the (non-coherent) scalar cache.
-template <bool kFast, bool kPhasePrio = true, bool kTightRegisters = false, bool kCoherentState = false>
+// kLeanBlock: the kernel instantiating this policy takes the lean forms of the block loop (aecm_wave.h: AECM_LEAN_BLOCK).  Only
+// the two chunk-queue kernels without a clean input pass true; every other family keeps the text it was measured with.
+template <bool kFast, bool kPhasePrio = true, bool kTightRegisters = false, bool kCoherentState = false, bool kLeanBlock = false>
 struct Gfx950Wave {
     static constexpr bool kTight = kTightRegisters;
     static constexpr bool kCoherent = kCoherentState;
+    static constexpr bool kLean = kLeanBlock;
     using vi = int;
     using vb = bool;
     static constexpr bool kPrecomputedConstants = true;    // lane constants and LDS tables come from the host-built blob
@@ -244,6 +247,8 @@ struct Gfx950Wave {
     static __device__ __forceinline__ int cos360(int i) { return sext16(g_lds[0].cossin[i]); }
     static __device__ __forceinline__ int sin360(int i) { return g_lds[0].cossin[i] >> 16; }
 #endif
+    // cos360 of lane 0's index, wave-uniform: the table word the lanes' gather has fetched anyway, out of lane 0, narrowed on the scalar unit
+    static __device__ __forceinline__ int cos360_lane0(int i) { return sext16(__builtin_amdgcn_readlane(g_lds[0].cossin[i], 0)); }
 
     // ---- xor shuffles ----
     template <int M>
