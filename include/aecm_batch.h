@@ -322,6 +322,31 @@ size_t WebRtcAecmSessions_session_size_bytes(void);
 int32_t WebRtcAecmSessions_ExportSession(AecmSessions *s, int32_t session, void *snapshot, size_t size_bytes);
 int32_t WebRtcAecmSessions_ImportSession(AecmSessions *s, int32_t session, const void *snapshot, size_t size_bytes);
 
+/* The same for a LIST of sessions at once -- draining a GPU for maintenance, rebalancing calls between GPUs, checkpointing an
+ * object: one gather (scatter) launch on the device for the whole list instead of about ten blocking copies and a host pass
+ * per session.  sessions_host: count distinct session indices in [0, S), any order; NULL means 0 .. count-1.  snapshots: count
+ * snapshots of WebRtcAecmSessions_session_size_bytes() each, back to back, in list order (size_bytes = count x that).
+ *   Every snapshot is byte for byte what ExportSession of that session would have written at that moment; the exporting
+ * object is not changed.  All four calls are ordered behind the ticks and bursts already enqueued on the object's stream and
+ * return when their work is done.
+ *   The host forms stage through a grow-only device buffer of at most 256 snapshots (8.4 MiB): one copy per 256 sessions, the
+ * copy of each chunk ordered before the next gather.  The *Device forms take anything the device can address -- device memory
+ * (the staging buffer of a peer-to-peer migration) or the alias of a host buffer registered with
+ * WebRtcAecmBatch_RegisterHostBuffer -- 4-byte aligned; a 16-byte-aligned buffer moves 16 bytes per lane.  For
+ * ImportSessionsDevice the buffer must not change while the call runs.
+ *   ImportSessions is all or nothing: every snapshot is validated by ImportSession's rules (any_rate != 0:
+ * ImportSessionAnyRate's) before any slot is touched -- on the host for the host form, by a validation launch and one read-back
+ * for the *Device form; a refused list changes nothing.  After a successful import the object is exactly what `count` single
+ * imports would have left (session rates, the clean near-end ring).
+ *   count == 0: 0, nothing happens.  AECM_BAD_PARAMETER_ERROR (nothing changed): count < 0, another size_bytes, an index out of
+ * range, a duplicate in the list (export and import alike), a device pointer that is not 4-byte aligned, a snapshot
+ * ImportSession would refuse.  AECM_NULL_POINTER_ERROR: snapshots NULL with count > 0.  An uninitialised or poisoned object:
+ * as ExportSession. */
+int32_t WebRtcAecmSessions_ExportSessions(AecmSessions *s, const int32_t *sessions_host, int32_t count, void *snapshots_host, size_t size_bytes);
+int32_t WebRtcAecmSessions_ImportSessions(AecmSessions *s, const int32_t *sessions_host, int32_t count, const void *snapshots_host, size_t size_bytes, int32_t any_rate);
+int32_t WebRtcAecmSessions_ExportSessionsDevice(AecmSessions *s, const int32_t *sessions_host, int32_t count, void *snapshots_dev, size_t size_bytes);
+int32_t WebRtcAecmSessions_ImportSessionsDevice(AecmSessions *s, const int32_t *sessions_host, int32_t count, const void *snapshots_dev, size_t size_bytes, int32_t any_rate);
+
 /* Sessions of both sampling rates in ONE object -- one object per clock, not per rate: narrowband (8 kHz, 10 ms = 80 samples)
  * and wideband (16 kHz, 10 ms = 160 samples) calls tick together, a 160-sample tick with AECM_SESSION_HALF_CALL for the
  * sessions whose 10 ms are 80 samples.  Every session runs at its own rate wherever the reference looks at an instance's rate

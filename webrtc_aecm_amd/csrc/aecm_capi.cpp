@@ -632,6 +632,37 @@ int32_t WebRtcAecmSessions_ImportSessionAnyRate(AecmSessions *s, int32_t session
     return s->batch->ImportSession(session, snapshot, true);
 }
 
+static int32_t CheckSessionsBulk(const AecmSessions *s, int32_t count, const void *snapshots, size_t size_bytes) {
+    if (!s) return -1;
+    if (count < 0) return AECM_BAD_PARAMETER_ERROR;
+    if (count == 0) return 0;
+    if (!snapshots) return AECM_NULL_POINTER_ERROR;
+    if (size_bytes != (size_t)count * aecm::SessionBatch::kSessionBytes) return AECM_BAD_PARAMETER_ERROR;
+    return 0;
+}
+
+int32_t WebRtcAecmSessions_ExportSessions(AecmSessions *s, const int32_t *sessions_host, int32_t count, void *snapshots_host, size_t size_bytes) {
+    if (int32_t rc = CheckSessionsBulk(s, count, snapshots_host, size_bytes)) return rc;
+    return s->batch->ExportSessions(sessions_host, count, snapshots_host, false);
+}
+
+int32_t WebRtcAecmSessions_ImportSessions(AecmSessions *s, const int32_t *sessions_host, int32_t count, const void *snapshots_host, size_t size_bytes,
+                                          int32_t any_rate) {
+    if (int32_t rc = CheckSessionsBulk(s, count, snapshots_host, size_bytes)) return rc;
+    return s->batch->ImportSessions(sessions_host, count, snapshots_host, false, any_rate != 0);
+}
+
+int32_t WebRtcAecmSessions_ExportSessionsDevice(AecmSessions *s, const int32_t *sessions_host, int32_t count, void *snapshots_dev, size_t size_bytes) {
+    if (int32_t rc = CheckSessionsBulk(s, count, snapshots_dev, size_bytes)) return rc;
+    return s->batch->ExportSessions(sessions_host, count, snapshots_dev, true);
+}
+
+int32_t WebRtcAecmSessions_ImportSessionsDevice(AecmSessions *s, const int32_t *sessions_host, int32_t count, const void *snapshots_dev, size_t size_bytes,
+                                                int32_t any_rate) {
+    if (int32_t rc = CheckSessionsBulk(s, count, snapshots_dev, size_bytes)) return rc;
+    return s->batch->ImportSessions(sessions_host, count, snapshots_dev, true, any_rate != 0);
+}
+
 int32_t WebRtcAecmSessions_InitRates(AecmSessions *s, int32_t sampFreq, const int32_t *rates_host) { return s ? s->batch->InitRates(sampFreq, rates_host) : -1; }
 
 int32_t WebRtcAecmSessions_InitSessionRate(AecmSessions *s, int32_t session, int32_t sampFreq) {

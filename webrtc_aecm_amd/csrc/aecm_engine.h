@@ -211,6 +211,9 @@ public:
     // blobs) before any stream is touched.
     bool ExportStates(int first, int count, void *states, bool device);
     int32_t ImportStates(int first, int count, const void *states, bool device);
+    // The session batch scattered a core state of another rate than fs() into a stream itself (bulk session import): what
+    // ImportState notes when it brings one in.
+    void NoteStreamOfOtherRate() { mixed_rates_ = true; }
     void set_variant(int v) { switches_.variant = v; }
     // blocks = 0: every launch in the one-stream-per-wave form.  min_streams < 0: launches of more streams than the chip
     // holds waves take the queue form (the default); otherwise launches of more than min_streams streams do (tests).

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/echo_control_mobile.h"
+#include "aecm_session_snapshot.h"
 #include "aecm_state_check.h"
 
 namespace aecm {
@@ -61,6 +62,9 @@ SessionBatch::~SessionBatch() {
     (void)hipFree(far_frames_);
     (void)hipFree(far_old_);
     (void)hipFree(live_dev_);
+    (void)hipFree(snap_list_);
+    (void)hipFree(snap_stage_);
+    (void)hipFree(snap_verdict_);
     for (int k = 0; k < kArgSlots; ++k) {
         if (bases_host_[k]) (void)hipHostFree(bases_host_[k]);
         if (ms_host_[k]) (void)hipHostFree(ms_host_[k]);
@@ -429,20 +433,10 @@ int32_t SessionBatch::TickAsync(const int16_t *far, const int16_t *near, const i
 }
 
 // ---- session snapshots ---------------------------------------------------------------------------------
-namespace {
-struct SessionSnapshotHeader {
-    uint32_t magic, version, fs, has_clean, flow_words, far_ring, out_tail, near_tail;
-};
-constexpr uint32_t kSessionMagic = 0x4e534541u;       // "AESN"
-constexpr uint32_t kSessionVersion = 1;               // bump with aecm_flow_plan.h's field list or the layout below
-static_assert(sizeof(SessionSnapshotHeader) == SessionBatch::kSessionHeaderBytes, "session snapshot header");
-struct SessionOffsets {                                // byte offsets of the parts behind the header
-    size_t state = SessionBatch::kSessionHeaderBytes, flow = state + BatchEngine::kStateBytes, far = flow + kFlowWords * 4,
-           out = far + kFlowFarRing * 2, near = out + SessionBatch::kOutTail * 2, clean = near + SessionBatch::kNearTail * 2,
-           frames = clean + SessionBatch::kNearTail * 2, old = frames + kFlowFarFrameRing * 2, end = old + 2 * kFlowFrame * 2;
-};
-static_assert(SessionOffsets().end == SessionBatch::kSessionBytes, "session snapshot size");
-}  // namespace
+// The layout (header, offsets of the parts) and its one statement for host and device: aecm_session_snapshot.h.
+static_assert(kSessionHeaderBytes == SessionBatch::kSessionHeaderBytes && kSessionBytes == SessionBatch::kSessionBytes &&
+                  kSessionOutTail == SessionBatch::kOutTail && kSessionNearTail == SessionBatch::kNearTail && kStateBlobBytes == BatchEngine::kStateBytes,
+              "session snapshot size");
 
 int32_t SessionBatch::ExportSession(int session, void *buf) {
     if (buf == nullptr) return AECM_NULL_POINTER_ERROR;
@@ -540,6 +534,135 @@ int32_t SessionBatch::ImportSession(int session, const void *buf, bool any_rate)
     ok = ok && AECM_HIP_OK(hipMemcpy(far_frames_ + (size_t)session * kFlowFarFrameRing, p + at.frames, kFlowFarFrameRing * 2, hipMemcpyHostToDevice)) &&
          AECM_HIP_OK(hipMemcpy(far_old_ + (size_t)session * 2 * kFlowFrame, p + at.old, 2 * kFlowFrame * 2, hipMemcpyHostToDevice));
     return ok ? 0 : Fail();           // a session half written is not a session: the object is poisoned
+}
+
+// ---- bulk session snapshots: a list of sessions, one or two launches, no per-session host work ---------------
+SessionView SessionBatch::View() const {
+    return SessionView{engine_->state_ptrs(), flow_state_, (int64_t)engine_->num_streams(), far_ring_, near_ring_, clean_ring_, out_ring_,
+                       far_frames_, far_old_, (uint32_t)near_pos_, lag_.deferred_lag};
+}
+
+// In range and distinct, or nothing is touched.
+int32_t SessionBatch::CheckSessionList(const int32_t *sessions, int count) const {
+    const int S = engine_->num_streams();
+    if (count > S) return AECM_BAD_PARAMETER_ERROR;          // (more entries than sessions: out of range without a list, a duplicate with one)
+    if (!sessions) return 0;
+    std::vector<uint8_t> seen((size_t)S, 0);
+    for (int i = 0; i < count; ++i) {
+        if (sessions[i] < 0 || sessions[i] >= S || seen[(size_t)sessions[i]]) return AECM_BAD_PARAMETER_ERROR;
+        seen[(size_t)sessions[i]] = 1;
+    }
+    return 0;
+}
+
+bool SessionBatch::EnsureSnapshotBuffers(int list_entries, int stage_sessions, int info_words) {
+    const auto grow = [&](void **buf, size_t *have, size_t need, size_t unit) {
+        if (need <= *have) return true;
+        if (!AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return false;      // (nothing enqueued may still use the old one)
+        (void)hipFree(*buf);
+        *buf = nullptr;
+        *have = 0;
+        if (!AECM_HIP_OK(hipMalloc(buf, need * unit))) { *buf = nullptr; return false; }
+        *have = need;
+        return true;
+    };
+    return grow((void **)&snap_list_, &snap_list_entries_, (size_t)list_entries, sizeof(int32_t)) &&
+           grow((void **)&snap_stage_, &snap_stage_bytes_, (size_t)std::min(stage_sessions, kSnapshotStageSessions) * kSessionBytes, 1) &&
+           grow((void **)&snap_verdict_, &snap_verdict_words_, info_words > 0 ? (size_t)info_words + 1 : 0, sizeof(uint32_t));
+}
+
+int32_t SessionBatch::ExportSessions(const int32_t *sessions, int count, void *snapshots, bool device) {
+    if (count < 0) return AECM_BAD_PARAMETER_ERROR;
+    if (count == 0) return 0;
+    if (snapshots == nullptr) return AECM_NULL_POINTER_ERROR;
+    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (poisoned_) return AECM_UNSPECIFIED_ERROR;
+    if (int32_t rc = CheckSessionList(sessions, count)) return rc;
+    if (device && (reinterpret_cast<uintptr_t>(snapshots) & 3)) return AECM_BAD_PARAMETER_ERROR;      // the kernels move 32-bit words at least
+    if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
+    if (!EnsureSnapshotBuffers(sessions ? count : 0, device ? 0 : count, 0)) return AECM_UNSPECIFIED_ERROR;
+    hipStream_t st = engine_->stream();
+    if (sessions && !AECM_HIP_OK(hipMemcpyAsync(snap_list_, sessions, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st))) return Fail();
+    const SessionView view = View();
+    bool ok = true;
+    if (device) {
+        ok = AECM_HIP_OK(LaunchGatherSessions(view, sessions ? snap_list_ : nullptr, 0, count, snapshots, (reinterpret_cast<uintptr_t>(snapshots) & 15) == 0, st));
+    } else {
+        uint8_t *dst = static_cast<uint8_t *>(snapshots);
+        for (int s0 = 0; s0 < count && ok; s0 += kSnapshotStageSessions) {            // the copy of a chunk is ordered before the next gather
+            const int n = std::min(kSnapshotStageSessions, count - s0);
+            ok = AECM_HIP_OK(LaunchGatherSessions(view, sessions ? snap_list_ + s0 : nullptr, s0, n, snap_stage_, true, st)) &&
+                 AECM_HIP_OK(hipMemcpyAsync(dst + (size_t)s0 * kSessionBytes, snap_stage_, (size_t)n * kSessionBytes, hipMemcpyDeviceToHost, st));
+        }
+    }
+    if (!ok || !AECM_HIP_OK(hipStreamSynchronize(st))) return Fail();
+    return 0;
+}
+
+int32_t SessionBatch::ImportSessions(const int32_t *sessions, int count, const void *snapshots, bool device, bool any_rate) {
+    if (count < 0) return AECM_BAD_PARAMETER_ERROR;
+    if (count == 0) return 0;
+    if (snapshots == nullptr) return AECM_NULL_POINTER_ERROR;
+    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (poisoned_) return AECM_UNSPECIFIED_ERROR;
+    if (int32_t rc = CheckSessionList(sessions, count)) return rc;
+    if (device && (reinterpret_cast<uintptr_t>(snapshots) & 3)) return AECM_BAD_PARAMETER_ERROR;
+    if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
+    if (!EnsureSnapshotBuffers(sessions ? count : 0, device ? 0 : count, device ? count : 0)) return AECM_UNSPECIFIED_ERROR;
+    hipStream_t st = engine_->stream();
+    const bool wide = (reinterpret_cast<uintptr_t>(snapshots) & 15) == 0;
+    const uint8_t *src = static_cast<const uint8_t *>(snapshots);
+    // All or nothing: every snapshot before any slot.  info[i] = rate | has_clean << 31 of snapshot i.
+    std::vector<uint32_t> info((size_t)count + 1);
+    if (device) {
+        static const uint32_t preset = 0xffffffffu;           // the verdict word; the info words follow it
+        if (!AECM_HIP_OK(hipMemcpyAsync(snap_verdict_, &preset, sizeof preset, hipMemcpyHostToDevice, st)) ||
+            !AECM_HIP_OK(LaunchValidateSessions(snapshots, count, fs_, any_rate, snap_verdict_, snap_verdict_ + 1, st)) ||
+            !AECM_HIP_OK(hipMemcpyAsync(info.data(), snap_verdict_, ((size_t)count + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) ||
+            !AECM_HIP_OK(hipStreamSynchronize(st))) {
+            (void)hipStreamSynchronize(st);                   // (the read-back into `info` may still be in flight)
+            return AECM_UNSPECIFIED_ERROR;                    // nothing of the object has been written: no poison
+        }
+        if (info[0] != 0xffffffffu) return AECM_BAD_PARAMETER_ERROR;
+    } else {
+        for (int i = 0; i < count; ++i) {
+            const uint8_t *blob = src + (size_t)i * kSessionBytes;
+            for (int t = 0; t < kLanes; ++t)
+                if (SessionBlobDefect(blob, fs_, any_rate, t) != 0) return AECM_BAD_PARAMETER_ERROR;
+            info[(size_t)i + 1] = SessionBlobWord(blob, 0, 2) | (SessionBlobWord(blob, 0, 3) << 31);
+        }
+    }
+    const int S = engine_->num_streams();
+    bool has_clean = false, other_rate = false;
+    for (int i = 0; i < count; ++i) {
+        has_clean = has_clean || (info[(size_t)i + 1] >> 31) != 0;
+        other_rate = other_rate || (int32_t)(info[(size_t)i + 1] & 0x7fffffffu) != fs_;
+    }
+    if (has_clean && !clean_ring_) {                        // as the first tick that carries a clean near end would
+        const size_t bytes = (size_t)S * kRing * 2;
+        if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
+        if (!AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, st))) {
+            (void)hipFree(clean_ring_);
+            clean_ring_ = nullptr;
+            return Fail();
+        }
+    }
+    if (sessions && !AECM_HIP_OK(hipMemcpyAsync(snap_list_, sessions, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st))) return Fail();
+    const SessionView view = View();
+    bool ok = true;
+    if (device) {
+        ok = AECM_HIP_OK(LaunchScatterSessions(view, sessions ? snap_list_ : nullptr, 0, count, snapshots, wide, st));
+    } else {
+        for (int s0 = 0; s0 < count && ok; s0 += kSnapshotStageSessions) {            // the scatter of a chunk is ordered before the next copy
+            const int n = std::min(kSnapshotStageSessions, count - s0);
+            ok = AECM_HIP_OK(hipMemcpyAsync(snap_stage_, src + (size_t)s0 * kSessionBytes, (size_t)n * kSessionBytes, hipMemcpyHostToDevice, st)) &&
+                 AECM_HIP_OK(LaunchScatterSessions(view, sessions ? snap_list_ + s0 : nullptr, s0, n, snap_stage_, true, st));
+        }
+    }
+    if (!ok || !AECM_HIP_OK(hipStreamSynchronize(st))) return Fail();      // sessions half written are no sessions: the object is poisoned
+    for (int i = 0; i < count; ++i) SetRate(sessions ? sessions[i] : i, (int32_t)(info[(size_t)i + 1] & 0x7fffffffu));
+    if (other_rate) engine_->NoteStreamOfOtherRate();
+    return 0;
 }
 
 int32_t SessionBatch::Synchronize() {

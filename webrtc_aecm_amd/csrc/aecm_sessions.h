@@ -19,6 +19,8 @@
 
 namespace aecm {
 
+struct SessionView;      // aecm_session_snapshot.h
+
 class SessionBatch {
 public:
     static SessionBatch *Create(int num_streams, int device_id);
@@ -106,6 +108,18 @@ public:
     int32_t ExportSession(int session, void *buf);
     // any_rate: a snapshot of the other rate is taken too (ImportSessionAnyRate); the slot then runs at the snapshot's rate.
     int32_t ImportSession(int session, const void *buf, bool any_rate = false);
+    // The same for a LIST of sessions (draining or rebalancing a GPU, checkpointing an object): `sessions` = count distinct
+    // indices in any order (host array; null: 0 .. count - 1), `snapshots` = count snapshots of kSessionBytes back to back in list
+    // order -- host memory, or (device = true) anything the device can address, 4-byte aligned (16-byte aligned: the kernels move
+    // 16 bytes per lane).  One gather (scatter) launch for the whole list instead of about ten blocking copies per session
+    // (aecm_session_snapshot.h); the host forms stage through a grow-only device buffer of at most kSnapshotStageSessions
+    // snapshots, one copy per chunk.  Every snapshot is byte for byte ExportSession's.  ImportSessions is all or nothing: every
+    // snapshot is validated by ImportSession's rules (host memory: on the host; device memory: by a validation launch and one
+    // read-back) before any slot, mirror or ring is touched; afterwards the object is what count ImportSession calls would have
+    // left.  Both wait for what is enqueued on the object's stream and return when their work is done.
+    static constexpr int kSnapshotStageSessions = 256;
+    int32_t ExportSessions(const int32_t *sessions, int count, void *snapshots, bool device);
+    int32_t ImportSessions(const int32_t *sessions, int count, const void *snapshots, bool device, bool any_rate);
 
 private:
     SessionBatch() {}
@@ -150,6 +164,16 @@ private:
     bool EventUsable(void *ev) const;
     int AcquireArgSlot(bool needed, bool *ok);
     int32_t Fail();
+    // bulk snapshots: the list on the device, the host forms' stage, the validation verdict (word 0) + info words; all grow-only
+    int32_t CheckSessionList(const int32_t *sessions, int count) const;
+    bool EnsureSnapshotBuffers(int list_entries, int stage_sessions, int info_words);
+    SessionView View() const;
+    int32_t *snap_list_ = nullptr;
+    size_t snap_list_entries_ = 0;
+    uint8_t *snap_stage_ = nullptr;
+    size_t snap_stage_bytes_ = 0;
+    uint32_t *snap_verdict_ = nullptr;
+    size_t snap_verdict_words_ = 0;
     int device_ = 0;
 };
 

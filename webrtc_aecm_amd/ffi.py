@@ -64,6 +64,8 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_DescribeTickLive", "WebRtcAecmSessions_ForceSparseTicks",
     "WebRtcAecmSessions_InitRates", "WebRtcAecmSessions_InitSessionRate", "WebRtcAecmSessions_GetSessionRate",
     "WebRtcAecmSessions_ImportSessionAnyRate",
+    "WebRtcAecmSessions_ExportSessions", "WebRtcAecmSessions_ImportSessions", "WebRtcAecmSessions_ExportSessionsDevice",
+    "WebRtcAecmSessions_ImportSessionsDevice",
 ]
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
@@ -199,6 +201,10 @@ def load():
     lib.WebRtcAecmSessions_InitSessionRate.argtypes = [vp, C.c_int32, C.c_int32]
     lib.WebRtcAecmSessions_GetSessionRate.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.WebRtcAecmSessions_ImportSessionAnyRate.argtypes = [vp, C.c_int32, vp, C.c_size_t]
+    lib.WebRtcAecmSessions_ExportSessions.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t]
+    lib.WebRtcAecmSessions_ExportSessionsDevice.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t]
+    lib.WebRtcAecmSessions_ImportSessions.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t, C.c_int32]
+    lib.WebRtcAecmSessions_ImportSessionsDevice.argtypes = [vp, vp, C.c_int32, vp, C.c_size_t, C.c_int32]
     lib.WebRtcAecm_SetDefaultDevice.argtypes = [C.c_int32]
     lib.WebRtcAecmSessions_Create.restype = vp
     lib.WebRtcAecmSessions_Create.argtypes = [C.c_int32, C.c_int32]
@@ -728,6 +734,39 @@ class AecmSessions:
 
     def import_session(self, session: int, snapshot: bytes) -> int:
         return self.lib.WebRtcAecmSessions_ImportSession(self.h, session, snapshot, len(snapshot))
+
+    def _session_list(self, sessions, count=None):
+        """(keep-alive array or None, pointer or None, count) of a session list; None: sessions 0 .. count-1 (all without a count)."""
+        if sessions is None:
+            return None, None, self.num_streams if count is None else count
+        lst = np.ascontiguousarray(sessions, dtype=np.int32).reshape(-1)
+        return lst, lst.ctypes.data, lst.size
+
+    def export_sessions(self, sessions=None):
+        """(code, snapshots as bytes: one per listed session, back to back, in list order; None: all) --
+        WebRtcAecmSessions_ExportSessions."""
+        lst, ptr, count = self._session_list(sessions)
+        buf = np.zeros(count * self.lib.WebRtcAecmSessions_session_size_bytes(), dtype=np.uint8)
+        rc = self.lib.WebRtcAecmSessions_ExportSessions(self.h, ptr, count, buf.ctypes.data, buf.nbytes)
+        return rc, buf.tobytes()
+
+    def import_sessions(self, sessions, snapshots, any_rate: bool = False) -> int:
+        """WebRtcAecmSessions_ImportSessions: snapshots (bytes or a uint8 array) into the listed slots (None: 0 .. count-1), all or nothing."""
+        n = self.lib.WebRtcAecmSessions_session_size_bytes()
+        blob = np.frombuffer(snapshots, dtype=np.uint8) if isinstance(snapshots, (bytes, bytearray, memoryview)) else np.ascontiguousarray(snapshots, dtype=np.uint8).reshape(-1)
+        lst, ptr, count = self._session_list(sessions, blob.size // n)
+        return self.lib.WebRtcAecmSessions_ImportSessions(self.h, ptr, count, blob.ctypes.data, blob.size, 1 if any_rate else 0)
+
+    def export_sessions_device(self, ptr: int, sessions=None) -> int:
+        """WebRtcAecmSessions_ExportSessionsDevice into device memory (or a registered host buffer's alias) at ptr."""
+        lst, lptr, count = self._session_list(sessions)
+        return self.lib.WebRtcAecmSessions_ExportSessionsDevice(self.h, lptr, count, ptr, count * self.lib.WebRtcAecmSessions_session_size_bytes())
+
+    def import_sessions_device(self, ptr: int, sessions, count: int, any_rate: bool = False) -> int:
+        """WebRtcAecmSessions_ImportSessionsDevice: count snapshots at ptr into the listed slots (None: 0 .. count-1)."""
+        lst, lptr, _ = self._session_list(sessions, count)
+        return self.lib.WebRtcAecmSessions_ImportSessionsDevice(self.h, lptr, count, ptr, count * self.lib.WebRtcAecmSessions_session_size_bytes(),
+                                                                1 if any_rate else 0)
 
     def tick_device_per_session(self, far_ptr, near_ptr, out_ptr, stream_stride, n, ms_per_session, clean_ptr=None):
         ms = np.ascontiguousarray(ms_per_session, dtype=np.int16)
