@@ -250,6 +250,46 @@ int32_t WebRtcAecmSessions_TickAsync(AecmSessions *s, const int16_t *far_dev, co
                                      int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples, int16_t msInSndCardBuf,
                                      const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host,
                                      void *wait_hip_event, void *done_hip_event);
+/* Several call pairs per tick: the 20 ms packet of Opus or G.711 (and the 40 and 60 ms ones) on 10 ms calls.  A tick of
+ * `calls` = K call pairs of nrOfSamples = n samples is, for every session s that calls, exactly
+ *     for (c = 0; c < K; ++c) {
+ *         WebRtcAecm_BufferFarend(inst_s, far[s] + c * n, n);                                   (unless AECM_SESSION_NO_FAREND)
+ *         WebRtcAecm_Process(inst_s, near[s] + c * n, clean ? clean[s] + c * n : NULL, out[s] + c * n, n, ms_s);
+ *     }
+ * -- bit for bit K ordinary ticks on the same rows (outputs, codes, echo path, the complete session state), and interchangeable
+ * with them at any point of a session's life; NOT WebRtcAecmSessions_BufferFarend(calls) followed by Process, which is far, far,
+ * near.  K ordinary ticks cost K planning launches, K tick launches and K round trips of the core state; this is one planning
+ * launch and one tick launch that keeps a session's core state in registers across its K call pairs.
+ *   rows                        : [S][stream_stride] with stream_stride >= calls * nrOfSamples; call c uses samples [c n, (c + 1) n)
+ *   calls                       : 1 .. AECM_SESSION_MAX_TICK_CALLS.  calls == 1 is TickAsync / TickFlags with the same arguments:
+ *                                 the same launches, the same kernels
+ *   msInSndCardBuf(_host)       : as in TickAsync -- one value per session, used for all K calls
+ *   codes_host[s]               : the first non-zero code of the session's calls (0 for an idle session); the function returns 0 or
+ *                                 the first non-zero code
+ *   AECM_SESSION_IDLE           : the session makes none of the K pairs and falls calls * n samples behind the object; its out row
+ *                                 is not written by the device forms and comes back as zeros from the Host form; everything said
+ *                                 of idle sessions above stays true
+ *   AECM_SESSION_NO_FAREND      : none of the session's K pairs has a WebRtcAecm_BufferFarend
+ *   AECM_SESSION_SPLIT_CALLS, AECM_SESSION_HALF_CALL on a session that calls, with calls > 1: AECM_BAD_PARAMETER_ERROR
+ * With calls > 1, an object that holds a session of another rate than its own (WebRtcAecmSessions_InitRates and friends) is
+ * refused with AECM_UNSUPPORTED_FUNCTION_ERROR: such a session gets its 10 ms through half calls, and K half calls per row is a
+ * layout of its own, left for later.  So is the safe kernel variant, as for every tick.  The arguments are checked in the
+ * reference's order (NULL, uninitialised, sizes -- calls out of range and a short stride are AECM_BAD_PARAMETER_ERROR --, then a
+ * poisoned object); a refused call changes nothing, neither the sessions nor the object's position.  K-call ticks, ordinary
+ * ticks, bursts, Process, InitSession*, set_config_session, Export / ImportSession(s) and ticks of another K mix freely.
+ * TickCalls waits for the tick, TickCallsHost stages host audio like TickFlagsHost (its staging grows to calls * n samples per
+ * row, once), TickCallsAsync is TickAsync's form. */
+enum { AECM_SESSION_MAX_TICK_CALLS = 6 };      /* 60 ms of 10 ms calls */
+int32_t WebRtcAecmSessions_TickCalls(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                     int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples, int32_t calls, int16_t msInSndCardBuf,
+                                     const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host);
+int32_t WebRtcAecmSessions_TickCallsHost(AecmSessions *s, const int16_t *far_host, const int16_t *near_host, const int16_t *near_clean_host,
+                                         int16_t *out_host, int64_t stream_stride, size_t nrOfSamples, int32_t calls, int16_t msInSndCardBuf,
+                                         const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host);
+int32_t WebRtcAecmSessions_TickCallsAsync(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                          int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples, int32_t calls, int16_t msInSndCardBuf,
+                                          const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host,
+                                          void *wait_hip_event, void *done_hip_event);
 /* Far-end bursts.  The reference lets a caller make ANY number of WebRtcAecm_BufferFarend calls between two
  * WebRtcAecm_Process calls (echo_control_mobile.h:87,135) -- what a jittery network produces: no far frame for a tick or
  * two, then several at once.  Each call runs the delay compensation once the session is past its start-up phase and then

@@ -25,6 +25,13 @@ every 160-sample tick, the rest 16 kHz / 160; device-resident audio, TickAsync w
 next to (a) the all-16 kHz object of the same size without a flags array -- and once more with the arrays the mixed rows pass, flags
 that name nothing --, and (d) what a user without mixed objects does for the
 50 % case: two objects of S / 2 sessions, one 8 kHz / 80 and one 16 kHz / 160, ticked back to back.  --repeats times each.
+
+--calls K[,K...]: ticks of K call pairs (WebRtcAecmSessions_TickCallsAsync: a 20 .. 60 ms packet interval on 10 ms calls in one
+planning and one tick launch).  For each K, in one process and interleaved (K-call object, twin, K-call object, twin, ...,
+--repeats rounds): one K-call tick of an object against K back-to-back WebRtcAecmSessions_TickAsync ticks of a twin object on the
+same rows; device-resident audio, per-session msInSndCardBuf and flags.  With --occupancy P (a fraction, or per cent when > 1) a
+fixed, seeded random share of the sessions is live and the others sit out every tick.  Printed: ms per K-call tick, ms per K
+ordinary ticks, the ratio (< 1: the K-call tick is cheaper).
 """
 import argparse
 import json
@@ -49,8 +56,11 @@ def main():
                     help="WebRtcAecmSessions_TickAsync: ticks are enqueued back to back, one synchronisation at the end (host-staged always is)")
     ap.add_argument("--occupancy", default="", help="P[,P...]: share of the sessions that is live; the others are idle every tick (see above)")
     ap.add_argument("--mixed", default="", help="P[,P...]: per cent of the sessions that are 8 kHz half-call sessions in a 16 kHz object (see above)")
-    ap.add_argument("--repeats", type=int, default=3, help="--occupancy / --mixed: measurements per column (the median is reported, all are listed)")
+    ap.add_argument("--repeats", type=int, default=3, help="--occupancy / --mixed / --calls: measurements per column (the median is reported, all are listed)")
+    ap.add_argument("--calls", default="", help="K[,K...]: a tick of K call pairs against K back-to-back ticks of a twin object (see above)")
     args = ap.parse_args()
+    if args.calls:
+        return calls_sweep(args)
     if args.occupancy:
         return occupancy_sweep(args)
     if args.mixed:
@@ -202,6 +212,68 @@ def occupancy_sweep(args):
     print(json.dumps({"streams": S, "fs": fs, "audio": "device", "async": True, "ticks": args.ticks,
                       "dense_ms_per_tick": float(np.median(dense)), "dense_all_ms_per_tick": dense,
                       "dense_tick_workgroup_rounds": aecm.describe_tick(S, cus)["rounds_x1000"] / 1000.0, "sparse": rows}))
+
+
+def calls_sweep(args):
+    import math
+
+    import numpy as np
+    import torch
+
+    import webrtc_aecm_amd as aecm
+    S, fs = args.streams, args.fs
+    n = fs // 100
+    ks = [int(x) for x in args.calls.split(",")]
+    width = n * max(ks) * 2                           # two packet intervals of the largest K per row
+    g = torch.Generator(device="cuda").manual_seed(1)
+    far = (torch.randn((S, width), generator=g, device="cuda") * 3000).clamp_(-32768, 32767).to(torch.int16)
+    near = (far.roll(37, dims=1) // 3 + (torch.randn((S, width), generator=g, device="cuda") * 200).to(torch.int16))
+    out_a, out_b = torch.empty_like(far), torch.empty_like(far)
+    ms = np.full(S, 40, dtype=np.int16)
+    p = float(args.occupancy) if args.occupancy else 1.0
+    p = p / 100.0 if p > 1.0 else p
+    live = min(S, math.ceil(p * S))
+    flags = None
+    if live < S:
+        flags = np.full(S, aecm.ffi.SESSION_IDLE, dtype=np.uint8)
+        flags[np.random.default_rng(7).permutation(S)[:live]] = 0
+    rows = []
+    for K in ks:
+        a, b = aecm.AecmSessions(S, fs, 1, 1), aecm.AecmSessions(S, fs, 1, 1)
+
+        def tick_a(i):
+            off = (i % 2) * K * n * 2
+            rc, _ = a.tick_calls_device(far.data_ptr() + off, near.data_ptr() + off, out_a.data_ptr() + off, width, n, K, ms, flags=flags, asynchronous=True)
+            assert rc == 0, rc
+
+        def tick_b(i):
+            for c in range(K):
+                off = ((i % 2) * K + c) * n * 2
+                rc = b.tick_async(far.data_ptr() + off, near.data_ptr() + off, out_b.data_ptr() + off, width, n, 40, ms_per_session=ms, flags=flags)
+                assert rc == 0, rc
+        warm = -(-40 // K)                            # both through the start-up phase, on the same calls
+        for i in range(warm):
+            tick_a(i)
+            tick_b(i)
+        times = {"a": [], "b": []}
+        at = warm
+        for r in range(args.repeats):
+            for key, obj, tick in (("a", a, tick_a), ("b", b, tick_b)):
+                assert a.synchronize() == 0 and b.synchronize() == 0
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for i in range(args.ticks):
+                    tick(at + i)
+                assert obj.synchronize() == 0
+                times[key].append((time.perf_counter() - t0) / args.ticks * 1e3)
+            at += args.ticks
+        assert a.synchronize() == 0 and b.synchronize() == 0
+        same = bool(torch.equal(out_a[:, :2 * K * n], out_b[:, :2 * K * n])) if live == S else None      # (idle rows are never written)
+        ta, tb = float(np.median(times["a"])), float(np.median(times["b"]))
+        rows.append({"calls": K, "ms_per_k_call_tick": ta, "ms_per_k_ticks": tb, "ratio": ta / tb, "all_k_call": times["a"], "all_k_ticks": times["b"],
+                     "outputs_equal": same})
+        a.close(), b.close()
+    print(json.dumps({"streams": S, "fs": fs, "n": n, "audio": "device", "async": True, "ticks": args.ticks, "live": live, "rows": rows}))
 
 
 def mixed_sweep(args):

@@ -146,6 +146,20 @@ def main():
         out, codes, paths = sparse_helpers.drive_reference(lambda: pyoracle.RefSession(fs, 1, 3), fs, flags, ms, np.full(T, frame), far, near)
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, flags=flags, ms=ms, out=out, codes=codes.astype(np.int16), paths=paths)
         print("sesssparse", fs, frame, "live calls", int(((flags & 4) == 0).sum()), "of", T * S, sorted(set(codes.ravel().tolist())))
+    # Ticks of K call pairs (WebRtcAecmSessions_TickCalls; tests/calls_helpers.py: golden_pattern): 9 sessions x 48 calls, every
+    # session on a reference instance of its own that makes the K pairs of a tick in order (far, near, far, near, ...) and is not
+    # called in an idle tick.  Arrays only: the recipe's seed and K, per-tick flags and msInSndCardBuf, outputs, codes, final echo paths.
+    import calls_helpers
+    for name, (fs, frame, K, seed) in calls_helpers.GOLDEN_CASES.items():
+        if only and only not in name:
+            continue
+        flags, ms = calls_helpers.golden_pattern(frame, K, seed)
+        far, near, _ = sparse_helpers.signals(seed, calls_helpers.GOLDEN_S, calls_helpers.GOLDEN_CALLS * frame, fs)
+        out, codes, refs = calls_helpers.run_reference(lambda: pyoracle.RefSession(fs, 1, 3), calls_helpers.calls_ops(K, frame, flags, ms),
+                                                       calls_helpers.Feed(far, near))
+        paths = np.stack([r.get_echo_path()[1] for r in refs])
+        np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, calls=K, flags=flags, ms=ms, out=out, codes=codes.astype(np.int16), paths=paths)
+        print("sesscalls", fs, frame, K, "live calls", int(((flags & 4) == 0).sum()) * K, sorted(set(codes.ravel().tolist())))
     # Objects of mixed rates and call sizes (WebRtcAecmSessions_InitRates, AECM_SESSION_HALF_CALL; tests/mixed_helpers.py: the mixed
     # run): every session on a reference instance of its own, initialised at ITS rate and called with ITS sizes.  Arrays only:
     # the seed, the per-session rates, flags, msInSndCardBuf and burst calls of every tick, outputs, codes, final echo paths --

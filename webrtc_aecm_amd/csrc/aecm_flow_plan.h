@@ -537,6 +537,24 @@ AECM_FLOW_HD void FlowTickMixed(FlowRegs &s, int fs, int n, int ms, int flags, u
     if (half) s.v[F_NEAR_LAG] = FlowIdleTick(s.v[F_NEAR_LAG], kFlowFrame);
 }
 
+// A tick of K call pairs of n samples (a 20 .. 60 ms packet interval on 10 ms calls; WebRtcAecmSessions_TickCalls): K times
+// FlowTick, in order, the near position advancing n per call -- call c's samples are [c n, (c + 1) n) of every row and land at
+// near-ring positions near_pos + c n.  One plan per call, handed to `sink(c, plan)` as it is made (on the device: packed and
+// stored, so that only one plan is ever in registers).  No new arithmetic: every state between two calls is a state between two
+// ordinary ticks, and the replay-row spill test is made per call, with its one-tick margin.  The session is in step
+// (FlowResync ONCE, before the first call, otherwise); a session that sits the tick out falls calls * n samples behind
+// (FlowIdleTick(lag, calls * n)).  flags: kFlowNoFarend (none of the K pairs has a BufferFarend) or 0.
+constexpr int kFlowMaxTickCalls = 6;                // = AECM_SESSION_MAX_TICK_CALLS: 60 ms of 10 ms calls
+template <class Sink>
+AECM_FLOW_HD void FlowTickCalls(FlowRegs &s, int fs, int n, int calls, int ms, int flags, uint32_t near_pos, Sink &&sink) {
+    for (int c = 0; c < calls; ++c) {
+        FlowPlan p;
+        FlowTick(s, fs, n, ms, flags & kFlowNoFarend, near_pos + (uint32_t)(c * n), p);
+        sink(c, p);
+    }
+}
+static_assert(kFlowMaxTickCalls * 2 * kFlowFrame < kFlowFarRing - kFlowJitterCapacity, "a K-call tick fits the rings");
+
 // The host's pass over a tick's flags (SessionBatch::Enqueue): FlowLiveBlockBases, and in the same pass what the sessions that
 // call ask for -- *any = the OR of their bytes, *half_and_split = some session carries kFlowHalfCall and kFlowSplitCalls together.
 inline int32_t FlowScanFlags(const uint8_t *flags, int32_t n_sessions, uint32_t *bases, uint8_t *any, bool *half_and_split) {

@@ -183,6 +183,18 @@ struct TickSparseIo {
 // the session lags 80 samples (aecm_flow_plan.h: FlowTickMixed).  The tick launch is the same either way.
 hipError_t LaunchTickFlowSparse(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int live_count,
                                 hipStream_t stream, bool mixed_plan = false);
+// A tick of `calls` (1 .. kFlowMaxTickCalls) call pairs of io.n samples per session (aecm_tick_calls_kernels.hip): call c uses
+// samples [c n, (c + 1) n) of every row (io.io_stride >= calls * io.n).  Two launches whatever `calls` is:
+//   aecm_flow_plan_calls_kernel   everything the sparse planning kernel does, then FlowTickCalls: fio.plans is
+//                                 [S][calls][kFlowPlanWords] here
+//   aecm_tick_calls_kernel        wavefront w serves session live[w]; the core state is loaded once, stays in registers across
+//                                 the calls and is stored once
+// Always by the live list (sp.live and sp.block_base must be set; everybody live: block_base[b] = b * kFlowPlanBlock).  Every
+// session at fio.fs: the caller refuses objects that hold a session of another rate.
+hipError_t LaunchTickCalls(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int live_count,
+                           int calls, hipStream_t stream);
+// The planning launch alone (aecm_tick_calls_plan_kernels.hip; LaunchTickCalls calls it).
+hipError_t LaunchPlanCalls(const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int calls, hipStream_t stream);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront
@@ -210,6 +222,8 @@ hipError_t LaunchFft128(int16_t *data_dev, int32_t *scales_dev, int variant, int
 hipError_t ReadCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_block_kernels.hip (device symbols are per translation unit); ReadCheckCounters adds it in.  Does not synchronise.
 hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_tick_calls_kernels.hip, for callers that audit K-call ticks (ReadCheckCounters does not add it in).  Does not synchronise.
+hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
 
 // Device self test of the wave primitives; counters[0..7] are failure counts (all must be 0):
 //  0 shfl_xor, 1 exchange, 2 reduce_max/min/add, 3 shift_up1, 4 bpermute/readlane/writelane, 5 ballot,

@@ -59,6 +59,7 @@ SessionBatch::~SessionBatch() {
     (void)hipFree(io_dev_);
     (void)hipFree(flow_state_);
     (void)hipFree(flow_plans_);
+    (void)hipFree(calls_plans_);
     (void)hipFree(far_frames_);
     (void)hipFree(far_old_);
     (void)hipFree(live_dev_);
@@ -270,7 +271,7 @@ int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_
 
 int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride, size_t n_samples,
                               int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes,
-                              bool host_pointers, void *wait_event, void *done_event, int flags) {
+                              bool host_pointers, void *wait_event, void *done_event, int flags, int32_t calls) {
     if (near == nullptr || out == nullptr) return AECM_NULL_POINTER_ERROR;
     if (far == nullptr) {                 // only a tick in which nobody makes a WebRtcAecm_BufferFarend call needs no far rows
         bool nobody = flags_per_session ? true : (flags & kNoFarend) != 0;
@@ -280,12 +281,18 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     }
     if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
     if (n_samples != 80 && n_samples != 160) return AECM_BAD_PARAMETER_ERROR;       // compared as size_t: 2^32 + 80 is not 80
-    if (stride < (int64_t)n_samples) return AECM_BAD_PARAMETER_ERROR;
+    // calls: the call pairs of n_samples every session that calls makes in this tick (TickCalls; 1: the tick of old, by the
+    // launches and kernels of old) -- call c on samples [c n, (c + 1) n) of every row
+    if (calls < 1 || calls > kFlowMaxTickCalls) return AECM_BAD_PARAMETER_ERROR;
+    if (stride < (int64_t)n_samples * calls) return AECM_BAD_PARAMETER_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
     // the tick kernel exists for the fast cross-lane primitives only: a batch switched to the safe variant is told so (and
     // stays usable after switching back) instead of being poisoned
     if (engine_->variant() != kVariantFast) return AECM_UNSUPPORTED_FUNCTION_ERROR;
-    const int n = (int)n_samples;
+    // K calls per row of a session of the other rate (K half calls, for an 8 kHz session of a 16 kHz object) is a layout of its own
+    if (calls > 1 && other_rates_ > 0) return AECM_UNSUPPORTED_FUNCTION_ERROR;
+    const int n = (int)n_samples, span = n * calls;          // span: the samples of the tick in every row
+    const bool k_calls = calls > 1;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
     const int S = engine_->num_streams();
     hipStream_t st = engine_->stream();
@@ -297,6 +304,7 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     bool half_and_split = false;
     if (flags_per_session) live = FlowScanFlags(flags_per_session, S, live_bases_.data(), &any, &half_and_split);
     if (!FlowTickFlagsValid(n, any, half_and_split)) return AECM_BAD_PARAMETER_ERROR;     // two 80-sample calls, or 80 of 160, need 160 samples
+    if (k_calls && (any & (kSplitCalls | kHalfCall)) != 0) return AECM_BAD_PARAMETER_ERROR;    // a K-call tick's calls are whole calls of n samples
     const bool half_calls = flags_per_session && (any & kHalfCall) != 0;                  // some session that calls makes a half call
     const auto idle = [&](int s) { return flags_per_session && (flags_per_session[s] & kIdle) != 0; };
     if (live == 0) {
@@ -306,15 +314,30 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
             (void)hipGetLastError();
             return AECM_BAD_PARAMETER_ERROR;
         }
-        near_pos_ += n;
-        (void)FlowRouteTick(lag_, 0, S, n, force_sparse_);
+        near_pos_ += span;
+        (void)FlowRouteTick(lag_, 0, S, span, force_sparse_);
         if (codes) memset(codes, 0, (size_t)S * sizeof(int32_t));
         if (host_pointers)
-            for (int s = 0; s < S; ++s) memset(out + (size_t)s * stride, 0, (size_t)n * 2);
+            for (int s = 0; s < S; ++s) memset(out + (size_t)s * stride, 0, (size_t)span * 2);
         if (done_event && !AECM_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(done_event), st))) return Fail();
         return 0;
     }
-    const bool sparse_tick = live < S || force_sparse_;      // (as FlowRouteTick will say below, once the tick is certain to be enqueued)
+    // (as FlowRouteTick will say below, once the tick is certain to be enqueued; a K-call tick always goes by the live list)
+    const bool sparse_tick = live < S || force_sparse_ || k_calls;
+    if (k_calls && !calls_plans_ &&
+        !AECM_HIP_OK(hipMalloc((void **)&calls_plans_, (size_t)S * kFlowMaxTickCalls * kFlowPlanWords * sizeof(int32_t)))) {
+        calls_plans_ = nullptr;
+        return AECM_UNSPECIFIED_ERROR;
+    }
+    // host audio of a K-call tick: the staging planes grow to calls * n samples per row (grow-only)
+    if (host_pointers && (size_t)span > io_row_) {
+        if (!AECM_HIP_OK(hipStreamSynchronize(st))) return Fail();      // (nothing enqueued may still use the old planes)
+        int16_t *grown = nullptr;
+        if (!AECM_HIP_OK(hipMalloc((void **)&grown, 4 * (size_t)S * span * 2))) return AECM_UNSPECIFIED_ERROR;
+        (void)hipFree(io_dev_);
+        io_dev_ = grown;
+        io_row_ = (size_t)span;
+    }
     if (clean && !clean_ring_) {
         const size_t bytes = (size_t)S * kRing * 2;
         if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
@@ -366,19 +389,19 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     const int16_t *dfar = far, *dnear = near, *dclean = clean;
     int16_t *dout = out;
     int64_t dstride = stride;
-    // Host audio: staged in device rows of n samples; rows that are dense on the host too travel as one copy each way.
+    // Host audio: staged in device rows of n (K calls: calls * n) samples; rows that are dense on the host too travel as one copy each way.
     auto copy_rows = [&](void *dst, size_t dpitch, const void *src, size_t spitch, hipMemcpyKind kind) {
-        const size_t width = (size_t)n * 2;
+        const size_t width = (size_t)span * 2;
         if (dpitch == width && spitch == width) return AECM_HIP_OK(hipMemcpyAsync(dst, src, width * S, kind, st));
         return AECM_HIP_OK(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, S, kind, st));
     };
     if (host_pointers) {
-        dstride = n;
-        const size_t plane = (size_t)S * 160;
+        dstride = span;
+        const size_t plane = (size_t)S * io_row_;
         int16_t *f = io_dev_, *d = io_dev_ + plane, *c = io_dev_ + 3 * plane;
-        if (!copy_rows(f, (size_t)n * 2, far, (size_t)stride * 2, hipMemcpyHostToDevice) ||
-            !copy_rows(d, (size_t)n * 2, near, (size_t)stride * 2, hipMemcpyHostToDevice) ||
-            (clean && !copy_rows(c, (size_t)n * 2, clean, (size_t)stride * 2, hipMemcpyHostToDevice)))
+        if (!copy_rows(f, (size_t)span * 2, far, (size_t)stride * 2, hipMemcpyHostToDevice) ||
+            !copy_rows(d, (size_t)span * 2, near, (size_t)stride * 2, hipMemcpyHostToDevice) ||
+            (clean && !copy_rows(c, (size_t)span * 2, clean, (size_t)stride * 2, hipMemcpyHostToDevice)))
             return fail();
         dfar = f;
         dnear = d;
@@ -386,7 +409,7 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         if (clean) dclean = c;
         // whole planes travel back: the rows of sessions that sit out, which no kernel writes, as zeros
         // (and the second halves of the rows of sessions that make a half call)
-        if ((live < S || half_calls) && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * n * 2, st))) return fail();
+        if ((live < S || half_calls) && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * span * 2, st))) return fail();
     }
     TickIo tio{dfar, dnear, dclean, dout, dstride, n, far_ring_, near_ring_, clean_ring_, out_ring_, kRing, near_pos_};
     TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, ms_per_session ? ms_dev_[slot] : nullptr,
@@ -397,30 +420,35 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     }
     bool ok;
     bool mixed_plan;
-    const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, n, force_sparse_, half_calls, other_rates_ > 0, &mixed_plan);
-    if (!route.sparse_plan) {
+    // (a K-call tick: no half calls, no other rates -- FlowRouteTick itself, told the whole tick's samples and that the tick goes by the live list)
+    const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, span, force_sparse_ || k_calls, half_calls, other_rates_ > 0, &mixed_plan);
+    if (k_calls) {
+        fio.plans = calls_plans_;
+        const TickSparseIo sp{near_ring_, clean_ring_, kRing, live_dev_, bases_dev_[slot], route.deferred_lag};
+        ok = AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, live, calls, st));
+    } else if (!route.sparse_plan) {
         ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
     } else {
         const TickSparseIo sp{near_ring_, clean_ring_, kRing, route.sparse_tick ? live_dev_ : nullptr, route.sparse_tick ? bases_dev_[slot] : nullptr,
                               route.deferred_lag};
         ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, sp, S, live, st, mixed_plan));
     }
-    near_pos_ += n;
+    near_pos_ += span;
     if (!ok) return fail();
     if (ms_per_session || flags_per_session || sparse_tick) {            // both launches of the tick are behind this event; only the first reads the slot
         if (!AECM_HIP_OK(hipEventRecord(slot_read_[slot], st))) return fail();
         slot_busy_[slot] = true;
     }
-    if (host_pointers && !copy_rows(out, (size_t)stride * 2, dout, (size_t)n * 2, hipMemcpyDeviceToHost)) return fail();
+    if (host_pointers && !copy_rows(out, (size_t)stride * 2, dout, (size_t)span * 2, hipMemcpyDeviceToHost)) return fail();
     if (done_event && !AECM_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(done_event), st))) return fail();
     return first_rc;
 }
 
 int32_t SessionBatch::Tick(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride, size_t n_samples,
                            int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes,
-                           bool host_pointers, int flags) {
+                           bool host_pointers, int flags, int32_t calls) {
     const int32_t rc = Enqueue(far, near, clean, out, stride, n_samples, ms, ms_per_session, flags_per_session, codes, host_pointers,
-                               nullptr, nullptr, flags);
+                               nullptr, nullptr, flags, calls);
     if (rc != 0 && rc != AECM_BAD_PARAMETER_WARNING) return rc;            // nothing was enqueued (or the object is poisoned)
     if (!AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return Fail();
     return rc;
@@ -428,8 +456,8 @@ int32_t SessionBatch::Tick(const int16_t *far, const int16_t *near, const int16_
 
 int32_t SessionBatch::TickAsync(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride,
                                 size_t n_samples, int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session,
-                                int32_t *codes, void *wait_event, void *done_event, int flags) {
-    return Enqueue(far, near, clean, out, stride, n_samples, ms, ms_per_session, flags_per_session, codes, false, wait_event, done_event, flags);
+                                int32_t *codes, void *wait_event, void *done_event, int flags, int32_t calls) {
+    return Enqueue(far, near, clean, out, stride, n_samples, ms, ms_per_session, flags_per_session, codes, false, wait_event, done_event, flags, calls);
 }
 
 // ---- session snapshots ---------------------------------------------------------------------------------

@@ -63,14 +63,23 @@ public:
     //   flags: the same bits for every session when flags_per_session is null (kNoFarend / kSplitCalls).
     //   far may be null when no session makes a BufferFarend call in this tick (kNoFarend or kIdle for everybody).
     int32_t Tick(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
-                 int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers, int flags = 0);
+                 int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers, int flags = 0,
+                 int32_t calls = 1);
+    // calls (1 .. kFlowMaxTickCalls; WebRtcAecmSessions_TickCalls): every session that calls makes `calls` [BufferFarend] + Process
+    // call pairs of n samples in this tick, in order, call c on samples [c n, (c + 1) n) of its rows (stream_stride >= calls * n),
+    // all with the session's one ms -- the 20 .. 60 ms packet interval of a server on 10 ms calls, bit for bit `calls` ordinary
+    // ticks on the same rows, in ONE planning and ONE tick launch that keeps the core state in registers across the calls
+    // (aecm_tick_calls_kernels.hip).  calls == 1 is the tick above: the same launches, the same kernels.  With calls > 1:
+    // kSplitCalls / kHalfCall on a session that calls are refused (bad parameter), kNoFarend means none of the pairs has a
+    // BufferFarend, an idle session falls calls * n samples behind; an object that holds a session of another rate than its own
+    // is refused (unsupported function: K half calls per row is a layout of its own).  A refused tick changes nothing.
     // The same tick, enqueued on the object's stream without waiting for it (device pointers, or host memory the device
     // can address: see RegisterHostAudio): the two launches of tick t + 1 may be issued while tick t still runs.
     // wait_event (hipEvent_t, may be null): the tick's kernels wait for it first (the caller's producer of far / near);
     // done_event (hipEvent_t, may be null): recorded behind the tick (the caller's consumer of out waits for it).
     int32_t TickAsync(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
                       int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, void *wait_event,
-                      void *done_event, int flags = 0);
+                      void *done_event, int flags = 0, int32_t calls = 1);
     // Far-end bursts: WebRtcAecm_BufferFarend calls that come without a WebRtcAecm_Process (reference
     // echo_control_mobile.cc:215-234) -- session s makes calls_per_session[s] (host array, S entries <= calls; null:
     // everybody makes `calls`) consecutive calls of n samples on far[s][c * n .. + n).  Together with ticks whose sessions are
@@ -143,7 +152,9 @@ private:
     std::vector<uint32_t> live_bases_;         // [ceil(S / kFlowPlanBlock)] FlowLiveBlockBases of the tick's flags
     int16_t *far_ring_ = nullptr, *near_ring_ = nullptr, *out_ring_ = nullptr;   // [S][kRing]
     int16_t *clean_ring_ = nullptr;            // [S][kRing], allocated by the first tick that carries a clean near-end
-    int16_t *io_dev_ = nullptr;                // [4][S][160] staging when the caller passes host pointers
+    int16_t *io_dev_ = nullptr;                // [4][S][io_row_] staging when the caller passes host pointers
+    size_t io_row_ = 160;                      // samples per staged row: grows (only) with the host form of a K-call tick, to calls * n
+    int32_t *calls_plans_ = nullptr;           // [S][kFlowMaxTickCalls][kFlowPlanWords]: the plans of a K-call tick; allocated by the first one
     int32_t *flow_state_ = nullptr;            // [kFlowFieldsUsed][S] wrapper state, field-major
     int32_t *flow_plans_ = nullptr;            // [S][kFlowPlanWords]: this tick's plan of every session
     int16_t *far_frames_ = nullptr;            // [S][kFlowFarFrameRing]
@@ -160,7 +171,7 @@ private:
     int slot_ = 0;
     int32_t Enqueue(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
                     int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers,
-                    void *wait_event, void *done_event, int flags);
+                    void *wait_event, void *done_event, int flags, int32_t calls = 1);
     bool EventUsable(void *ev) const;
     int AcquireArgSlot(bool needed, bool *ok);
     int32_t Fail();

@@ -1783,6 +1783,34 @@ struct BlockEngine {
         store_state(r, vec, scal);
     }
 
+    // A third entry, for a launch that runs SEVERAL runs of blocks on one stream with the state in registers throughout (the
+    // K-call tick, aecm_tick_calls_kernels.hip: one run per call pair): n_blocks blocks on registers the caller has loaded
+    // (init_lane_constants + load_state) and possibly run on before; nothing is stored -- the caller calls store_state once,
+    // behind its last run.  io.ready() is called ahead of this run's first fetch, as above.  The block loop is the text of
+    // the two entries above once more: they stay what they were.
+    template <class Io>
+    static AECM_HD void run_blocks_loaded(Regs &r, const StatePtrs &st, Io &io, int64_t stream, int n_blocks) {
+        uint16_t *hist = st.hist + stream * (int64_t)kHistWordsPerStream;
+        io.ready();
+        vi far_next = io.far(r, 0);
+        vi near_next = io.near(r, 0);
+        vi clean_next = kHasClean ? io.clean(r, 0) : vi(0);
+        W::begin_stream();
+        for (int blk = 0; blk < n_blocks; ++blk) {
+            vi far_cur = far_next, near_cur = near_next, clean_cur = clean_next;
+            if (blk + 1 < n_blocks) {             // prefetch the next block's 3 x 128 bytes
+                far_next = io.far(r, blk + 1);
+                near_next = io.near(r, blk + 1);
+                if (kHasClean) clean_next = io.clean(r, blk + 1);
+            }
+            W::begin_block(blk, n_blocks);
+            vi out = process_block(r, hist, far_cur, near_cur, clean_cur);
+            io.out(r, blk, out);
+            AECM_PHASE_MARK(13, r.out_ovl, r.x_old);
+        }
+        AECM_PHASE_MARK(14, r.out_ovl, r.x_old);
+    }
+
     // The strided audio view of the batch interface (aecm_state.h: IoView).
     struct StridedIo {
         const IoView &v;

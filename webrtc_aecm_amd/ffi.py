@@ -66,11 +66,13 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_ImportSessionAnyRate",
     "WebRtcAecmSessions_ExportSessions", "WebRtcAecmSessions_ImportSessions", "WebRtcAecmSessions_ExportSessionsDevice",
     "WebRtcAecmSessions_ImportSessionsDevice",
+    "WebRtcAecmSessions_TickCalls", "WebRtcAecmSessions_TickCallsHost", "WebRtcAecmSessions_TickCallsAsync",
 ]
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
 SESSION_IDLE = 4
 SESSION_HALF_CALL = 8
+SESSION_MAX_TICK_CALLS = 6
 
 
 class AecmConfig(C.Structure):
@@ -223,6 +225,9 @@ def load():
     lib.WebRtcAecmSessions_InitEchoPath.argtypes = [vp, C.c_int32, vp, C.c_size_t]
     lib.WebRtcAecmSessions_GetEchoPath.argtypes = [vp, C.c_int32, vp, C.c_size_t]
     lib.WebRtcAecmSessions_TickAsync.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int16, vp, vp, vp, vp, vp]
+    lib.WebRtcAecmSessions_TickCalls.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp]
+    lib.WebRtcAecmSessions_TickCallsHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp]
+    lib.WebRtcAecmSessions_TickCallsAsync.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp, vp, vp]
     lib.WebRtcAecmSessions_BufferFarend.argtypes = [vp, vp, C.c_int64, C.c_size_t, C.c_int32, vp]
     lib.WebRtcAecmSessions_BufferFarendHost.argtypes = [vp, vp, C.c_int64, C.c_size_t, C.c_int32, vp]
     lib.WebRtcAecmSessions_BufferFarendAsync.argtypes = [vp, vp, C.c_int64, C.c_size_t, C.c_int32, vp, vp, vp]
@@ -798,6 +803,61 @@ class AecmSessions:
         codes = np.zeros(self.num_streams, dtype=np.int32)
         rc = self.lib.WebRtcAecmSessions_TickFlags(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, ms.ctypes.data,
                                                    fl.ctypes.data, codes.ctypes.data)
+        return rc, codes
+
+    def tick_calls_host(self, far, near, calls: int, ms_per_session, clean=None, flags=None):
+        """WebRtcAecmSessions_TickCallsHost: `calls` call pairs per session in one tick.  far/near(/clean): [S, calls * n] int16
+        (n = 80 or 160; call c is columns [c n, (c + 1) n)); ms_per_session: S msInSndCardBuf values, or one int for everybody;
+        flags: S uint8 (SESSION_NO_FAREND, SESSION_IDLE) or None.  Returns (code, out, codes[S]); an idle session's out row is zeros."""
+        far = np.ascontiguousarray(far, dtype=np.int16)
+        near = np.ascontiguousarray(near, dtype=np.int16)
+        if far.ndim != 2 or far.shape[0] != self.num_streams or near.shape != far.shape:
+            raise ValueError(f"far and near must be [{self.num_streams}, calls * n] int16, got {far.shape} and {near.shape}")
+        if calls < 1 or far.shape[1] % calls != 0:
+            raise ValueError("the rows must hold `calls` calls of n samples")
+        cptr = None
+        if clean is not None:
+            clean = np.ascontiguousarray(clean, dtype=np.int16)
+            if clean.shape != far.shape:
+                raise ValueError(f"clean {clean.shape} must have the shape of far {far.shape}")
+            cptr = clean.ctypes.data
+        ms, msp, fl, flp = self._calls_args(ms_per_session, flags)
+        out = np.empty_like(near)
+        codes = np.zeros(self.num_streams, dtype=np.int32)
+        rc = self.lib.WebRtcAecmSessions_TickCallsHost(self.h, far.ctypes.data, near.ctypes.data, cptr, out.ctypes.data, far.shape[1],
+                                                       far.shape[1] // calls, calls, ms, msp, flp, codes.ctypes.data)
+        return rc, out, codes
+
+    def _calls_args(self, ms_per_session, flags):
+        """(scalar ms, pointer or None, keep-alive flags array, pointer or None) of a K-call tick's per-session arguments."""
+        if np.ndim(ms_per_session) == 0:
+            ms, msp = int(ms_per_session), None
+            self._calls_ms = None
+        else:
+            self._calls_ms = np.ascontiguousarray(ms_per_session, dtype=np.int16)
+            if self._calls_ms.shape != (self.num_streams,):
+                raise ValueError("ms_per_session must have one entry per session")
+            ms, msp = 0, self._calls_ms.ctypes.data
+        fl = flp = None
+        if flags is not None:
+            fl = np.ascontiguousarray(flags, dtype=np.uint8)
+            if fl.shape != (self.num_streams,):
+                raise ValueError("flags must have one entry per session")
+            flp = fl.ctypes.data
+        return ms, msp, fl, flp
+
+    def tick_calls_device(self, far_ptr, near_ptr, out_ptr, stream_stride, n, calls: int, ms_per_session, clean_ptr=None, flags=None,
+                          asynchronous=False, wait_event=None, done_event=None):
+        """WebRtcAecmSessions_TickCalls / TickCallsAsync (device pointers; rows of stream_stride >= calls * n samples).  Returns
+        (code, codes[S]); the out row of a session that carries SESSION_IDLE is not written."""
+        ms, msp, fl, flp = self._calls_args(ms_per_session, flags)
+        codes = np.zeros(self.num_streams, dtype=np.int32)
+        if asynchronous:
+            rc = self.lib.WebRtcAecmSessions_TickCallsAsync(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, calls, ms, msp, flp,
+                                                            codes.ctypes.data, wait_event, done_event)
+        else:
+            rc = self.lib.WebRtcAecmSessions_TickCalls(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, calls, ms, msp, flp,
+                                                       codes.ctypes.data)
         return rc, codes
 
     def force_sparse_ticks(self, on: bool = True) -> int:
