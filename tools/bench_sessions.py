@@ -32,6 +32,14 @@ planning and one tick launch).  For each K, in one process and interleaved (K-ca
 same rows; device-resident audio, per-session msInSndCardBuf and flags.  With --occupancy P (a fraction, or per cent when > 1) a
 fixed, seeded random share of the sessions is live and the others sit out every tick.  Printed: ms per K-call tick, ms per K
 ordinary ticks, the ratio (< 1: the K-call tick is cheaper).
+
+--packets K[,K...] [--mixed P[,P...]]: packet ticks (WebRtcAecmSessions_TickPacketsAsync: one packet of K 10 ms calls per session,
+every session at its own rate and call size, rows packed).  For each P (per cent of the sessions that are 8 kHz sessions making half
+calls in a 16 kHz object ticking 160; default 0) and each K, by --calls' interleaved, median-of-repeats method: one packet tick of
+an object against K back-to-back WebRtcAecmSessions_TickAsync ticks flagged AECM_SESSION_HALF_CALL of a twin object of the same
+rates.  P = 0 is a uniform object without half flags: the routing falls back to the K-call tick's launches (compare with --calls).
+Outputs are compared at P = 0 only (with half calls the twin's rows are laid out differently; tests/test_gpu_tick_packets.py
+compares those).
 """
 import argparse
 import json
@@ -58,7 +66,10 @@ def main():
     ap.add_argument("--mixed", default="", help="P[,P...]: per cent of the sessions that are 8 kHz half-call sessions in a 16 kHz object (see above)")
     ap.add_argument("--repeats", type=int, default=3, help="--occupancy / --mixed / --calls: measurements per column (the median is reported, all are listed)")
     ap.add_argument("--calls", default="", help="K[,K...]: a tick of K call pairs against K back-to-back ticks of a twin object (see above)")
+    ap.add_argument("--packets", default="", help="K[,K...]: a packet tick of K calls per session against K back-to-back ticks of a twin object; with --mixed P[,P...] (see above)")
     args = ap.parse_args()
+    if args.packets:
+        return packets_sweep(args)
     if args.calls:
         return calls_sweep(args)
     if args.occupancy:
@@ -274,6 +285,63 @@ def calls_sweep(args):
                      "outputs_equal": same})
         a.close(), b.close()
     print(json.dumps({"streams": S, "fs": fs, "n": n, "audio": "device", "async": True, "ticks": args.ticks, "live": live, "rows": rows}))
+
+
+def packets_sweep(args):
+    import numpy as np
+    import torch
+
+    import webrtc_aecm_amd as aecm
+    S, fs, n = args.streams, 16000, 160
+    ks = [int(x) for x in args.packets.split(",")]
+    width = n * max(ks) * 2                           # two packets of the largest K per row
+    g = torch.Generator(device="cuda").manual_seed(1)
+    far = (torch.randn((S, width), generator=g, device="cuda") * 3000).clamp_(-32768, 32767).to(torch.int16)
+    near = (far.roll(37, dims=1) // 3 + (torch.randn((S, width), generator=g, device="cuda") * 200).to(torch.int16))
+    out_a, out_b = torch.empty_like(far), torch.empty_like(far)
+    ms = np.full(S, 40, dtype=np.int16)
+    rows = []
+    for p in [float(x) for x in (args.mixed or "0").split(",")]:
+        narrow = np.zeros(S, dtype=bool)
+        narrow[np.random.default_rng(7).permutation(S)[:int(round(p / 100 * S))]] = True
+        rates = np.where(narrow, 8000, 16000).astype(np.int32)
+        flags = np.where(narrow, aecm.ffi.SESSION_HALF_CALL, 0).astype(np.uint8) if narrow.any() else None
+        for K in ks:
+            a, b = (aecm.AecmSessions(S, fs, 1, 1, rates=rates if narrow.any() else None) for _ in range(2))
+
+            def tick_a(i):
+                off = (i % 2) * K * n * 2
+                rc, _ = a.tick_packets_device(far.data_ptr() + off, near.data_ptr() + off, out_a.data_ptr() + off, width, n, K, ms, flags=flags, asynchronous=True)
+                assert rc == 0, rc
+
+            def tick_b(i):
+                for c in range(K):
+                    off = ((i % 2) * K + c) * n * 2
+                    rc = b.tick_async(far.data_ptr() + off, near.data_ptr() + off, out_b.data_ptr() + off, width, n, 40, ms_per_session=ms, flags=flags)
+                    assert rc == 0, rc
+            warm = -(-40 // K)                        # both through the start-up phase, on the same number of calls
+            for i in range(warm):
+                tick_a(i)
+                tick_b(i)
+            times = {"a": [], "b": []}
+            at = warm
+            for r in range(args.repeats):
+                for key, obj, tick in (("a", a, tick_a), ("b", b, tick_b)):
+                    assert a.synchronize() == 0 and b.synchronize() == 0
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for i in range(args.ticks):
+                        tick(at + i)
+                    assert obj.synchronize() == 0
+                    times[key].append((time.perf_counter() - t0) / args.ticks * 1e3)
+                at += args.ticks
+            assert a.synchronize() == 0 and b.synchronize() == 0
+            same = bool(torch.equal(out_a[:, :2 * K * n], out_b[:, :2 * K * n])) if not narrow.any() else None
+            ta, tb = float(np.median(times["a"])), float(np.median(times["b"]))
+            rows.append({"mixed_percent": p, "narrowband": int(narrow.sum()), "calls": K, "ms_per_packet_tick": ta, "ms_per_k_ticks": tb, "ratio": ta / tb,
+                         "all_packet": times["a"], "all_k_ticks": times["b"], "outputs_equal": same})
+            a.close(), b.close()
+    print(json.dumps({"streams": S, "fs": fs, "n": n, "audio": "device", "async": True, "ticks": args.ticks, "rows": rows}))
 
 
 def mixed_sweep(args):

@@ -181,6 +181,20 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, object_fs=mh.OBJECT_FS, rates=mh.RATES, flags=flags, ms=ms, bursts=bursts, **res)
         print("sessmixed", name, "half calls", int((((flags & 8) != 0) & ((flags & 4) == 0)).sum()), "active from", res["active_from"].tolist(),
               sorted(set(res["codes"].ravel().tolist())))
+    # Packet ticks (WebRtcAecmSessions_TickPackets; tests/packets_helpers.py: golden_pattern): the 9 sessions and rates of the mixed
+    # run, 48 calls each in packets of K, every session on a reference instance at ITS rate making its K calls of ITS size (80 with
+    # a half flag) in order on packed rows.  Arrays only: flags, msInSndCardBuf, outputs (zeros where no call delivers), codes, paths.
+    import packets_helpers as ph
+    for name, (fs, frame, K, seed) in ph.GOLDEN_CASES.items():
+        if only and only not in name:
+            continue
+        flags, ms = ph.golden_pattern(K, seed)
+        far, near, _ = mh.signals(seed, mh.RATES, ph.GOLDEN_CALLS * frame)
+        out, codes, refs = ph.run_reference(lambda rate: pyoracle.RefSession(rate, 1, 3), mh.RATES, ph.packets_ops(K, frame, flags, ms), ph.Feed(far, near))
+        paths = np.stack([r.get_echo_path()[1] for r in refs])
+        np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, calls=K, rates=mh.RATES, flags=flags, ms=ms, out=out,
+                            codes=codes.astype(np.int16), paths=paths)
+        print("sesspackets", fs, frame, K, "half packets", int((((flags & 8) != 0) & ((flags & 4) == 0)).sum()), sorted(set(codes.ravel().tolist())))
     from helpers import stream_config
     for name, S, nb, fs, seed0 in RAGGED_CASES:
         if only and only not in name:

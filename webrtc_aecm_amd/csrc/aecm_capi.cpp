@@ -779,6 +779,36 @@ int32_t WebRtcAecmSessions_TickCallsAsync(AecmSessions *s, const int16_t *far_de
                                flags_host, codes_host, wait_hip_event, done_hip_event, 0, calls);
 }
 
+// One packet of K 10 ms calls per session and tick, every session at its own rate and call size, on packed rows: SessionBatch::Enqueue
+// with `calls` and `packets`.
+int32_t WebRtcAecmSessions_TickPackets(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                       int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples, int32_t calls, int16_t msInSndCardBuf,
+                                       const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host) {
+    if (!s) return -1;
+    if (flags_host && !msInSndCardBuf_host) return AECM_NULL_POINTER_ERROR;
+    return s->batch->Tick(far_dev, near_dev, near_clean_dev, out_dev, stream_stride, nrOfSamples, msInSndCardBuf, msInSndCardBuf_host,
+                          flags_host, codes_host, false, 0, calls, true);
+}
+
+int32_t WebRtcAecmSessions_TickPacketsHost(AecmSessions *s, const int16_t *far_host, const int16_t *near_host, const int16_t *near_clean_host,
+                                           int16_t *out_host, int64_t stream_stride, size_t nrOfSamples, int32_t calls, int16_t msInSndCardBuf,
+                                           const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host) {
+    if (!s) return -1;
+    if (flags_host && !msInSndCardBuf_host) return AECM_NULL_POINTER_ERROR;
+    return s->batch->Tick(far_host, near_host, near_clean_host, out_host, stream_stride, nrOfSamples, msInSndCardBuf, msInSndCardBuf_host,
+                          flags_host, codes_host, true, 0, calls, true);
+}
+
+int32_t WebRtcAecmSessions_TickPacketsAsync(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev, const int16_t *near_clean_dev,
+                                            int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples, int32_t calls, int16_t msInSndCardBuf,
+                                            const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host,
+                                            void *wait_hip_event, void *done_hip_event) {
+    if (!s) return -1;
+    if (flags_host && !msInSndCardBuf_host) return AECM_NULL_POINTER_ERROR;
+    return s->batch->TickAsync(far_dev, near_dev, near_clean_dev, out_dev, stream_stride, nrOfSamples, msInSndCardBuf, msInSndCardBuf_host,
+                               flags_host, codes_host, wait_hip_event, done_hip_event, 0, calls, true);
+}
+
 int32_t WebRtcAecmSessions_BufferFarend(AecmSessions *s, const int16_t *far_dev, int64_t stream_stride, size_t nrOfSamples, int32_t calls,
                                         const uint8_t *calls_host) {
     return s ? s->batch->BufferFarend(far_dev, stream_stride, nrOfSamples, calls, calls_host, false, true, nullptr, nullptr) : -1;

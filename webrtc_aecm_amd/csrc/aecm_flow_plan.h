@@ -555,6 +555,25 @@ AECM_FLOW_HD void FlowTickCalls(FlowRegs &s, int fs, int n, int calls, int ms, i
 }
 static_assert(kFlowMaxTickCalls * 2 * kFlowFrame < kFlowFarRing - kFlowJitterCapacity, "a K-call tick fits the rings");
 
+// A packet tick (WebRtcAecmSessions_TickPackets): K call pairs per session, every session at its OWN rate (fs: the session's) and
+// its own call size -- n_s = 80 with kFlowHalfCall in a 160-sample tick, else n -- on PACKED rows: call c's samples are
+// [c n_s, (c + 1) n_s) of the session's rows and land at near-ring positions near_pos + c n_s, so the session's own near positions
+// are contiguous across its K calls and nothing has to be brought back in step between them.  K times FlowTick of n_s samples
+// (each plan carries the call size in n_frames); once, at the end, the samples of the tick the session did not consume become its
+// lag: K * 80 for a session that made half calls, exactly as after K ordinary half-call ticks.  The session is in step at entry
+// (FlowResync ONCE, before the first call, otherwise).  flags: kFlowNoFarend and kFlowHalfCall count.
+AECM_FLOW_HD int FlowPacketCallSize(int n, int flags) { return (flags & kFlowHalfCall) != 0 && n == 2 * kFlowFrame ? kFlowFrame : n; }
+template <class Sink>
+AECM_FLOW_HD void FlowTickPackets(FlowRegs &s, int fs, int n, int calls, int ms, int flags, uint32_t near_pos, Sink &&sink) {
+    const int n_s = FlowPacketCallSize(n, flags);
+    for (int c = 0; c < calls; ++c) {
+        FlowPlan p;
+        FlowTick(s, fs, n_s, ms, flags & kFlowNoFarend, near_pos + (uint32_t)(c * n_s), p);
+        sink(c, p);
+    }
+    s.v[F_NEAR_LAG] = FlowIdleTick(s.v[F_NEAR_LAG], calls * (n - n_s));
+}
+
 // The host's pass over a tick's flags (SessionBatch::Enqueue): FlowLiveBlockBases, and in the same pass what the sessions that
 // call ask for -- *any = the OR of their bytes, *half_and_split = some session carries kFlowHalfCall and kFlowSplitCalls together.
 inline int32_t FlowScanFlags(const uint8_t *flags, int32_t n_sessions, uint32_t *bases, uint8_t *any, bool *half_and_split) {

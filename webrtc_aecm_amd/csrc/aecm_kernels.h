@@ -195,6 +195,18 @@ hipError_t LaunchTickCalls(const StatePtrs &st, const TickIo &io, const TickFlow
                            int calls, hipStream_t stream);
 // The planning launch alone (aecm_tick_calls_plan_kernels.hip; LaunchTickCalls calls it).
 hipError_t LaunchPlanCalls(const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int calls, hipStream_t stream);
+// A packet tick (aecm_tick_packets_kernels.hip; WebRtcAecmSessions_TickPackets): `calls` call pairs per session, every session at
+// its own rate (st.scal: S_MULT) and its own call size n_s -- 80 for a session flagged kFlowHalfCall in a tick of io.n == 160, else
+// io.n -- on PACKED rows: call c uses samples [c n_s, (c + 1) n_s) of the session's rows (io.io_stride >= calls * io.n).
+//   aecm_flow_plan_packets_kernel   what aecm_flow_plan_calls_kernel does, with FlowTickPackets at the lane's rate: fio.plans is
+//                                   [S][calls][kFlowPlanWords], every plan carrying its call size in n_frames
+//   aecm_tick_packets_kernel        aecm_tick_calls_kernel with the call size and the row step taken from the session's plans
+// Always by the live list, as LaunchTickCalls.
+hipError_t LaunchTickPackets(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int live_count,
+                             int calls, hipStream_t stream);
+// The planning launch alone (aecm_tick_packets_plan_kernels.hip; LaunchTickPackets calls it).
+hipError_t LaunchPlanPackets(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int calls,
+                             hipStream_t stream);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront
@@ -224,6 +236,8 @@ hipError_t ReadCheckCounters(uint64_t counters[2], bool reset);
 hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_calls_kernels.hip, for callers that audit K-call ticks (ReadCheckCounters does not add it in).  Does not synchronise.
 hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_tick_packets_kernels.hip, likewise.
+hipError_t ReadTickPacketsCheckCounters(uint64_t counters[2], bool reset);
 
 // Device self test of the wave primitives; counters[0..7] are failure counts (all must be 0):
 //  0 shfl_xor, 1 exchange, 2 reduce_max/min/add, 3 shift_up1, 4 bpermute/readlane/writelane, 5 ballot,

@@ -271,7 +271,7 @@ int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_
 
 int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride, size_t n_samples,
                               int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes,
-                              bool host_pointers, void *wait_event, void *done_event, int flags, int32_t calls) {
+                              bool host_pointers, void *wait_event, void *done_event, int flags, int32_t calls, bool packets) {
     if (near == nullptr || out == nullptr) return AECM_NULL_POINTER_ERROR;
     if (far == nullptr) {                 // only a tick in which nobody makes a WebRtcAecm_BufferFarend call needs no far rows
         bool nobody = flags_per_session ? true : (flags & kNoFarend) != 0;
@@ -289,8 +289,9 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     // the tick kernel exists for the fast cross-lane primitives only: a batch switched to the safe variant is told so (and
     // stays usable after switching back) instead of being poisoned
     if (engine_->variant() != kVariantFast) return AECM_UNSUPPORTED_FUNCTION_ERROR;
-    // K calls per row of a session of the other rate (K half calls, for an 8 kHz session of a 16 kHz object) is a layout of its own
-    if (calls > 1 && other_rates_ > 0) return AECM_UNSUPPORTED_FUNCTION_ERROR;
+    // K calls per row of a session of the other rate (K half calls, for an 8 kHz session of a 16 kHz object) is a layout of its own:
+    // the packed rows of a packet tick (packets; TickPackets), which TickCalls keeps refusing
+    if (calls > 1 && other_rates_ > 0 && !packets) return AECM_UNSUPPORTED_FUNCTION_ERROR;
     const int n = (int)n_samples, span = n * calls;          // span: the samples of the tick in every row
     const bool k_calls = calls > 1;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
@@ -304,7 +305,8 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     bool half_and_split = false;
     if (flags_per_session) live = FlowScanFlags(flags_per_session, S, live_bases_.data(), &any, &half_and_split);
     if (!FlowTickFlagsValid(n, any, half_and_split)) return AECM_BAD_PARAMETER_ERROR;     // two 80-sample calls, or 80 of 160, need 160 samples
-    if (k_calls && (any & (kSplitCalls | kHalfCall)) != 0) return AECM_BAD_PARAMETER_ERROR;    // a K-call tick's calls are whole calls of n samples
+    // a K-call tick's calls are whole calls of n samples; a packet tick's are whole calls of the session's own size (80 with kHalfCall)
+    if (k_calls && (any & (packets ? kSplitCalls : kSplitCalls | kHalfCall)) != 0) return AECM_BAD_PARAMETER_ERROR;
     const bool half_calls = flags_per_session && (any & kHalfCall) != 0;                  // some session that calls makes a half call
     const auto idle = [&](int s) { return flags_per_session && (flags_per_session[s] & kIdle) != 0; };
     if (live == 0) {
@@ -420,12 +422,20 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     }
     bool ok;
     bool mixed_plan;
-    // (a K-call tick: no half calls, no other rates -- FlowRouteTick itself, told the whole tick's samples and that the tick goes by the live list)
+    // (a K-call tick: no half calls, no other rates -- FlowRouteTick itself, told the whole tick's samples and that the tick goes by the
+    // live list; a packet tick: half calls leave their sessions calls * 80 behind, the object out of step)
     const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, span, force_sparse_ || k_calls, half_calls, other_rates_ > 0, &mixed_plan);
     if (k_calls) {
         fio.plans = calls_plans_;
         const TickSparseIo sp{near_ring_, clean_ring_, kRing, live_dev_, bases_dev_[slot], route.deferred_lag};
-        ok = AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, live, calls, st));
+        // (mixed_plan with K calls: a packet tick in which somebody makes half calls or runs at another rate -- the packed layout and
+        // its kernels; a packet tick of a uniform object without half calls IS the K-call tick)
+        if (mixed_plan) {
+            fio.flags = flags & kNoFarend;
+            ok = AECM_HIP_OK(LaunchTickPackets(engine_->state_ptrs(), tio, fio, sp, S, live, calls, st));
+        } else {
+            ok = AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, live, calls, st));
+        }
     } else if (!route.sparse_plan) {
         ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
     } else {
@@ -446,9 +456,9 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
 
 int32_t SessionBatch::Tick(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride, size_t n_samples,
                            int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes,
-                           bool host_pointers, int flags, int32_t calls) {
+                           bool host_pointers, int flags, int32_t calls, bool packets) {
     const int32_t rc = Enqueue(far, near, clean, out, stride, n_samples, ms, ms_per_session, flags_per_session, codes, host_pointers,
-                               nullptr, nullptr, flags, calls);
+                               nullptr, nullptr, flags, calls, packets);
     if (rc != 0 && rc != AECM_BAD_PARAMETER_WARNING) return rc;            // nothing was enqueued (or the object is poisoned)
     if (!AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return Fail();
     return rc;
@@ -456,8 +466,9 @@ int32_t SessionBatch::Tick(const int16_t *far, const int16_t *near, const int16_
 
 int32_t SessionBatch::TickAsync(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride,
                                 size_t n_samples, int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session,
-                                int32_t *codes, void *wait_event, void *done_event, int flags, int32_t calls) {
-    return Enqueue(far, near, clean, out, stride, n_samples, ms, ms_per_session, flags_per_session, codes, false, wait_event, done_event, flags, calls);
+                                int32_t *codes, void *wait_event, void *done_event, int flags, int32_t calls, bool packets) {
+    return Enqueue(far, near, clean, out, stride, n_samples, ms, ms_per_session, flags_per_session, codes, false, wait_event, done_event, flags, calls,
+                   packets);
 }
 
 // ---- session snapshots ---------------------------------------------------------------------------------

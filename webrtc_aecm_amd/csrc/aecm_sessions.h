@@ -64,7 +64,7 @@ public:
     //   far may be null when no session makes a BufferFarend call in this tick (kNoFarend or kIdle for everybody).
     int32_t Tick(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
                  int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers, int flags = 0,
-                 int32_t calls = 1);
+                 int32_t calls = 1, bool packets = false);
     // calls (1 .. kFlowMaxTickCalls; WebRtcAecmSessions_TickCalls): every session that calls makes `calls` [BufferFarend] + Process
     // call pairs of n samples in this tick, in order, call c on samples [c n, (c + 1) n) of its rows (stream_stride >= calls * n),
     // all with the session's one ms -- the 20 .. 60 ms packet interval of a server on 10 ms calls, bit for bit `calls` ordinary
@@ -72,14 +72,21 @@ public:
     // (aecm_tick_calls_kernels.hip).  calls == 1 is the tick above: the same launches, the same kernels.  With calls > 1:
     // kSplitCalls / kHalfCall on a session that calls are refused (bad parameter), kNoFarend means none of the pairs has a
     // BufferFarend, an idle session falls calls * n samples behind; an object that holds a session of another rate than its own
-    // is refused (unsupported function: K half calls per row is a layout of its own).  A refused tick changes nothing.
+    // is refused (unsupported function: K half calls per row is a layout of its own, the packet tick's).  A refused tick changes nothing.
+    // packets (WebRtcAecmSessions_TickPackets): the tick is one PACKET of `calls` 10 ms calls per session, every session at its own
+    // rate and its own call size n_s -- 80 with kHalfCall (n == 160), else n -- on packed rows: call c on samples [c n_s, (c + 1) n_s)
+    // of its rows (a decoded 20 ms G.711 packet: 160 contiguous samples).  Objects holding both rates and kHalfCall are accepted
+    // with calls > 1; the samples [calls * 80, calls * n) of a half-call session's rows are neither read nor written (host pointers:
+    // out zeros), and the session ends calls * 80 samples behind the object.  calls == 1: the ordinary tick; calls > 1 in a uniform
+    // object with no half call among the sessions that call: the K-call tick above, by its launches and kernels.  Otherwise
+    // aecm_tick_packets_kernels.hip.  kSplitCalls with calls > 1 stays refused.
     // The same tick, enqueued on the object's stream without waiting for it (device pointers, or host memory the device
     // can address: see RegisterHostAudio): the two launches of tick t + 1 may be issued while tick t still runs.
     // wait_event (hipEvent_t, may be null): the tick's kernels wait for it first (the caller's producer of far / near);
     // done_event (hipEvent_t, may be null): recorded behind the tick (the caller's consumer of out waits for it).
     int32_t TickAsync(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
                       int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, void *wait_event,
-                      void *done_event, int flags = 0, int32_t calls = 1);
+                      void *done_event, int flags = 0, int32_t calls = 1, bool packets = false);
     // Far-end bursts: WebRtcAecm_BufferFarend calls that come without a WebRtcAecm_Process (reference
     // echo_control_mobile.cc:215-234) -- session s makes calls_per_session[s] (host array, S entries <= calls; null:
     // everybody makes `calls`) consecutive calls of n samples on far[s][c * n .. + n).  Together with ticks whose sessions are
@@ -171,7 +178,7 @@ private:
     int slot_ = 0;
     int32_t Enqueue(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stream_stride, size_t n,
                     int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers,
-                    void *wait_event, void *done_event, int flags, int32_t calls = 1);
+                    void *wait_event, void *done_event, int flags, int32_t calls = 1, bool packets = false);
     bool EventUsable(void *ev) const;
     int AcquireArgSlot(bool needed, bool *ok);
     int32_t Fail();

@@ -67,6 +67,7 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_ExportSessions", "WebRtcAecmSessions_ImportSessions", "WebRtcAecmSessions_ExportSessionsDevice",
     "WebRtcAecmSessions_ImportSessionsDevice",
     "WebRtcAecmSessions_TickCalls", "WebRtcAecmSessions_TickCallsHost", "WebRtcAecmSessions_TickCallsAsync",
+    "WebRtcAecmSessions_TickPackets", "WebRtcAecmSessions_TickPacketsHost", "WebRtcAecmSessions_TickPacketsAsync",
 ]
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
@@ -228,6 +229,9 @@ def load():
     lib.WebRtcAecmSessions_TickCalls.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp]
     lib.WebRtcAecmSessions_TickCallsHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp]
     lib.WebRtcAecmSessions_TickCallsAsync.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp, vp, vp]
+    lib.WebRtcAecmSessions_TickPackets.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp]
+    lib.WebRtcAecmSessions_TickPacketsHost.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp]
+    lib.WebRtcAecmSessions_TickPacketsAsync.argtypes = [vp, vp, vp, vp, vp, C.c_int64, C.c_size_t, C.c_int32, C.c_int16, vp, vp, vp, vp, vp]
     lib.WebRtcAecmSessions_BufferFarend.argtypes = [vp, vp, C.c_int64, C.c_size_t, C.c_int32, vp]
     lib.WebRtcAecmSessions_BufferFarendHost.argtypes = [vp, vp, C.c_int64, C.c_size_t, C.c_int32, vp]
     lib.WebRtcAecmSessions_BufferFarendAsync.argtypes = [vp, vp, C.c_int64, C.c_size_t, C.c_int32, vp, vp, vp]
@@ -809,6 +813,17 @@ class AecmSessions:
         """WebRtcAecmSessions_TickCallsHost: `calls` call pairs per session in one tick.  far/near(/clean): [S, calls * n] int16
         (n = 80 or 160; call c is columns [c n, (c + 1) n)); ms_per_session: S msInSndCardBuf values, or one int for everybody;
         flags: S uint8 (SESSION_NO_FAREND, SESSION_IDLE) or None.  Returns (code, out, codes[S]); an idle session's out row is zeros."""
+        return self._tick_k_host(self.lib.WebRtcAecmSessions_TickCallsHost, far, near, calls, ms_per_session, clean, flags)
+
+    def tick_packets_host(self, far, near, calls: int, ms_per_session, clean=None, flags=None):
+        """WebRtcAecmSessions_TickPacketsHost: one packet of `calls` 10 ms calls per session, every session at its own rate and call
+        size, rows packed.  far/near(/clean): [S, calls * n] int16 (n = 80 or 160: the object's tick); a session flagged
+        SESSION_HALF_CALL (n = 160) makes calls of 80 samples on columns [c 80, (c + 1) 80), everybody else calls of n on
+        [c n, (c + 1) n); flags: S uint8 (SESSION_NO_FAREND, SESSION_IDLE, SESSION_HALF_CALL) or None.  Returns (code, out, codes[S]);
+        an idle session's out row and a half-call session's columns [calls * 80, calls * 160) are zeros."""
+        return self._tick_k_host(self.lib.WebRtcAecmSessions_TickPacketsHost, far, near, calls, ms_per_session, clean, flags)
+
+    def _tick_k_host(self, fn, far, near, calls, ms_per_session, clean, flags):
         far = np.ascontiguousarray(far, dtype=np.int16)
         near = np.ascontiguousarray(near, dtype=np.int16)
         if far.ndim != 2 or far.shape[0] != self.num_streams or near.shape != far.shape:
@@ -824,8 +839,8 @@ class AecmSessions:
         ms, msp, fl, flp = self._calls_args(ms_per_session, flags)
         out = np.empty_like(near)
         codes = np.zeros(self.num_streams, dtype=np.int32)
-        rc = self.lib.WebRtcAecmSessions_TickCallsHost(self.h, far.ctypes.data, near.ctypes.data, cptr, out.ctypes.data, far.shape[1],
-                                                       far.shape[1] // calls, calls, ms, msp, flp, codes.ctypes.data)
+        rc = fn(self.h, far.ctypes.data, near.ctypes.data, cptr, out.ctypes.data, far.shape[1], far.shape[1] // calls, calls, ms, msp, flp,
+                codes.ctypes.data)
         return rc, out, codes
 
     def _calls_args(self, ms_per_session, flags):
@@ -858,6 +873,21 @@ class AecmSessions:
         else:
             rc = self.lib.WebRtcAecmSessions_TickCalls(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, calls, ms, msp, flp,
                                                        codes.ctypes.data)
+        return rc, codes
+
+    def tick_packets_device(self, far_ptr, near_ptr, out_ptr, stream_stride, n, calls: int, ms_per_session, clean_ptr=None, flags=None,
+                            asynchronous=False, wait_event=None, done_event=None):
+        """WebRtcAecmSessions_TickPackets / TickPacketsAsync (device pointers; rows of stream_stride >= calls * n samples, packed per
+        session: see tick_packets_host).  Returns (code, codes[S]); the out row of a session that carries SESSION_IDLE and the samples
+        [calls * 80, calls * 160) of one that carries SESSION_HALF_CALL are not written."""
+        ms, msp, fl, flp = self._calls_args(ms_per_session, flags)
+        codes = np.zeros(self.num_streams, dtype=np.int32)
+        if asynchronous:
+            rc = self.lib.WebRtcAecmSessions_TickPacketsAsync(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, calls, ms, msp, flp,
+                                                              codes.ctypes.data, wait_event, done_event)
+        else:
+            rc = self.lib.WebRtcAecmSessions_TickPackets(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, calls, ms, msp, flp,
+                                                         codes.ctypes.data)
         return rc, codes
 
     def force_sparse_ticks(self, on: bool = True) -> int:
