@@ -22,8 +22,9 @@ _libs = {}
 # decisions counted by AECM_LEAN_COUNT (aecm_wave.h, process_binary)
 DECISIONS = {0: "valley above the minimum spread", 1: "min_prob above its lower limit (the test the lean form drops)",
              2: "a new delay estimate is stored", 3: "step size: the quotient is below 8 (the early return's two ways in)"}
-# (The clamp of the candidate -- all 100 means at their maximum -- is the parent's own select, moved into the store; no signal
-# here or in the parent's tests reaches it, and it is no branch of the lean form's.)
+# (The clamp of the candidate -- all 100 means at their maximum -- is the parent's own select, moved into the store.  No signal
+# reaches it: a mean stalls at 16 384 - 127.  tests/decision_allowlist.json has it, in both forms, with that argument, and
+# tests/test_decision_coverage.py reports it should an input ever take it.)
 
 
 # bench.py's content profiles (its PROFILES table: far-end envelope levels, near-end talk levels, envelope segment), restated with

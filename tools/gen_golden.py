@@ -195,6 +195,20 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, calls=K, rates=mh.RATES, flags=flags, ms=ms, out=out,
                             codes=codes.astype(np.int16), paths=paths)
         print("sesspackets", fs, frame, K, "half packets", int((((flags & 8) != 0) & ((flags & 4) == 0)).sum()), sorted(set(codes.ravel().tolist())))
+    # The block corpus as sessions (tests/corpus_sessions.py): every case of a rate without a clean input as one session, ordinary
+    # ticks with call_pattern delays and underruns for the whole case.  Kept: the output tail, a SHA-256 of the whole output, the
+    # non-zero codes and the final echo paths.
+    import corpus_sessions as cs
+    for name, fs in cs.GOLDEN_CASES.items():
+        if only and only not in name:
+            continue
+        cases = cs.session_cases(fs)
+        ops, far, near, rates = cs.plan(cases, fs)
+        refs = [cs.configure_session(pyoracle.RefSession(c["fs"], 1, 3), c) for c in cases]
+        out, codes, refs = ph.run_reference(None, rates, ops, ph.Feed(far, near), sessions=refs)
+        np.savez_compressed(GOLD / f"{name}.npz", fs=fs, names=np.array([c["name"] for c in cases]),
+                            **cs.summary(cases, out, codes, np.stack([r.get_echo_path()[1] for r in refs])))
+        print("sesscorpus", fs, len(cases), "sessions", len(ops), "ticks")
     from helpers import stream_config
     for name, S, nb, fs, seed0 in RAGGED_CASES:
         if only and only not in name:
