@@ -89,6 +89,19 @@ AECM_HD int mul24(int a, int b) {
 #endif
 }
 
+// The same product as the instruction itself (v_mul_i32_i24 reads the low 24 bits of either operand).  __mul24 is written with
+// sign extensions that the compiler removes only where it can see the operand's range; for an operand it cannot see through (a
+// value made opaque, one that arrives from another basic block) it keeps them.  The audit and host builds check the precondition
+// exactly as mul24 does.  Lane vectors only: a wave-uniform product belongs on the scalar unit (mul).
+#if defined(__HIP_DEVICE_COMPILE__)
+extern "C" __device__ int aecm_llvm_amdgcn_mul_i24(int, int) __asm("llvm.amdgcn.mul.i24.i32");   // no clang builtin (like v_ffbh_i32 below)
+#endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(AECM_CHECKED)
+AECM_HD int mul24_insn(int a, int b) { return aecm_llvm_amdgcn_mul_i24(a, b); }
+#else
+template <class I> AECM_HD I mul24_insn(I a, I b) { return mul24(a, b); }      // any lane-vector type that has a mul24
+#endif
+
 // The reference narrows many intermediate values to int16_t.  Where the value provably already lies
 // in [-32768, 32767] the narrowing is the identity and costs nothing here; the host build checks the
 // claim (the CPU lane simulator runs every test input, including the full-scale fuzz, through it).
@@ -320,6 +333,19 @@ AECM_HD int norm_u32(int a) { return clz32(a) & 31; }          // clz32(0) == 32
 #else
 AECM_HD int ffbh_i(int a) { return (a == 0 || a == -1) ? -1 : __builtin_clz((unsigned)(a < 0 ? ~a : a)); }
 template <class I> AECM_HD I norm_u32(I a) { return sel(a == 0, I(0), clz32(a)); }
+#endif
+// norm_u32 of a lane vector in two instructions: v_ffbh_u32 answers -1 for 0, so one signed maximum with 0 is the whole zero
+// fix-up (written with the count, the compiler pairs a minimum with 32 and a mask of 31 instead).  Vector registers only: a
+// wave-uniform operand would be moved to the vector unit for it.
+#if defined(__HIP_DEVICE_COMPILE__)
+AECM_HD int norm_u32_v(int a) {
+    int r;
+    asm("v_ffbh_u32 %0, %1" : "=v"(r) : "v"(a));
+    return r > 0 ? r : 0;
+}
+#else
+// the host (the lane simulator) runs the same two steps on the instruction's definition: the count, -1 for 0, then the maximum
+template <class I> AECM_HD I norm_u32_v(I a) { return imax(sel(a == 0, I(-1), clz32(a)), I(0)); }
 #endif
 AECM_HD int min_u32(int a, int b) { return (unsigned)a < (unsigned)b ? a : b; }
 template <class I> AECM_HD I norm_u32_nn(I a) { return imax(ffbh_i(as_nonneg(a)), I(0)); }

@@ -80,11 +80,16 @@
 //   2  suppression gain / far-energy filters: narrowings that are the identity dropped
 //   8  suppression gain, NLP average, step size: more narrowings that are the identity (each argued where it is dropped)
 //   4  comfort noise of bin 64: its table entry rides in lane 0 of the vector gather (bin 0 gets no comfort noise)
+// and the second set (profiles/r22_experiments.md), vector forms that are identities for every input:
+//  16  NLMS step: the zero fix-ups of three of its norms in fewer instructions (nlms_bin)
+//  32  delay estimator: the second history word kept clear above slot 99, so the far bit counts and the second key need no select
+//  64  Wiener gain / NLP: the echo filter's and supGain's norms without their +-1, the gain times 4 as one shift
+// 128  comfort noise: the tracking estimator's step up as shifts and adds, the noise amplitude's 24-bit product as the instruction itself
 // A kernel family takes them when its wave policy says so (W::kLean) AND it is not a W::kTight policy (the tick kernels, pinned
 // by tests/golden/tick_dense_fingerprints.json) AND it has no clean input: BlockEngine::kLeanItems.  No state, Regs or Uniform
 // member changes with the switch.  Policies without a kLean member (the lane simulator) follow AECM_LEAN_POLICY_DEFAULT.
 #ifndef AECM_LEAN_BLOCK
-#define AECM_LEAN_BLOCK 15
+#define AECM_LEAN_BLOCK 255
 #endif
 #ifndef AECM_LEAN_POLICY_DEFAULT
 #define AECM_LEAN_POLICY_DEFAULT 0
@@ -170,7 +175,15 @@ struct BlockEngine {
     // The lean block loop (AECM_LEAN_BLOCK): which items this instantiation takes.
     static constexpr int kLeanItems = (!W::kTight && !kHasClean && PolicyLean<W>::value) ? (AECM_LEAN_BLOCK) : 0;
     static constexpr bool kLeanDelayTail = (kLeanItems & 1) != 0, kLeanNarrowings = (kLeanItems & 2) != 0,
-                          kLeanNoise64 = (kLeanItems & 4) != 0, kLeanNarrowings2 = (kLeanItems & 8) != 0;
+                          kLeanNoise64 = (kLeanItems & 4) != 0, kLeanNarrowings2 = (kLeanItems & 8) != 0,
+                          kLeanNlmsNorms = (kLeanItems & 16) != 0, kLeanDelayKeys = (kLeanItems & 32) != 0,
+                          kLeanGainNorms = (kLeanItems & 64) != 0, kLeanNoiseTrack = (kLeanItems & 128) != 0;
+    // "some lane" of a lane condition, or the condition itself for bin 64: for the decision counters (AECM_LEAN_COUNT) only
+    template <class B>
+    static AECM_HD bool lean_any(const B &c) {
+        if constexpr (sizeof(B) <= sizeof(int)) return c != 0;      // bool, or the int two of them combine to
+        else return W::ballot(c) != 0;
+    }
 
     // Joint scaling tests of the inverse transform (fft128): per kernel family, because the duplicated stage bodies cost
     // registers.
@@ -641,7 +654,9 @@ struct BlockEngine {
         // leaves 16 bits: slots t and t + 64 are advanced together as the two halves of one word (r.m01, the layout of the
         // V_M01 state word), with packed 16-bit instructions.  Upper halves of lanes >= 36 (no slot) stay 0: their far
         // bit count is masked to 0, which freezes them.
-        const vi fb = popc(r.bh0) | shl(sel(valid1, popc(r.bh1), vi(0)), 16);                     // far_bit_counts
+        // lean: delay_block keeps the second history word 0 in the lanes without a slot, so its count needs no select
+        const vi fb = kLeanDelayKeys ? (popc(r.bh0) | shl(popc(r.bh1), 16))
+                                     : (popc(r.bh0) | shl(sel(valid1, popc(r.bh1), vi(0)), 16));  // far_bit_counts
         // lean: the far bit counts are non-zero exactly where a history word with a slot has a bit set -- one compare and one
         // 64-bit test instead of two compares, a mask, an or and a test
         if constexpr (kLeanDelayTail) any_far = W::ballot(fb != 0) != 0;
@@ -654,7 +669,15 @@ struct BlockEngine {
         // first minimum / maximum over the 100 means (:568-576): (mean << 7 | slot) is a total order
         const vi m0 = zext16(r.m01), m1 = lsr(r.m01, 16);
         vi key0 = shl(m0, 7) | r.lane;
-        vi key1 = sel(valid1, shl(m1, 7) | (r.lane + 64), vi(0x7fffffff));
+        vi key1;
+        if constexpr (kLeanDelayKeys) {
+            // The slot number and the "no slot" key are one lane constant: m1 << 7 < 2^23 has no bit that 0x7fffffff lacks, so or-ing
+            // it in leaves the lanes without a slot at 0x7fffffff -- the select of the other form.  (Formed from r.lane, which does
+            // not change in a launch: it takes the register that held lane + 64.)
+            key1 = shl(m1, 7) | sel(r.lane < vi(kHistory - 64), r.lane + 64, vi(0x7fffffff));
+        } else {
+            key1 = sel(valid1, shl(m1, 7) | (r.lane + 64), vi(0x7fffffff));
+        }
         int kmin, worst;
         W::reduce_min_max(imin(key0, key1), imax(m0, m1), kmin, worst);
         if constexpr (kLeanDelayTail) {
@@ -832,16 +855,27 @@ struct BlockEngine {
     // Channel update (reference aecm/aecm_core.cc:810-986)
     // ------------------------------------------------------------------------------------------
     // NLMS step of one bin (:831-921).  div_magic_k/div_shift_k: reciprocal of (bin index + 1).
-    template <class I>
+    // NormU32 in the lanes' short form or the plain one.  kUni below: the instantiation for bin 64 (wave-uniform operands; on the
+    // device I is int for both, so the type cannot tell them apart).
+    template <bool kVectorForm, class I>
+    static AECM_HD I nlms_norm_u32(I a) {
+        if constexpr (kVectorForm) return norm_u32_v(a);
+        else return norm_u32(a);
+    }
+    template <class I, bool kUni = false>
     static AECM_HD void nlms_bin(BinState<I> &s, I far, I dfa, I div_magic_k, I div_shift_k, int dfa_noisy_q, int far_q,
                                  int mu) {
-        I zeros_ch = norm_u32(s.ch_adapt32);                                                   // may be negative right after InitEchoPath
+        // lean: NormU32 (0 for 0) of the lanes as leading-zero count and one maximum (norm_u32_v)
+        constexpr bool kVecNorms = kLeanNlmsNorms && !kUni;
+        if constexpr (kLeanNlmsNorms) AECM_LEAN_COUNT(4, lean_any(s.ch_adapt32 == 0));
+        I zeros_ch = nlms_norm_u32<kVecNorms>(s.ch_adapt32);                                   // may be negative right after InitEchoPath
         I zeros_far = norm_u32_nn(far);                                                        // far is a uint16
         I shift_ch_far = imax(I(32) - zeros_ch - zeros_far, I(0));                            // :836-850: 0 when zeros_ch + zeros_far > 31
         // shift_ch_far == 32 only for ch_adapt32 == 0 (norm 0 by convention) and far == 0: the product is 0 either way,
         // and sar() takes its count modulo 32, so the reference's "shift 0 when the norms sum to 0" needs no select
         I u1 = mul(sar(s.ch_adapt32, shift_ch_far), far);
-        I zeros_num = norm_u32(u1);                                                           // :852-867
+        if constexpr (kLeanNlmsNorms) AECM_LEAN_COUNT(5, lean_any(u1 == 0));
+        I zeros_num = nlms_norm_u32<kVecNorms>(u1);                                           // :852-867
         I zeros_dfa = clz32(dfa);                                                             // NormU32, and 32 for dfa == 0 (:856-860)
         I t16 = as_i16(zeros_dfa - 2 + dfa_noisy_q - kResChannel32 - far_q + shift_ch_far);   // |.| < 128: counts, Q values
         // :861-867  "if (zerosNum > tmp16no1 + 1) { xfaQ = tmp16no1; dfaQ = zerosDfa - 2; } else { xfaQ = zerosNum - 2;
@@ -853,9 +887,16 @@ struct BlockEngine {
         u1 = shift_u31(u1, xfa_q);                                                            // :869-872; both counts lie in [-28, 30]
         I u2 = shift_u31(dfa, dfa_q);
         I t1 = sub(u2, u1);
-        zeros_num = norm_w32_nz(t1);                                                          // t1 == 0: no update, nothing below is used
+        if constexpr (!kLeanNlmsNorms) zeros_num = norm_w32_nz(t1);                           // t1 == 0: no update, nothing below is used
         auto update = (t1 != 0) & (far > shl(I(kChannelVad), far_q));                         // :873
-        I shift_num = imax(I(32) - (zeros_num + zeros_far), I(0));                            // :886-902: 0 when the sum > 31
+        I shift_num;                                                                          // :886-902: 0 when the sum > 31
+        if constexpr (kLeanNlmsNorms) {
+            // NormW32(t1) + 1 in two instructions: the sign-bit count is -1 for 0 and -1 and 1 + norm for everything else, and
+            // min_u32(count, 32) == min_u32(count - 1, 31) + 1 for each of those; the 1 goes into the constant
+            shift_num = imax(I(33) - (min_u32(ffbh_i(t1), I(32)) + zeros_far), I(0));
+        } else {
+            shift_num = imax(I(32) - (zeros_num + zeros_far), I(0));
+        }
         // |t1| < 2^30 (both aligned operands keep two bits of headroom, :852-872) and the shift above leaves the product
         // below 2^31, so the reference's sign juggling around its unsigned multiply (:886-902) and its truncating signed
         // division (:904) amount to: magnitude = (|t1| >> shift_num) * far, divide it, give it the sign of t1.
@@ -887,7 +928,7 @@ struct BlockEngine {
             // blocks with mu > 0 of the bench signal, instrumented lane simulator).  Below it nlms_bin leaves the channel alone,
             // so the ~50 scalar instructions of its update are skipped for one compare and a branch.
             if (AECM_STEADY_NEVER(far64 > shl(kChannelVad, far_q)))
-                nlms_bin<int>(r.b64, far64, dfa64, r.bin64_div_magic, r.bin64_div_shift, u.dfa_noisy_q, far_q, mu);
+                nlms_bin<int, true>(r.b64, far64, dfa64, r.bin64_div_magic, r.bin64_div_shift, u.dfa_noisy_q, far_q, mu);
         }
         if (AECM_STEADY_NEVER((u.startup == 0) & (u.cur_vad != 0))) {                         // :926-929
             store_adaptive_channel(r, far, far64, echo_est, echo_est64);
@@ -1009,8 +1050,20 @@ struct BlockEngine {
         }
 
         // echoFilt == 0: the product below is 0 whatever the regime and the gain is then ONE_Q14 (:582): its norm is never looked at
-        I zeros32 = norm_w32_nz(s.echo_filt) + 1;                                             // :527-550
-        int zeros16 = norm_w16(sup_gain) + 1;
+        I zeros32;                                                                            // :527-550
+        int zeros16;
+        if constexpr (kLeanGainNorms) {
+            // NormW32 + 1 is min_u32(sign-bit count, 32) for every operand (see nlms_bin).  supGain: this form of the function is
+            // only called with 0 < supGain <= 32767 where the gain-zero path exists (gain_block), and NormW16 + 1 of such a value
+            // is its sign-bit count less 16 -- no zero test, no minimum
+            AECM_LEAN_COUNT(7, lean_any(s.echo_filt == 0));
+            zeros32 = min_u32(ffbh_i(s.echo_filt), I(32));
+            // (not an identity for supGain <= 0: as_nonneg(sup_gain - 1) makes the host and audit builds check the precondition)
+            zeros16 = kGainZeroPath ? ffbh_i(as_nonneg(sup_gain - 1) + 1) - 16 : norm_w16(sup_gain) + 1;
+        } else {
+        zeros32 = norm_w32_nz(s.echo_filt) + 1;
+        zeros16 = norm_w16(sup_gain) + 1;
+        }
         I t16 = I(17) - zeros32 - zeros16;                                                    // :529: the "safe" regime is t16 <= 0
         int dq = clean_q - zeros_xbuf;
         I tpos = imax(t16, I(0));
@@ -1099,6 +1152,38 @@ struct BlockEngine {
         p_im = mul24(opaque_v(neg(n8)), W::sin360(idx));                  // opaque: a plain negation, not one redone in 24 bits
     }
 
+    // noise_bin<I, true, kSilent, kNoLookup> in its lean form (AECM_LEAN_BLOCK bit 128), a function of its own so that noise_bin and
+    // its instantiations stay what they were for every other kernel.  kUni: the call for bin 64 (on the device I is int for both).
+    template <class I, bool kSilent, bool kNoLookup, bool kUni>
+    static AECM_HD void noise_bin_tracking_lean(BinState<I> &s, I dfa, I hnl, I rnd, I gate, int shift_n, int min_track, I &p_re, I &p_im) {
+        I in = shl(dfa, shift_n);                                                             // :81-127
+        auto lt = in < s.noise_est;
+        I ne_lt = sub(s.noise_est, sar(sub(s.noise_est, in), min_track));
+        // The step up's two products as shifts and adds.  With hi = est >> 11:  hi * 2049 == (hi << 11) + hi modulo 2^32, and below
+        // 2^19 (est * 2049) >> 11 == est + hi, because est * 2048 is a multiple of 2^11 and the product stays below 2^30.
+        // "est >> 19 > 0" is est > 2^19 - 1 for either sign.  No mask, no bit-field extract, no multiply.
+        const I hi = sar(s.noise_est, 11);
+        I ne_ge = sel(s.noise_est > 0x7ffff, shl_add(hi, 11, hi), add(s.noise_est, hi));
+        I ne = sel(lt, ne_lt, ne_ge);
+        s.low_ctr = sel(lt, I(0), s.low_ctr);
+        s.high_ctr = sel(lt, s.high_ctr, I(0));
+        I t32 = sar(ne, shift_n);                                                             // :129-140
+        auto clamp = t32 > 32767;
+        t32 = sel(clamp, I(32767), t32);
+        s.noise_est = sel(clamp, shl(I(32767), shift_n), ne);
+        if constexpr (kSilent) return;
+        // The gain reaches this point opaque (gain_block), so __mul24 keeps its sign extension of ONE_Q14 - hnl -- (x << 8) >> 8
+        // around the subtraction; the instruction reads the low 24 bits by itself (mul24_insn).  Bin 64: a scalar multiply.
+        const I amp = as_i16(I(kOneQ14) - hnl), level = as_i16(t32);                          // 0 <= hnl <= 2^14, 0 <= t32 <= 32767
+        I n16 = as_i16(sar(kUni ? mul(amp, level) : mul24_insn(amp, level), 14));
+        n16 = n16 & gate;                                                                     // bin 0 gets no comfort noise (:146-147)
+        I idx = as_i16(sar(mul24(I(359), rnd), 15));                                            // :150
+        const I n8 = shl(n16, 3);                                                             // :153-156, see noise_bin
+        if constexpr (kNoLookup) { p_re = n8; p_im = idx; return; }
+        p_re = mul24(n8, W::cos360(idx));
+        p_im = mul24(opaque_v(neg(n8)), W::sin360(idx));
+    }
+
     // cos360 of lane 0's index as a wave-uniform value: the policy's own way where it has one (the device reads the table word out
     // of lane 0 and narrows it on the scalar unit), else the lane vector's element.
     template <class P>
@@ -1130,8 +1215,13 @@ struct BlockEngine {
         const bool tracking = kNoiseTrackingFastPath && (W::ballot(r.b.noise_est > vi(2047)) == ~0ull) & (r.b64.noise_est > 2047);
         constexpr bool kShared = kLeanNoise64 && !kSilent;       // bin 64's table entry comes with the lanes' (below)
         if (AECM_STEADY_ALWAYS(AECM_LIKELY(tracking))) {
+            if constexpr (kLeanNoiseTrack) {
+                noise_bin_tracking_lean<vi, kSilent, kShared, false>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
+                noise_bin_tracking_lean<int, kSilent, kShared, true>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
+            } else {
             noise_bin<vi, true, kSilent, kShared>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
             noise_bin<int, true, kSilent, kShared>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
+            }
         } else {
             noise_bin<vi, false, kSilent, kShared>(r.b, clean.mag, hnl, rnd, gate, shift_n, min_track, p_re, p_im);
             noise_bin<int, false, kSilent, kShared>(r.b64, clean.mag64, hnl64, rnd64, -1, shift_n, min_track, p_re64, p_im64);
@@ -1489,6 +1579,9 @@ struct BlockEngine {
             int carry = W::readlane(r.bh0, 63);
             r.bh0 = W::shift_up1(r.bh0, word);
             r.bh1 = W::shift_up1(r.bh1, carry);
+            // lean: slot 99's word moves up into lane 36, which has no slot (delay_estimator.cc:369-382 drops it); cleared here
+            // (one v_writelane), every lane above stays 0 as load_state left it and process_binary needs no mask for them
+            if constexpr (kLeanDelayKeys) r.bh1 = W::writelane(r.bh1, 0, kHistory - 64);
         }
         AECM_PHASE_MARK(3, r.bh0, r.mean);
         W::template phase_priority<4>();
@@ -1651,7 +1744,8 @@ struct BlockEngine {
         // :680-685  efw = (dfw * hnl + 8192) >> 14 (|dfw| <= 2^15, 0 <= hnl <= 2^14: an int16).  With the gain times 4 the wanted 16 bits
         // are the upper half of dfw * (hnl << 2) + 32768 (|.| <= 2^31, exact in 32 bits), and one byte permute packs both parts
         {
-            const vi hnl4 = shl(hnl, 2);
+            // lean: the shifted gain opaque as well -- seen through, the 24-bit multiplies make it (hnl << 10) >> 8, two shifts
+            const vi hnl4 = kLeanGainNorms ? opaque_v(shl(hnl, 2)) : shl(hnl, 2);
             e = pack_hi16(add(mul24(clean.re, hnl4), 32768), add(mul24(clean.im, hnl4), 32768));
         }
         e_re64 = sext16(sar(mul(clean.re64, hnl64) + 8192, 14));
