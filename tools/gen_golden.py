@@ -209,6 +209,17 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", fs=fs, names=np.array([c["name"] for c in cases]),
                             **cs.summary(cases, out, codes, np.stack([r.get_echo_path()[1] for r in refs])))
         print("sesscorpus", fs, len(cases), "sessions", len(ops), "ticks")
+    # The session-flow corpus (tests/flow_corpus.py): every object of it, one reference instance per session at the session's rate and
+    # call sizes.  Kept: a SHA-256 of every session's output, the non-zero codes and the final echo paths.
+    import flow_corpus as fc
+    for family, name in fc.GOLDEN_NAMES.items():
+        if only and only not in name:
+            continue
+        sch = fc.family_schedule(family)
+        far, near = fc.signals(sch)
+        out, codes, paths = fc.drive_reference(sch, far, near, lambda rate: pyoracle.RefSession(rate, 1, 3))
+        np.savez_compressed(GOLD / f"{name}.npz", **fc.summary(out, codes, paths))
+        print("sessflow", family, out.shape, "codes", int((codes != 0).sum()))
     from helpers import stream_config
     for name, S, nb, fs, seed0 in RAGGED_CASES:
         if only and only not in name:

@@ -28,6 +28,30 @@
 #define AECM_FLOW_HD inline
 #endif
 
+// Every data-dependent decision of the Flow* functions below carries a marker, AECM_FLOW_MARK(id, outcome) -- in the style of
+// AECM_LEAN_COUNT (aecm_wave.h).  It expands to nothing in every build but the coverage harness (tests/sim/sim_flowcov.cpp defines
+// it before including this header), which records (decision, outcome) per tick and session: tools/flow_coverage.py computes from
+// that record whether two sessions of one wavefront of a planning kernel ever disagreed on a decision within one launch, which
+// branch counters cannot say.  AECM_FLOW_MARK_IF(guard, ...) marks a decision that is only evaluated under `guard` (the second
+// operand of a || or &&).  The outcome expressions repeat the conditions next to them and have no side effects.
+#ifndef AECM_FLOW_MARK
+#define AECM_FLOW_MARK(id, outcome) ((void)0)
+#define AECM_FLOW_MARK_IF(guard, id, outcome) ((void)0)
+#endif
+#define AECM_FLOW_DECISIONS(X) \
+    X(MRP_BY_READABLE) X(MRP_BY_FREE) X(DC_FIRES) X(DC_NADD_FLOOR) X(DC_NADD_CEILING) X(FC_STARTUP) X(FC_TRUNCATED) X(FC_NOTHING_FITS) \
+    X(BB_OFFERED_FITS) X(BB_IN_ROW) X(BB_AGED) X(EB_SHORT) X(EB_ACC_NOT_POSITIVE) X(EB_DIFF_HIGH) X(EB_HIGH_LAST_LOW) X(EB_DIFF_LOW) \
+    X(EB_KNOWN_POSITIVE) X(EB_LOW_LAST_HIGH) X(EB_CHANGE) X(EB_KNOWN_FLOOR) X(SU_CHECKING) X(SU_COUNTER_ZERO) X(SU_D_NEGATIVE) X(SU_TOL_ABS) \
+    X(SU_TOL_REL) X(SU_COUNTER_LIMIT) X(SU_CLAMP_MEAN) X(SU_CTR_LIMIT) X(SU_CLAMP_LAST) X(SU_CHECKED) X(SU_FILLED_EQ) X(SU_FILLED_GT) \
+    X(RS_LAGGING) X(MN_SAME_PLACE) X(MN_BACKWARDS) X(LS_WAVE_BEFORE) X(T_FS16) X(T_SPLIT_FLAG) X(T_SPLIT_N) X(T_SPILL_IN_ROW) X(T_SPILL_AGED) \
+    X(T_MS_NEGATIVE) X(T_MS_HIGH) X(T_NO_SECOND_CALL) X(T_NO_FAREND) X(T_STARTUP) X(T_NO_SECOND_FRAME) X(T_FRESH) X(T_REPLAY_IN_RING) X(T_EST) \
+    X(T_FROM_STREAM) X(T_NEW_RUN) X(T_TWO_BLOCKS) X(T_STUFF) X(T_SPILL_SET) X(T_SPILL_NOT_REFRESHED) X(T_ACTIVE0) X(T_ACTIVE1) X(T_DIRECT) \
+    X(T_FF_WAS_DIRECT) X(T_LEFT_PENDING) X(TM_HALF_FLAG) X(TM_HALF_N) X(PK_HALF_FLAG) X(PK_HALF_N) X(K_LIVE) X(K_RESYNC)
+#define AECM_FLOW_DECISION_ENUM(name) FD_##name,
+namespace aecm {
+enum FlowDecision : int { AECM_FLOW_DECISIONS(AECM_FLOW_DECISION_ENUM) kFlowDecisions };   // K_*: decisions of the planning kernels' own text
+}
+
 namespace aecm {
 
 // One session's wrapper state: kFlowFieldsUsed int32, stored field-major on the device (state[field * S + session],
@@ -169,7 +193,9 @@ AECM_FLOW_HD int FlowStateDefect(const int32_t v[kFlowWords]) {
 AECM_FLOW_HD void FlowMoveFarReadPtr(FlowRegs &s, int32_t n) {
     const int32_t readable = (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]);
     const int32_t free_elems = kFlowJitterCapacity - readable;
+    AECM_FLOW_MARK(FD_MRP_BY_READABLE, n > readable);
     n = FlowMin(n, readable);
+    AECM_FLOW_MARK(FD_MRP_BY_FREE, n < -free_elems);
     n = FlowMax(n, -free_elems);
     s.v[F_FAR_RP] = (int32_t)((uint32_t)s.v[F_FAR_RP] + (uint32_t)n);
 }
@@ -179,8 +205,11 @@ AECM_FLOW_HD void FlowDelayComp(FlowRegs &s, int mult) {
     const int32_t n_samp_far = (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]);
     const int32_t n_samp_snd_card = s.v[F_MS] * 8 * mult;
     const int32_t delay_new = n_samp_snd_card - n_samp_far;
+    AECM_FLOW_MARK(FD_DC_FIRES, delay_new > 256 - kFlowFrame * mult);
     if (delay_new > 256 - kFlowFrame * mult) {
+        AECM_FLOW_MARK(FD_DC_NADD_FLOOR, (n_samp_snd_card >> 1) - n_samp_far < kFlowFrame);
         int32_t n_add = FlowMax((n_samp_snd_card >> 1) - n_samp_far, kFlowFrame);
+        AECM_FLOW_MARK(FD_DC_NADD_CEILING, n_add > 10 * kFlowFrame);
         n_add = FlowMin(n_add, 10 * kFlowFrame);
         FlowMoveFarReadPtr(s, -n_add);
         s.v[F_DELAY_CHANGE] = 1;
@@ -191,8 +220,11 @@ AECM_FLOW_HD void FlowDelayComp(FlowRegs &s, int mult) {
 // the jitter buffer takes what fits -- a full buffer drops the rest (ring_buffer.c:142-150).  Returns the number of
 // samples accepted; they land at far-stream positions [F_FAR_WP before the call, + accepted).
 AECM_FLOW_HD int32_t FlowFarendCall(FlowRegs &s, int mult, int len) {
+    AECM_FLOW_MARK(FD_FC_STARTUP, s.v[F_EC_STARTUP] != 0);
     if (!s.v[F_EC_STARTUP]) FlowDelayComp(s, mult);
     const int32_t readable = (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]);
+    AECM_FLOW_MARK(FD_FC_TRUNCATED, len > kFlowJitterCapacity - readable);
+    AECM_FLOW_MARK(FD_FC_NOTHING_FITS, readable == kFlowJitterCapacity);
     const int32_t accepted = FlowMin(len, kFlowJitterCapacity - readable);
     s.v[F_FAR_WP] = (int32_t)((uint32_t)s.v[F_FAR_WP] + (uint32_t)accepted);
     return accepted;
@@ -212,9 +244,12 @@ struct FlowBurst {
 AECM_FLOW_HD void FlowBurstBegin(FlowRegs &s, int len, int calls, FlowBurst &b) {
     const int32_t readable = (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]);
     const int64_t offered = (int64_t)len * calls;
+    AECM_FLOW_MARK(FD_BB_OFFERED_FITS, offered < (int64_t)(kFlowJitterCapacity - readable));
     const int32_t most = (int32_t)(offered < (int64_t)(kFlowJitterCapacity - readable) ? offered : (int64_t)(kFlowJitterCapacity - readable));
     for (int i = 0; i < 2; ++i) {
         b.spill_pos[i] = (uint32_t)s.v[F_OLD_POS0 + i];
+        AECM_FLOW_MARK(FD_BB_IN_ROW, s.v[F_OLD_ROW0 + i] != 0);
+        AECM_FLOW_MARK_IF(!s.v[F_OLD_ROW0 + i], FD_BB_AGED, (int32_t)((uint32_t)s.v[F_FAR_WP] + (uint32_t)most - (uint32_t)s.v[F_OLD_POS0 + i]) > kFlowOldAge);
         b.spill[i] = !s.v[F_OLD_ROW0 + i] && (int32_t)((uint32_t)s.v[F_FAR_WP] + (uint32_t)most - (uint32_t)s.v[F_OLD_POS0 + i]) > kFlowOldAge;
         if (b.spill[i]) s.v[F_OLD_ROW0 + i] = 1;
     }
@@ -233,13 +268,20 @@ AECM_FLOW_HD void FlowEstBufDelay(FlowRegs &s, int mult) {
     const int32_t n_samp_far = FlowAsShort((int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]));
     const int32_t n_samp_snd_card = FlowAsShort(s.v[F_MS] * 8 * mult);
     int32_t delay_new = FlowAsShort(n_samp_snd_card - n_samp_far);
+    AECM_FLOW_MARK(FD_EB_SHORT, delay_new < kFlowFrame);
     if (delay_new < kFlowFrame) {
         FlowMoveFarReadPtr(s, kFlowFrame);
         delay_new = FlowAsShort(delay_new + kFlowFrame);
     }
     const int32_t acc = 8 * s.v[F_FILT_DELAY] + 2 * delay_new;            // C division truncates towards zero; negative -> max(0, .) = 0
+    AECM_FLOW_MARK(FD_EB_ACC_NOT_POSITIVE, acc <= 0);
     s.v[F_FILT_DELAY] = FlowAsShort(acc <= 0 ? 0 : (int32_t)((uint32_t)acc / 10u));
     const int32_t diff = FlowAsShort(s.v[F_FILT_DELAY] - s.v[F_KNOWN_DELAY]);
+    AECM_FLOW_MARK(FD_EB_DIFF_HIGH, diff > 224);
+    AECM_FLOW_MARK_IF(diff > 224, FD_EB_HIGH_LAST_LOW, s.v[F_LAST_DELAY_DIFF] < 96);
+    AECM_FLOW_MARK_IF(!(diff > 224), FD_EB_DIFF_LOW, diff < 96);
+    AECM_FLOW_MARK_IF(!(diff > 224) && diff < 96, FD_EB_KNOWN_POSITIVE, s.v[F_KNOWN_DELAY] > 0);
+    AECM_FLOW_MARK_IF(!(diff > 224) && diff < 96 && s.v[F_KNOWN_DELAY] > 0, FD_EB_LOW_LAST_HIGH, s.v[F_LAST_DELAY_DIFF] > 224);
     if (diff > 224) {
         s.v[F_TIME_FOR_DELAY_CHANGE] = s.v[F_LAST_DELAY_DIFF] < 96 ? 0 : s.v[F_TIME_FOR_DELAY_CHANGE] + 1;
     } else if (diff < 96 && s.v[F_KNOWN_DELAY] > 0) {
@@ -248,6 +290,8 @@ AECM_FLOW_HD void FlowEstBufDelay(FlowRegs &s, int mult) {
         s.v[F_TIME_FOR_DELAY_CHANGE] = 0;
     }
     s.v[F_LAST_DELAY_DIFF] = diff;
+    AECM_FLOW_MARK(FD_EB_CHANGE, s.v[F_TIME_FOR_DELAY_CHANGE] > 25);
+    AECM_FLOW_MARK_IF(s.v[F_TIME_FOR_DELAY_CHANGE] > 25, FD_EB_KNOWN_FLOOR, s.v[F_FILT_DELAY] - 160 < 0);
     if (s.v[F_TIME_FOR_DELAY_CHANGE] > 25) s.v[F_KNOWN_DELAY] = FlowMax(s.v[F_FILT_DELAY] - 160, 0);
 }
 
@@ -257,8 +301,10 @@ AECM_FLOW_HD void FlowStartup(FlowRegs &s, int mult, int n_frames) {
     const int32_t avail = (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]);
     const int32_t filled = FlowAsShort(FlowAsShort(avail) / kFlowFrame);
     const int32_t ms = s.v[F_MS];
+    AECM_FLOW_MARK(FD_SU_CHECKING, s.v[F_CHECK_BUFF_SIZE] != 0);
     if (s.v[F_CHECK_BUFF_SIZE]) {
         s.v[F_CHECK_BUF_SIZE_CTR] = FlowAsShort(s.v[F_CHECK_BUF_SIZE_CTR] + 1);
+        AECM_FLOW_MARK(FD_SU_COUNTER_ZERO, s.v[F_COUNTER] == 0);
         if (s.v[F_COUNTER] == 0) {
             s.v[F_FIRST_VAL] = ms;
             s.v[F_SUM] = 0;
@@ -266,7 +312,10 @@ AECM_FLOW_HD void FlowStartup(FlowRegs &s, int mult, int n_frames) {
         // |firstVal - ms| < max(0.2 * ms, 8.0) in doubles (:310-312): 0.2 * ms rounds to ms / 5 exactly whenever that is an
         // integer (ms <= 510), so the comparison with an integer is d < 8 || 5 d < ms.
         int32_t d = s.v[F_FIRST_VAL] - ms;
+        AECM_FLOW_MARK(FD_SU_D_NEGATIVE, d < 0);
         d = d < 0 ? -d : d;
+        AECM_FLOW_MARK(FD_SU_TOL_ABS, d < 8);
+        AECM_FLOW_MARK_IF(!(d < 8), FD_SU_TOL_REL, 5 * d < ms);
         if (d < 8 || 5 * d < ms) {
             s.v[F_SUM] = FlowAsShort(s.v[F_SUM] + ms);
             s.v[F_COUNTER] = FlowAsShort(s.v[F_COUNTER] + 1);
@@ -276,15 +325,22 @@ AECM_FLOW_HD void FlowStartup(FlowRegs &s, int mult, int n_frames) {
         // Both comparisons are made in size_t in the reference (short counter * size_t nBlocks10ms, :320,:330): a counter
         // that has wrapped negative -- more than 32 767 start-up calls of 80 samples at 16 kHz, where nBlocks10ms is 0 and
         // neither limit can fire -- is a huge unsigned product there.
+        AECM_FLOW_MARK(FD_SU_COUNTER_LIMIT, (uint64_t)(int64_t)s.v[F_COUNTER] * (uint64_t)n_blocks_10ms >= 6u);
         if ((uint64_t)(int64_t)s.v[F_COUNTER] * (uint64_t)n_blocks_10ms >= 6u) {
+            AECM_FLOW_MARK(FD_SU_CLAMP_MEAN, (3 * s.v[F_SUM] * mult) / (s.v[F_COUNTER] * 40) > 50);
             s.v[F_BUF_SIZE_START] = FlowAsShort(FlowMin((3 * s.v[F_SUM] * mult) / (s.v[F_COUNTER] * 40), 50));
             s.v[F_CHECK_BUFF_SIZE] = 0;
         }
+        AECM_FLOW_MARK(FD_SU_CTR_LIMIT, (uint64_t)(int64_t)s.v[F_CHECK_BUF_SIZE_CTR] * (uint64_t)n_blocks_10ms > 50u);
         if ((uint64_t)(int64_t)s.v[F_CHECK_BUF_SIZE_CTR] * (uint64_t)n_blocks_10ms > 50u) {
+            AECM_FLOW_MARK(FD_SU_CLAMP_LAST, (3 * ms * mult) / 40 > 50);
             s.v[F_BUF_SIZE_START] = FlowAsShort(FlowMin((3 * ms * mult) / 40, 50));
             s.v[F_CHECK_BUFF_SIZE] = 0;
         }
     }
+    AECM_FLOW_MARK(FD_SU_CHECKED, !s.v[F_CHECK_BUFF_SIZE]);
+    AECM_FLOW_MARK_IF(!s.v[F_CHECK_BUFF_SIZE], FD_SU_FILLED_EQ, filled == s.v[F_BUF_SIZE_START]);
+    AECM_FLOW_MARK_IF(!s.v[F_CHECK_BUFF_SIZE] && filled != s.v[F_BUF_SIZE_START], FD_SU_FILLED_GT, filled > s.v[F_BUF_SIZE_START]);
     if (!s.v[F_CHECK_BUFF_SIZE]) {
         if (filled == s.v[F_BUF_SIZE_START]) {
             s.v[F_EC_STARTUP] = 0;
@@ -312,6 +368,7 @@ struct FlowNearMove {          // near ring (and clean ring) positions [src, src
 };
 AECM_FLOW_HD void FlowResync(FlowRegs &s, uint32_t near_pos, FlowNearMove &m) {
     const uint32_t pending = (uint32_t)s.v[F_FRM_POS] - (uint32_t)s.v[F_BLK_POS];
+    AECM_FLOW_MARK(FD_RS_LAGGING, s.v[F_NEAR_LAG] != 0);
     m.count = s.v[F_NEAR_LAG] != 0 ? (int32_t)pending : 0;
     m.dst = near_pos - pending;
     m.src = m.dst - (uint32_t)s.v[F_NEAR_LAG];
@@ -323,7 +380,9 @@ AECM_FLOW_HD void FlowResync(FlowRegs &s, uint32_t near_pos, FlowNearMove &m) {
 template <class T>
 AECM_FLOW_HD void FlowMoveNear(T *ring, uint32_t mask, const FlowNearMove &m) {
     const uint32_t d = (m.dst - m.src) & mask;
+    AECM_FLOW_MARK(FD_MN_SAME_PLACE, d == 0);
     if (d == 0) return;
+    AECM_FLOW_MARK(FD_MN_BACKWARDS, d < (uint32_t)m.count);
     if (d < (uint32_t)m.count) {
         for (int32_t k = m.count - 1; k >= 0; --k) ring[(m.dst + (uint32_t)k) & mask] = ring[(m.src + (uint32_t)k) & mask];
     } else {
@@ -408,7 +467,10 @@ static_assert(kFlowIdle == 4, "FlowLiveBlockBases counts bit 2");
 // wave_counts[w] = live lanes of wavefront w of the workgroup, ballot = the live lanes of this lane's wavefront.
 AECM_FLOW_HD uint32_t FlowLiveSlot(uint32_t block_base, const uint32_t wave_counts[kFlowPlanBlock / 64], int wave, uint64_t ballot, int lane) {
     uint32_t slot = block_base;
-    for (int w = 0; w < kFlowPlanBlock / 64; ++w) slot += w < wave ? wave_counts[w] : 0u;
+    for (int w = 0; w < kFlowPlanBlock / 64; ++w) {
+        AECM_FLOW_MARK(FD_LS_WAVE_BEFORE, w < wave);
+        slot += w < wave ? wave_counts[w] : 0u;
+    }
     const uint64_t below = ballot & ((uint64_t(1) << lane) - 1u);
     return slot + (uint32_t)__builtin_popcountll(below);
 }
@@ -417,7 +479,10 @@ AECM_FLOW_HD uint32_t FlowLiveSlot(uint32_t block_base, const uint32_t wave_coun
 // (kFlowSplitCalls, n = 160).  ms = the caller's msInSndCardBuf, near_pos = near-ring position of the tick's first
 // near-end sample.  Advances s and fills the plan.  The session is in step (F_NEAR_LAG == 0; FlowResync first otherwise).
 AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32_t near_pos, FlowPlan &p) {
+    AECM_FLOW_MARK(FD_T_FS16, fs == 16000);
     const int mult = fs == 16000 ? 2 : 1;
+    AECM_FLOW_MARK(FD_T_SPLIT_FLAG, (flags & kFlowSplitCalls) != 0);
+    AECM_FLOW_MARK_IF((flags & kFlowSplitCalls) != 0, FD_T_SPLIT_N, n == 2 * kFlowFrame);
     const bool split = (flags & kFlowSplitCalls) != 0 && n == 2 * kFlowFrame;
     const int n_calls = split ? 2 : 1;
     const int len = split ? kFlowFrame : n;
@@ -437,10 +502,14 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
     int32_t refreshed[2] = {0, 0};
     for (int i = 0; i < 2; ++i) {
         p.spill_pos[i] = (uint32_t)s.v[F_OLD_POS0 + i];
+        AECM_FLOW_MARK(FD_T_SPILL_IN_ROW, s.v[F_OLD_ROW0 + i] != 0);
+        AECM_FLOW_MARK_IF(!s.v[F_OLD_ROW0 + i], FD_T_SPILL_AGED, (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_OLD_POS0 + i]) > kFlowOldAge);
         p.spill[i] = !s.v[F_OLD_ROW0 + i] && (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_OLD_POS0 + i]) > kFlowOldAge;
     }
     for (int f = 0; f < 2; ++f) p.frame[f] = FlowFrame{0, 0, 0u, 0, 0u, 0, 0u};
     for (int c = 0; c < 2; ++c) p.far[c] = FlowFarPiece{c * len, 0, (uint32_t)s.v[F_FAR_WP]};
+    AECM_FLOW_MARK(FD_T_MS_NEGATIVE, ms < 0);
+    AECM_FLOW_MARK_IF(!(ms < 0), FD_T_MS_HIGH, ms > 500);
     ms = ms < 0 ? 0 : ms > 500 ? 500 : ms;                                                   // :258-265 (the warning is the host's business)
     // Frame slot of frame i of call c: c * frames_per_call + i = c + i for the three shapes there are (1 x 1, 1 x 2,
     // 2 x 1); both loops have constant bounds so that the plan stays in registers on the device.
@@ -448,14 +517,17 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
 #pragma unroll
 #endif
     for (int c = 0; c < 2; ++c) {
+        AECM_FLOW_MARK_IF(c == 1, FD_T_NO_SECOND_CALL, c >= n_calls);
         if (c >= n_calls) break;
         // ---- WebRtcAecm_BufferFarend (:215-234) ----
+        AECM_FLOW_MARK(FD_T_NO_FAREND, (flags & kFlowNoFarend) != 0);
         if (!(flags & kFlowNoFarend)) {
             p.far[c].pos = (uint32_t)s.v[F_FAR_WP];
             p.far[c].count = FlowFarendCall(s, mult, len);
         }
         // ---- WebRtcAecm_Process (:236-408) ----
         s.v[F_MS] = ms + 10;
+        AECM_FLOW_MARK(FD_T_STARTUP, s.v[F_EC_STARTUP] != 0);
         if (s.v[F_EC_STARTUP]) {
             FlowStartup(s, mult, frames_per_call);
             continue;
@@ -464,11 +536,14 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
 #pragma unroll
 #endif
         for (int i = 0; i < 2; ++i) {
+            AECM_FLOW_MARK_IF(i == 1, FD_T_NO_SECOND_FRAME, i >= frames_per_call);
             if (i >= frames_per_call) break;
             FlowFrame &fr = p.frame[(c + i) & 1];
             fr.active = 1;
             fr.old_idx = i;
             const int32_t avail = (int32_t)((uint32_t)s.v[F_FAR_WP] - (uint32_t)s.v[F_FAR_RP]);
+            AECM_FLOW_MARK(FD_T_FRESH, FlowAsShort(FlowAsShort(avail) / kFlowFrame) > 0);
+            AECM_FLOW_MARK_IF(!(FlowAsShort(FlowAsShort(avail) / kFlowFrame) > 0), FD_T_REPLAY_IN_RING, !s.v[F_OLD_ROW0 + i]);
             if (FlowAsShort(FlowAsShort(avail) / kFlowFrame) > 0) {                              // :369-375
                 fr.far_from_stream = 1;
                 fr.far_pos = (uint32_t)s.v[F_FAR_RP];
@@ -480,9 +555,12 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
                 fr.far_from_stream = 1;
                 fr.far_pos = (uint32_t)s.v[F_OLD_POS0 + i];
             }
+            AECM_FLOW_MARK(FD_T_EST, (i == 0 && fs == 8000) || (i == 1 && fs == 16000));
             if ((i == 0 && fs == 8000) || (i == 1 && fs == 16000)) FlowEstBufDelay(s, mult);   // :384-387
             // WebRtcAecm_ProcessFrame (aecm_core.cc:501-572); the core's far delay line is a pass-through (knownDelay 0)
             fr.frm_pos = (uint32_t)s.v[F_FRM_POS];
+            AECM_FLOW_MARK(FD_T_FROM_STREAM, fr.far_from_stream != 0);
+            AECM_FLOW_MARK_IF(fr.far_from_stream != 0, FD_T_NEW_RUN, (int32_t)(fr.far_pos - fr.frm_pos) != s.v[F_RUN_DELTA]);
             if (fr.far_from_stream) {                       // does this frame continue the run of the far stream the previous one ended?
                 const int32_t delta = (int32_t)(fr.far_pos - fr.frm_pos);
                 if (delta != s.v[F_RUN_DELTA]) {
@@ -499,17 +577,27 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
                 s.v[F_BLK_POS] = (int32_t)((uint32_t)s.v[F_BLK_POS] + (uint32_t)kFlowBlock);
                 ++nb;
             }
+            AECM_FLOW_MARK(FD_T_TWO_BLOCKS, nb == 2);                                            // the loop's trip count: 1 or 2
             fr.n_blocks = nb;
             p.n_blocks += nb;
             const int32_t size = (int32_t)((uint32_t)s.v[F_BLK_POS] - (uint32_t)s.v[F_OUT_RP]);
+            AECM_FLOW_MARK(FD_T_STUFF, size < kFlowFrame);
             if (size < kFlowFrame) s.v[F_OUT_RP] = (int32_t)((uint32_t)s.v[F_BLK_POS] - (uint32_t)kFlowFrame);   // stuffing (:559-562)
             fr.out_pos = (uint32_t)s.v[F_OUT_RP];
             s.v[F_OUT_RP] = (int32_t)(fr.out_pos + (uint32_t)kFlowFrame);
         }
     }
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
+        AECM_FLOW_MARK(FD_T_SPILL_SET, p.spill[i] != 0);
+        AECM_FLOW_MARK_IF(p.spill[i] != 0, FD_T_SPILL_NOT_REFRESHED, !refreshed[i]);
         if (p.spill[i] && !refreshed[i]) s.v[F_OLD_ROW0 + i] = 1;
+    }
+    AECM_FLOW_MARK(FD_T_ACTIVE0, p.frame[0].active != 0);
+    AECM_FLOW_MARK_IF(!p.frame[0].active, FD_T_ACTIVE1, p.frame[1].active != 0);
     if (p.frame[0].active || p.frame[1].active) {          // every active frame completes at least one block
+        AECM_FLOW_MARK(FD_T_DIRECT, (int32_t)((uint32_t)s.v[F_RUN_POS] - p.blk_pos0) <= 0);
+        AECM_FLOW_MARK_IF(!((int32_t)((uint32_t)s.v[F_RUN_POS] - p.blk_pos0) <= 0), FD_T_FF_WAS_DIRECT, !s.v[F_FF_VALID]);
+        AECM_FLOW_MARK_IF(!((int32_t)((uint32_t)s.v[F_RUN_POS] - p.blk_pos0) <= 0) && !s.v[F_FF_VALID], FD_T_LEFT_PENDING, frm_start != p.blk_pos0);
         if ((int32_t)((uint32_t)s.v[F_RUN_POS] - p.blk_pos0) <= 0) {
             p.direct = 1;
             p.far_delta = (uint32_t)s.v[F_RUN_DELTA];
@@ -532,6 +620,8 @@ AECM_FLOW_HD void FlowTick(FlowRegs &s, int fs, int n, int ms, int flags, uint32
 // of the tick's near-end samples at the object's position; the second half lands ahead of the session's own position, where
 // the next call's resync and append overwrite it before any block asks for it (tests/sim/sim_mixed.cpp).
 AECM_FLOW_HD void FlowTickMixed(FlowRegs &s, int fs, int n, int ms, int flags, uint32_t near_pos, FlowPlan &p) {
+    AECM_FLOW_MARK(FD_TM_HALF_FLAG, (flags & kFlowHalfCall) != 0);
+    AECM_FLOW_MARK_IF((flags & kFlowHalfCall) != 0, FD_TM_HALF_N, n == 2 * kFlowFrame);
     const bool half = (flags & kFlowHalfCall) != 0 && n == 2 * kFlowFrame;
     FlowTick(s, fs, half ? kFlowFrame : n, ms, flags & (kFlowNoFarend | kFlowSplitCalls), near_pos, p);
     if (half) s.v[F_NEAR_LAG] = FlowIdleTick(s.v[F_NEAR_LAG], kFlowFrame);
@@ -562,7 +652,11 @@ static_assert(kFlowMaxTickCalls * 2 * kFlowFrame < kFlowFarRing - kFlowJitterCap
 // (each plan carries the call size in n_frames); once, at the end, the samples of the tick the session did not consume become its
 // lag: K * 80 for a session that made half calls, exactly as after K ordinary half-call ticks.  The session is in step at entry
 // (FlowResync ONCE, before the first call, otherwise).  flags: kFlowNoFarend and kFlowHalfCall count.
-AECM_FLOW_HD int FlowPacketCallSize(int n, int flags) { return (flags & kFlowHalfCall) != 0 && n == 2 * kFlowFrame ? kFlowFrame : n; }
+AECM_FLOW_HD int FlowPacketCallSize(int n, int flags) {
+    AECM_FLOW_MARK(FD_PK_HALF_FLAG, (flags & kFlowHalfCall) != 0);
+    AECM_FLOW_MARK_IF((flags & kFlowHalfCall) != 0, FD_PK_HALF_N, n == 2 * kFlowFrame);
+    return (flags & kFlowHalfCall) != 0 && n == 2 * kFlowFrame ? kFlowFrame : n;
+}
 template <class Sink>
 AECM_FLOW_HD void FlowTickPackets(FlowRegs &s, int fs, int n, int calls, int ms, int flags, uint32_t near_pos, Sink &&sink) {
     const int n_s = FlowPacketCallSize(n, flags);
