@@ -227,6 +227,43 @@ enum {
      * exactly the launches it takes without this flag. */
     AECM_SESSION_HALF_CALL = 8
 };
+enum {
+    /* A clean near-end input PER SESSION -- one object per clock, not per kind of call: behind one 10 ms clock some calls sit behind a
+     * noise suppressor and some do not.  On a tick that passes near_clean, this session's WebRtcAecm_Process is called with
+     * nearendClean = NULL: its near_clean row is not read (it may hold anything), its clean ring is neither written nor read, and
+     * the output of its start-up phase is the copy of its noisy near end (echo_control_mobile.cc:285-291).  Every other session of
+     * the tick gets its near_clean row, as without the flag.  Outputs, codes, echo paths and the complete session state are bit for
+     * bit those of one reference instance per session, each called with or without the clean pointer as flagged.
+     * Accepted by TickFlags, TickFlagsHost and TickAsync, and by TickCalls* / TickPackets* with calls == 1, which are those ticks;
+     * it combines with every other flag, with per-session msInSndCardBuf and with sessions of the other rate.
+     *   - A session is of ONE kind for its life between two initialisations: "always" or "never".  (A reference instance whose clean
+     *     pointer comes and goes hands out stale contents of its clean frame buffer; that is not reproduced, and not attempted.)  The
+     *     object keeps per session what its Process calls carried so far -- WebRtcAecmSessions_GetSessionCleanMode -- reset by Init,
+     *     InitRates, InitSession, InitSessionRate and ImportSession*: an imported session starts at "no call yet", the caller
+     *     continues it as it was exported.
+     *   - A tick in which some calling session carries the flag is accepted only if every calling session either has made no Process
+     *     call since its last initialisation or gets what all its calls got.  Otherwise: AECM_BAD_PARAMETER_ERROR, nothing changed --
+     *     not the sessions, not the object's position.  The check follows the other argument checks, in their order.
+     *   - Once an object has accepted such a tick since its last Init, every later Tick* and WebRtcAecmSessions_Process* is checked
+     *     the same way (a tick without flags, or without the flag, gives every calling session the clean input it passes, or none):
+     *     an unflagged tick cannot silently hand a "never" session a clean input.  An object that never uses the flag is never
+     *     refused for this reason and behaves as it always has.
+     *   - Idle sessions: ignored in an idle session's byte like every other bit; an idle session is exempt from the check.
+     *   - near_clean == NULL: the flag is ignored, the tick is the tick without it.
+     *   - No calling session carries the flag: exactly the tick without it, the same launches, the same kernels.
+     *   - Every calling session carries it: the launches of the tick without a clean input; near_clean is not touched.
+     *   - Otherwise the tick always goes by the live lists (as with idle sessions): one planning launch that writes the list of the
+     *     sessions with a clean input and, from the next multiple of four entries on, the list of those without; then, up to four
+     *     times the sessions the device holds at once (28 672 on an MI355X), one tick launch whose first ceil(with / 4) workgroups
+     *     serve the first list and the others the second, and for larger ticks one tick launch per list
+     *     (WebRtcAecmSessions_SplitCleanTwoLaunches).
+     *   - TickFlagsHost stages the whole near_clean plane as always; the flagged sessions' rows are never read by a kernel.
+     *   - calls > 1 (TickCalls*, TickPackets*) with a calling session that carries the flag and near_clean != NULL:
+     *     AECM_UNSUPPORTED_FUNCTION_ERROR, nothing changed.  K-call ticks of mixed kinds are not supported yet.
+     *   - Snapshots: layout, version and the export code are unchanged.  The clean tail of a "never" session's snapshot is whatever
+     *     its never-read ring row holds; it influences nothing. */
+    AECM_SESSION_NO_CLEAN = 16
+};
 int32_t WebRtcAecmSessions_TickFlags(AecmSessions *s, const int16_t *far_dev, const int16_t *near_dev,
                                      const int16_t *near_clean_dev, int16_t *out_dev, int64_t stream_stride, size_t nrOfSamples,
                                      const int16_t *msInSndCardBuf_host, const uint8_t *flags_host, int32_t *codes_host);
@@ -372,6 +409,14 @@ int32_t WebRtcAecmSessions_SetKernelVariant(AecmSessions *s, int32_t variant);
 /* Diagnostics (tools/bench_sessions.py --occupancy): on != 0 sends every tick through the live list and the sparse tick kernel,
  * idle sessions or not, so that the cost of the indirection itself can be measured.  Results do not change. */
 int32_t WebRtcAecmSessions_ForceSparseTicks(AecmSessions *s, int32_t on);
+/* What the WebRtcAecm_Process calls of `session` carried since its last initialisation (AECM_SESSION_NO_CLEAN):
+ * *mode = 0 no Process call yet, 1 every one carried a clean input, 2 none did, 3 both (only in an object that never used the flag).
+ * Needs no device. */
+int32_t WebRtcAecmSessions_GetSessionCleanMode(AecmSessions *s, int32_t session, int32_t *mode);
+/* Diagnostics (tools/bench_split_clean.py): the tick launch of a tick with sessions of both kinds.  on < 0 (the default of a new
+ * object): one fused launch up to four times the sessions the device holds at once, one launch per list beyond; on == 0: always the
+ * fused launch; on > 0: always one launch per list.  Results do not change. */
+int32_t WebRtcAecmSessions_SplitCleanTwoLaunches(AecmSessions *s, int32_t on);
 
 /* Zero-copy host audio.  A caller-owned host buffer is pinned and mapped into the device's address space once
  * (hipHostRegister); *device_alias is then a device pointer that every *_dev argument of this header accepts

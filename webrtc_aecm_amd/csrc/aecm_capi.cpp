@@ -847,6 +847,17 @@ int32_t WebRtcAecmSessions_ForceSparseTicks(AecmSessions *s, int32_t on) {
     return 0;
 }
 
+static_assert(AECM_SESSION_NO_CLEAN == aecm::kFlowNoClean, "AECM_SESSION_NO_CLEAN");
+int32_t WebRtcAecmSessions_GetSessionCleanMode(AecmSessions *s, int32_t session, int32_t *mode) {
+    return s ? s->batch->GetSessionCleanMode(session, mode) : -1;
+}
+
+int32_t WebRtcAecmSessions_SplitCleanTwoLaunches(AecmSessions *s, int32_t on) {
+    if (!s) return -1;
+    s->batch->SplitCleanTwoLaunches(on);
+    return 0;
+}
+
 int32_t WebRtcAecmSessions_SetKernelVariant(AecmSessions *s, int32_t variant) {
     if (!s) return -1;
     if (variant != AECM_KERNEL_SAFE && variant != AECM_KERNEL_FAST) return AECM_BAD_PARAMETER_ERROR;

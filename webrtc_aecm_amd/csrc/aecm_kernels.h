@@ -207,6 +207,26 @@ hipError_t LaunchTickPackets(const StatePtrs &st, const TickIo &io, const TickFl
 // The planning launch alone (aecm_tick_packets_plan_kernels.hip; LaunchTickPackets calls it).
 hipError_t LaunchPlanPackets(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, int n_streams, int calls,
                              hipStream_t stream);
+// A split tick (aecm_tick_split_kernels.hip; AECM_SESSION_NO_CLEAN): the tick carries a clean plane (io.clean_in) and per-session flags,
+// clean_count > 0 of the calling sessions take their clean row, plain_count > 0 carry kFlowNoClean and take none.  Always by the live
+// lists: sp.live holds FlowSplitListEntries(n_streams) entries -- the ids of the first kind, ascending, at [0, clean_count), those of
+// the second at [plain_start, plain_start + plain_count), plain_start = FlowPlainListStart(clean_count) -- sp.block_base and
+// split.plain_base the sessions of either kind before each planning workgroup (aecm_flow_clean.h: FlowScanFlagsClean).
+//   aecm_flow_plan_split_kernel<mixed_plan>   what aecm_flow_plan_sparse_kernel / aecm_flow_plan_mixed_kernel do, filling both lists
+//   aecm_tick_split_kernel                    workgroups [0, plain_start / 4) run the tick body with a clean input on the first list,
+//                                             the others the body without on the second
+// two_launches: the tick launch as one launch per list instead, by the sparse tick kernel's text (the caller's choice by the size of
+// the tick: SessionBatch::SplitTickTwoLaunches).
+struct TickSplitIo {
+    const uint32_t *plain_base;        // [ceil(S / kFlowPlanBlock)]
+    int32_t clean_count, plain_count;
+    uint32_t plain_start;
+};
+hipError_t LaunchTickSplit(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,
+                           bool mixed_plan, bool two_launches, hipStream_t stream);
+// The planning launch alone (aecm_tick_split_plan_kernels.hip; LaunchTickSplit calls it).
+hipError_t LaunchPlanSplit(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,
+                           bool mixed_plan, hipStream_t stream);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront
@@ -238,6 +258,8 @@ hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset);
 hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_packets_kernels.hip, likewise.
 hipError_t ReadTickPacketsCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_tick_split_kernels.hip, likewise.
+hipError_t ReadTickSplitCheckCounters(uint64_t counters[2], bool reset);
 
 // Device self test of the wave primitives; counters[0..7] are failure counts (all must be 0):
 //  0 shfl_xor, 1 exchange, 2 reduce_max/min/add, 3 shift_up1, 4 bpermute/readlane/writelane, 5 ballot,

@@ -37,7 +37,7 @@ SessionBatch *SessionBatch::Create(int num_streams, int device_id) {
     for (int k = 0; k < kArgSlots && slots; ++k)
         slots = AECM_HIP_OK(hipHostMalloc((void **)&b->ms_host_[k], S * sizeof(int16_t), hipHostMallocMapped)) &&
                 AECM_HIP_OK(hipHostMalloc((void **)&b->flags_host_[k], S, hipHostMallocMapped)) &&
-                AECM_HIP_OK(hipHostMalloc((void **)&b->bases_host_[k], plan_blocks * sizeof(uint32_t), hipHostMallocMapped)) &&
+                AECM_HIP_OK(hipHostMalloc((void **)&b->bases_host_[k], 2 * plan_blocks * sizeof(uint32_t), hipHostMallocMapped)) &&
                 AECM_HIP_OK(hipHostGetDevicePointer((void **)&b->ms_dev_[k], b->ms_host_[k], 0)) &&
                 AECM_HIP_OK(hipHostGetDevicePointer((void **)&b->flags_dev_[k], b->flags_host_[k], 0)) &&
                 AECM_HIP_OK(hipHostGetDevicePointer((void **)&b->bases_dev_[k], b->bases_host_[k], 0)) &&
@@ -63,6 +63,7 @@ SessionBatch::~SessionBatch() {
     (void)hipFree(far_frames_);
     (void)hipFree(far_old_);
     (void)hipFree(live_dev_);
+    (void)hipFree(split_live_dev_);
     (void)hipFree(snap_list_);
     (void)hipFree(snap_stage_);
     (void)hipFree(snap_verdict_);
@@ -93,6 +94,7 @@ int32_t SessionBatch::Init(int32_t samp_freq) {
     lag_ = FlowObjectLag();
     fs_ = samp_freq;
     rates_.assign((size_t)S, samp_freq);
+    clean_history_.Reset((size_t)S);
     other_rates_ = 0;
     poisoned_ = false;
     return 0;
@@ -122,6 +124,27 @@ int32_t SessionBatch::GetSessionRate(int session, int32_t *samp_freq) const {
     return 0;
 }
 
+int32_t SessionBatch::GetSessionCleanMode(int session, int32_t *mode) const {
+    if (mode == nullptr) return AECM_NULL_POINTER_ERROR;
+    if (int32_t rc = CheckSession(session)) return rc;
+    *mode = clean_history_.Get(session);
+    return 0;
+}
+
+// One launch or two for a split tick of `calling` sessions (profiles/r24_split_clean_ticks.txt).  The fused kernel holds both tick
+// bodies in one function and comes out with several times the scalar spills of either body alone: per session it is the slower code
+// (about a tenth more kernel time), but it is ONE dispatch; the second of two dependent launches costs 6 .. 12 us of ramp-down and
+// ramp-up whatever the size.  Measured at half the sessions flagged, fused against two launches, ms per tick: 4 096 sessions 0.0354 /
+// 0.0417, 8 192: 0.0538 / 0.0558, 16 384: 0.0832 / 0.0897, 32 768: 0.1442 / 0.1379, 65 536: 0.2653 / 0.2425.  The two lines cross
+// between 16 384 and 32 768 sessions, interpolated linearly at about 25 000 = 3.5 times what the device holds at once (7 168 on 256
+// CUs): the fused launch up to four residency rounds -- at that threshold the two forms differ by less than 2 us --, two beyond.
+constexpr int kSplitFusedRounds = 4;
+bool SessionBatch::SplitTickTwoLaunches(int calling) const {
+    if (split_two_launches_ >= 0) return split_two_launches_ > 0;
+    const int64_t resident = (int64_t)TickWorkgroupsPerCu() * TickWorkgroupWaves() * engine_->launch_policy().compute_units;
+    return calling > kSplitFusedRounds * resident;
+}
+
 int32_t SessionBatch::CheckSession(int session) const {
     if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
@@ -142,6 +165,7 @@ int32_t SessionBatch::InitSessionRate(int session, int32_t samp_freq) {
     const bool ok = AECM_HIP_OK(hipSetDevice(device_)) && engine_->InitStreamsAtRate(session, 1, samp_freq) && ResetFlowRows(session, 1);
     if (!ok) { poisoned_ = true; return AECM_UNSPECIFIED_ERROR; }
     SetRate(session, samp_freq);
+    clean_history_.ResetSession(session);
     return 0;
 }
 
@@ -308,6 +332,19 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     // a K-call tick's calls are whole calls of n samples; a packet tick's are whole calls of the session's own size (80 with kHalfCall)
     if (k_calls && (any & (packets ? kSplitCalls : kSplitCalls | kHalfCall)) != 0) return AECM_BAD_PARAMETER_ERROR;
     const bool half_calls = flags_per_session && (any & kHalfCall) != 0;                  // some session that calls makes a half call
+    // kNoClean (aecm_flow_clean.h): a tick that gives a calling session another kind of Process call than it has had is refused; the
+    // two lists of a tick that has callers of both kinds.  All callers flagged: the tick without a clean input, by its launches.
+    FlowCleanTick clean_tick;
+    if (const FlowCleanVerdict v = clean_history_.Check(flags_per_session, any, clean != nullptr, calls, &clean_tick))
+        return v == kCleanUnsupported ? AECM_UNSUPPORTED_FUNCTION_ERROR : AECM_BAD_PARAMETER_ERROR;
+    const bool had_clean = clean != nullptr;
+    int32_t clean_count = 0, plain_count = 0;
+    if (clean_tick.split) {
+        split_bases_.resize(2 * live_bases_.size());
+        FlowScanFlagsClean(flags_per_session, S, split_bases_.data(), split_bases_.data() + live_bases_.size(), &clean_count, &plain_count);
+        if (clean_count == 0) clean = nullptr;
+    }
+    const bool split_tick = clean_tick.split && clean_count > 0;
     const auto idle = [&](int s) { return flags_per_session && (flags_per_session[s] & kIdle) != 0; };
     if (live == 0) {
         // Nobody calls: nothing is launched.  The object's position moves on all the same; the sessions learn of it with the
@@ -325,7 +362,11 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         return 0;
     }
     // (as FlowRouteTick will say below, once the tick is certain to be enqueued; a K-call tick always goes by the live list)
-    const bool sparse_tick = live < S || force_sparse_ || k_calls;
+    const bool sparse_tick = live < S || force_sparse_ || k_calls || split_tick;
+    if (split_tick && !split_live_dev_ && !AECM_HIP_OK(hipMalloc((void **)&split_live_dev_, FlowSplitListEntries((uint32_t)S) * sizeof(uint32_t)))) {
+        split_live_dev_ = nullptr;
+        return AECM_UNSPECIFIED_ERROR;
+    }
     if (k_calls && !calls_plans_ &&
         !AECM_HIP_OK(hipMalloc((void **)&calls_plans_, (size_t)S * kFlowMaxTickCalls * kFlowPlanWords * sizeof(int32_t)))) {
         calls_plans_ = nullptr;
@@ -383,7 +424,8 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     if (sparse_tick) {
         if (!flags_per_session)
             for (size_t b = 0; b < live_bases_.size(); ++b) live_bases_[b] = (uint32_t)(b * kFlowPlanBlock);
-        memcpy(bases_host_[slot], live_bases_.data(), live_bases_.size() * sizeof(uint32_t));
+        if (split_tick) memcpy(bases_host_[slot], split_bases_.data(), split_bases_.size() * sizeof(uint32_t));      // both lists' bases, one behind the other
+        else memcpy(bases_host_[slot], live_bases_.data(), live_bases_.size() * sizeof(uint32_t));
     }
     // without far rows (nobody buffers a far frame in this tick) the kernel's far row pointer is never used for a sample that
     // counts; it still has to be an address: the near rows
@@ -424,8 +466,13 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     bool mixed_plan;
     // (a K-call tick: no half calls, no other rates -- FlowRouteTick itself, told the whole tick's samples and that the tick goes by the
     // live list; a packet tick: half calls leave their sessions calls * 80 behind, the object out of step)
-    const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, span, force_sparse_ || k_calls, half_calls, other_rates_ > 0, &mixed_plan);
-    if (k_calls) {
+    const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, span, force_sparse_ || k_calls || split_tick, half_calls, other_rates_ > 0, &mixed_plan);
+    clean_history_.Commit(flags_per_session, had_clean, clean_tick);
+    if (split_tick) {
+        const TickSparseIo sp{near_ring_, clean_ring_, kRing, split_live_dev_, bases_dev_[slot], route.deferred_lag};
+        const TickSplitIo split{bases_dev_[slot] + live_bases_.size(), clean_count, plain_count, FlowPlainListStart((uint32_t)clean_count)};
+        ok = AECM_HIP_OK(LaunchTickSplit(engine_->state_ptrs(), tio, fio, sp, split, S, mixed_plan, SplitTickTwoLaunches(live), st));
+    } else if (k_calls) {
         fio.plans = calls_plans_;
         const TickSparseIo sp{near_ring_, clean_ring_, kRing, live_dev_, bases_dev_[slot], route.deferred_lag};
         // (mixed_plan with K calls: a packet tick in which somebody makes half calls or runs at another rate -- the packed layout and
@@ -551,6 +598,7 @@ int32_t SessionBatch::ImportSession(int session, const void *buf, bool any_rate)
     // (ImportState validates the blob once more and is the first thing that writes)
     if (const int32_t rc = engine_->ImportState(session, p + at.state)) return rc;
     SetRate(session, (int32_t)h.fs);
+    clean_history_.ResetSession(session);      // the caller continues the session as it was exported
     // The session arrives in step with this object: its tail goes behind the object's near position, its lag is 0 -- behind
     // the position the device takes for the object's while all-idle ticks are still to be added to the lags, that is.
     flow[F_NEAR_LAG] = 0;
@@ -699,7 +747,10 @@ int32_t SessionBatch::ImportSessions(const int32_t *sessions, int count, const v
         }
     }
     if (!ok || !AECM_HIP_OK(hipStreamSynchronize(st))) return Fail();      // sessions half written are no sessions: the object is poisoned
-    for (int i = 0; i < count; ++i) SetRate(sessions ? sessions[i] : i, (int32_t)(info[(size_t)i + 1] & 0x7fffffffu));
+    for (int i = 0; i < count; ++i) {
+        SetRate(sessions ? sessions[i] : i, (int32_t)(info[(size_t)i + 1] & 0x7fffffffu));
+        clean_history_.ResetSession(sessions ? sessions[i] : i);
+    }
     if (other_rate) engine_->NoteStreamOfOtherRate();
     return 0;
 }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "aecm_engine.h"
+#include "aecm_flow_clean.h"
 #include "aecm_kernels.h"
 
 namespace aecm {
@@ -98,7 +99,19 @@ public:
     //     bit 3 (kHalfCall, 160-sample ticks only, not with kSplitCalls) = this session makes ONE call pair of 80 samples, on the
     //     first half of its rows; out[s][80..160) is not written (host pointers: zeros).  Its near-end position then lies 80
     //     samples behind the object's: F_NEAR_LAG, as after half an idle tick (aecm_flow_plan.h: FlowTickMixed).
-    static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle, kHalfCall = kFlowHalfCall;
+    //     bit 4 (kNoClean; a tick that passes `clean`, calls == 1) = this session's WebRtcAecm_Process gets nearendClean = NULL: its clean
+    //     row is not read, its clean ring row neither written nor read, its start-up output is the copy of its noisy near end.  A
+    //     session is of one kind between two initialisations (aecm_flow_clean.h: FlowCleanHistory); a tick that would change a calling
+    //     session's kind is refused (bad parameter) and changes nothing, and so is every later tick or Process of an object that has
+    //     accepted a tick with the bit, an object that never uses it is never refused for it.  Nobody flagged among the callers: the
+    //     tick without the bit, by its launches; everybody: the launches of the tick without `clean`; else aecm_tick_split_kernels.hip,
+    //     always by the live lists.  Ignored without `clean` and in an idle session's byte; with calls > 1: unsupported function.
+    static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle, kHalfCall = kFlowHalfCall, kNoClean = kFlowNoClean;
+    // 0 no Process call since the session's last initialisation, 1 every one carried a clean input, 2 none did, 3 both
+    int32_t GetSessionCleanMode(int session, int32_t *mode) const;
+    // The tick launch of a split tick: the fused kernel, or one launch per list -- by the size of the tick (SplitTickTwoLaunches below;
+    // mode < 0, the default), or as the caller says (diagnostics, tools/bench_split_clean.py: 0 fused, > 0 two).  Results do not change.
+    void SplitCleanTwoLaunches(int mode) { split_two_launches_ = mode < 0 ? -1 : mode > 0 ? 1 : 0; }
     // Diagnostics (tools/bench_sessions.py): every tick through the live list and the sparse tick kernel, idle sessions or
     // not -- what the indirection itself costs.
     void ForceSparseTicks(bool on) { force_sparse_ = on; }
@@ -147,6 +160,10 @@ private:
     std::vector<int32_t> rates_;               // [S] every session's own rate (mirror of the core states' S_MULT)
     int other_rates_ = 0;                      // sessions whose rate is not fs_
     void SetRate(int session, int32_t fs);
+    FlowCleanHistory clean_history_;           // [S] next to rates_: what every session's Process calls carried (kNoClean)
+    int split_two_launches_ = -1;
+    bool SplitTickTwoLaunches(int calling) const;
+    uint32_t *split_live_dev_ = nullptr;       // [FlowSplitListEntries(S)] the two lists of a split tick; allocated by the first one
     // A tick that failed on the device leaves the rings and the wrapper state out of step: every later call is refused
     // (AECM_UNSPECIFIED_ERROR) until Init.
     bool poisoned_ = false;
@@ -157,6 +174,7 @@ private:
     bool force_sparse_ = false;
     uint32_t *live_dev_ = nullptr;             // [S] the tick's live sessions, ascending (written by the planning launch)
     std::vector<uint32_t> live_bases_;         // [ceil(S / kFlowPlanBlock)] FlowLiveBlockBases of the tick's flags
+    std::vector<uint32_t> split_bases_;        // [2][ceil(S / kFlowPlanBlock)] FlowScanFlagsClean of a split tick's flags
     int16_t *far_ring_ = nullptr, *near_ring_ = nullptr, *out_ring_ = nullptr;   // [S][kRing]
     int16_t *clean_ring_ = nullptr;            // [S][kRing], allocated by the first tick that carries a clean near-end
     int16_t *io_dev_ = nullptr;                // [4][S][io_row_] staging when the caller passes host pointers

@@ -68,11 +68,13 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_ImportSessionsDevice",
     "WebRtcAecmSessions_TickCalls", "WebRtcAecmSessions_TickCallsHost", "WebRtcAecmSessions_TickCallsAsync",
     "WebRtcAecmSessions_TickPackets", "WebRtcAecmSessions_TickPacketsHost", "WebRtcAecmSessions_TickPacketsAsync",
+    "WebRtcAecmSessions_GetSessionCleanMode", "WebRtcAecmSessions_SplitCleanTwoLaunches",
 ]
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
 SESSION_IDLE = 4
 SESSION_HALF_CALL = 8
+SESSION_NO_CLEAN = 16
 SESSION_MAX_TICK_CALLS = 6
 
 
@@ -200,6 +202,8 @@ def load():
     lib.WebRtcAecmSessions_DescribeTick.argtypes = [C.c_int32, C.c_int32, C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmSessions_DescribeTickLive.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmSessions_ForceSparseTicks.argtypes = [vp, C.c_int32]
+    lib.WebRtcAecmSessions_GetSessionCleanMode.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.WebRtcAecmSessions_SplitCleanTwoLaunches.argtypes = [vp, C.c_int32]
     lib.WebRtcAecmSessions_InitRates.argtypes = [vp, C.c_int32, vp]
     lib.WebRtcAecmSessions_InitSessionRate.argtypes = [vp, C.c_int32, C.c_int32]
     lib.WebRtcAecmSessions_GetSessionRate.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
@@ -627,7 +631,7 @@ class AecmSessions:
 
     def tick_host_per_session(self, far, near, ms_per_session, clean=None, flags=None):
         """far/near(/clean): [S, n] int16; ms_per_session: S msInSndCardBuf values; flags: S uint8 (SESSION_NO_FAREND,
-        SESSION_SPLIT_CALLS, SESSION_IDLE, SESSION_HALF_CALL) or None.  Returns (code, out, codes[S]); the out row of a session
+        SESSION_SPLIT_CALLS, SESSION_IDLE, SESSION_HALF_CALL, SESSION_NO_CLEAN) or None.  Returns (code, out, codes[S]); the out row of a session
         that carries SESSION_IDLE is zeros, its code 0; so is the second half of the row of one that carries SESSION_HALF_CALL."""
         far, near, clean, cptr = self._rows(far, near, clean)
         ms = np.ascontiguousarray(ms_per_session, dtype=np.int16)
@@ -889,6 +893,17 @@ class AecmSessions:
             rc = self.lib.WebRtcAecmSessions_TickPackets(self.h, far_ptr, near_ptr, clean_ptr, out_ptr, stream_stride, n, calls, ms, msp, flp,
                                                          codes.ctypes.data)
         return rc, codes
+
+    def get_session_clean_mode(self, session: int):
+        """(code, 0 no Process call since the session's last initialisation / 1 all with a clean input / 2 none / 3 both)."""
+        mode = C.c_int32(-1)
+        rc = self.lib.WebRtcAecmSessions_GetSessionCleanMode(self.h, session, C.byref(mode))
+        return rc, mode.value
+
+    def split_clean_two_launches(self, on=True) -> int:
+        """Diagnostics: the tick launch of a tick with SESSION_NO_CLEAN sessions and others -- True: always one launch per list,
+        False: always the fused launch, None: by the size of the tick (the default of a new object)."""
+        return self.lib.WebRtcAecmSessions_SplitCleanTwoLaunches(self.h, -1 if on is None else 1 if on else 0)
 
     def force_sparse_ticks(self, on: bool = True) -> int:
         """Diagnostics: every tick through the live list and the sparse tick kernel (WebRtcAecmSessions_ForceSparseTicks)."""
