@@ -15,7 +15,7 @@ import simlib
 
 SRC = simlib.ROOT / "tests" / "sim" / "sim_mixed.cpp"
 SO = simlib.SIM_SO.parent / "libaecm_sim_mixed.so"
-DEPS = [SRC, simlib.CSRC / "aecm_flow_plan.h", simlib.CSRC / "aecm_session_flow.h", simlib.CSRC / "aecm_ops.h"]
+DEPS = [SRC, simlib.CSRC / "aecm_flow_plan.h", simlib.CSRC / "aecm_flow_clean.h", simlib.CSRC / "aecm_tick_plan.h", simlib.CSRC / "aecm_session_flow.h", simlib.CSRC / "aecm_ops.h"]
 _lib = None
 
 

@@ -15,7 +15,7 @@ import simlib
 
 SRC = simlib.ROOT / "tests" / "sim" / "sim_packets.cpp"
 SO = simlib.SIM_SO.parent / "libaecm_sim_packets.so"
-DEPS = [SRC, SRC.parent / "sim_mixed.cpp", simlib.CSRC / "aecm_flow_plan.h", simlib.CSRC / "aecm_session_flow.h", simlib.CSRC / "aecm_ops.h"]
+DEPS = [SRC, SRC.parent / "sim_mixed.cpp", simlib.CSRC / "aecm_flow_plan.h", simlib.CSRC / "aecm_flow_clean.h", simlib.CSRC / "aecm_tick_plan.h", simlib.CSRC / "aecm_session_flow.h", simlib.CSRC / "aecm_ops.h"]
 _lib = None
 
 

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: ticks of K call pairs (WebRtcAecmSessions_TickCalls) on sample TAGS -- the method of sim_flow.cpp and
-// sim_sparse.cpp.  The device side is what SessionBatch::Enqueue (calls > 1), aecm_flow_plan_calls_kernel and
+// sim_sparse.cpp.  The device side is what the host's tick planner (calls > 1), aecm_flow_plan_calls_kernel and
 // aecm_tick_calls_kernel (webrtc_aecm_amd/csrc/aecm_tick_calls_kernels.hip) do for ONE session of an object, in the kernel's own
 // order per call -- spill, far framing (fresh samples from call c's piece of the input row, everything older from the ring),
 // append, blocks, output frames -- on the rows of sim_sparse.cpp's device model, so that K-call ticks, ordinary ticks, bursts
@@ -26,16 +26,15 @@ struct CallsSide : DeviceSide {
                    const int64_t *near_in, int64_t *out, std::vector<int64_t> *blk_far, std::vector<int64_t> *blk_near, CallsCounters &cnt) {
         const int64_t mask = kRingLen - 1;
         const int span = calls * n;
-        const int n_sessions = 1 + (others_live ? 1 : 0) + (others_idle ? 1 : 0), live = (idle ? 0 : 1) + (others_live ? 1 : 0);
-        // SessionBatch::Enqueue: told the whole tick's samples, always by the live list
-        const FlowTickRoute route = FlowRouteTick(lag, live, n_sessions, span, true);
+        uint32_t tick_pos;
+        const TickPlan plan = HostTick(n, calls, flags, idle, others_live, others_idle, &tick_pos);
+        const FlowTickRoute &route = plan.route;
         if (!route.launch) {
-            near_pos += (uint32_t)span;
             ++deferred_ticks;
             return false;
         }
-        const uint32_t tick_pos = near_pos;
-        near_pos += (uint32_t)span;
+        // the host is told the whole tick's samples, and a K-call tick always goes by the live list
+        if (plan.span != span || plan.family != kTickFamily_calls || !route.sparse_plan || !route.sparse_tick) fault = 2;
         // aecm_flow_plan_calls_kernel
         if (idle) {
             regs.v[F_NEAR_LAG] = FlowIdleTick(FlowIdleTick(regs.v[F_NEAR_LAG], route.deferred_lag), span);
@@ -128,7 +127,7 @@ template <class D>
 void StartAt(D &dev, uint32_t start_pos) {
     dev.regs.v[F_FAR_RP] = dev.regs.v[F_FAR_WP] = (int32_t)start_pos;
     dev.regs.v[F_FRM_POS] = dev.regs.v[F_BLK_POS] = dev.regs.v[F_OUT_RP] = (int32_t)(start_pos * 3u);
-    dev.near_pos = start_pos * 80u;
+    dev.obj.near_pos = start_pos * 80u;
 }
 
 }  // namespace
@@ -233,10 +232,10 @@ int64_t sim_calls_fuzz(uint64_t seed, int fs, int n_ticks, uint32_t start_pos, i
         else if (called != !idle) what = 7;
         if (!what) {
             // the lag words: the twin's object defers what nobody ticked tick by tick, this one once -- the same sum
-            const int32_t own = FlowIdleTick(dev.regs.v[F_NEAR_LAG], dev.lag.deferred_lag), other = FlowIdleTick(twin.regs.v[F_NEAR_LAG], twin.lag.deferred_lag);
+            const int32_t own = FlowIdleTick(dev.regs.v[F_NEAR_LAG], dev.obj.lag.deferred_lag), other = FlowIdleTick(twin.regs.v[F_NEAR_LAG], twin.obj.lag.deferred_lag);
             for (int k = 0; k < kFlowTickFields && !what; ++k)
                 if (dev.regs.v[k] != twin.regs.v[k]) { what = 5; detail[12] = k + 1; }
-            if (!what && (own != other || dev.near_pos != twin.near_pos)) { what = 5; detail[12] = F_NEAR_LAG + 1; }
+            if (!what && (own != other || dev.obj.near_pos != twin.obj.near_pos)) { what = 5; detail[12] = F_NEAR_LAG + 1; }
         }
         if (what) { detail[0] = what; return tick; }
         if (!idle) {

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: the session wrapper's decision path (webrtc_aecm_amd/csrc/aecm_flow_plan.h: the Flow* functions) driven
-// as the planning kernels drive it -- N sessions, one lane each, tick by tick, through the routing of SessionBatch::Enqueue:
+// as the planning kernels drive it -- N sessions, one lane each, tick by tick, planned by the host's own planner (aecm_tick_plan.h):
 // the dense, the sparse and the mixed planning kernel, the K-call and the packets planner, and far-end bursts -- with the
 // header's decision markers switched on.  tools/flow_coverage.py builds this file with -O0 --coverage (branch counters) and reads
 // the record of (decision, outcome) per tick and session the markers leave: from it, whether two sessions of one wavefront
@@ -28,6 +28,7 @@ inline void flowcov_mark(int id, bool outcome) {
 
 #include "aecm_flow_plan.h"
 #include "aecm_session_flow.h"
+#include "aecm_tick_plan.h"
 
 namespace {
 
@@ -144,7 +145,7 @@ const char *flowcov_decision_name(int id) {
 }
 
 // A run of S sessions through T ticks of one object (rate object_fs; rates[S]: the sessions' own).
-//   kind[T]       0 an ordinary tick of n_t samples (routed as SessionBatch::Enqueue routes it: dense, sparse or mixed planning kernel),
+//   kind[T]       0 an ordinary tick of n_t samples (planned as SessionBatch::Enqueue plans it: dense, sparse or mixed planning kernel),
 //                 1 a K-call tick (TickCalls), 2 a packet tick (TickPackets); calls_t[T] = K
 //   flags[T * S], ms[T * S]      the tick's per-session arguments
 //   burst[T * S], burst_len[T]   WebRtcAecm_BufferFarend calls of burst_len samples the session makes before the tick (a launch of
@@ -153,10 +154,10 @@ const char *flowcov_decision_name(int id) {
 //                                start-up counters run on and wrap); far_off[S], frm_off[S]: where its position counters stand
 //   start_out[S * kFlowWords]    the wrapper words of that imported state (what the test patches into a snapshot)
 //   regs_out[T * S * kFlowFieldsUsed]   the wrapper words after every tick
-//   marks[T * 2 * S * kFlowDecisions]   the outcome record: [t][0] the tick's planning launch, [t][1] the burst launch before it;  kernel_out[T]: 0 nothing launched, 1 dense, 2 sparse, 3 mixed, 4 calls, 5 packets
+//   marks[T * 2 * S * kFlowDecisions]   the outcome record: [t][0] the tick's planning launch, [t][1] the burst launch before it;  kernel_out[T]: the tick's TickFamily (aecm_tick_plan.h)
 //   continues[T * S]             calls of the tick the session's call loop left with `continue` (the start-up phase)
 // Returns -1, or the first tick at which the two sides differed; detail[0] = what (1 block count, 2 far tags, 3 near tags, 4 output,
-// 5 return code, 6 live list, 100 + field: FlowStateDefect refused the state), detail[1] = the session.
+// 5 return code, 6 live list, 8 the host refuses the tick, 100 + field: FlowStateDefect refused the state), detail[1] = the session.
 int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t *rates, const int32_t *kind, const int32_t *n_t, const int32_t *calls_t,
                     const uint8_t *flags, const int16_t *ms, const uint8_t *burst, const int32_t *burst_len, const int32_t *preroll,
                     const int16_t *preroll_ms, const uint32_t *far_off, const uint32_t *frm_off, int32_t *start_out, int32_t *regs_out, uint8_t *marks,
@@ -165,11 +166,13 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
     std::vector<int32_t> far_in, near_in, out_dev, out_ref, dfar, dnear, rfar, rnear;
     detail[0] = detail[1] = 0;
     g_marks = nullptr;
-    int other_rates = 0;
+    TickObject obj;
+    obj.Init(S, object_fs);
+    obj.force_sparse = force_sparse != 0;
     for (int s = 0; s < S; ++s) {
         Session &x = sess[(size_t)s];
         x.fs = rates[s];
-        other_rates += rates[s] != object_fs;
+        obj.SetRate(s, rates[s]);
         x.ref.Init(x.fs);
         int32_t zeros[kFlowFrame], o[kFlowFrame];
         for (int c = 0; c < preroll[s]; ++c) {
@@ -192,10 +195,9 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
             return 0;
         }
     }
-    FlowObjectLag lag;
-    uint32_t near_pos = 0;
     const int n_groups = (S + kFlowPlanBlock - 1) / kFlowPlanBlock;
-    std::vector<uint32_t> bases((size_t)n_groups), live_list((size_t)S);
+    std::vector<uint32_t> live_list((size_t)S);
+    std::vector<int32_t> codes((size_t)S);
     for (int t = 0; t < T; ++t) {
         const int n = n_t[t], K = kind[t] == 0 ? 1 : calls_t[t], span = n * K;
         const uint8_t *fl = flags + (size_t)t * S;
@@ -207,18 +209,27 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
                 sess[(size_t)s].Burst(burst_len[t], burst[(size_t)t * S + s]);
                 g_marks = nullptr;
             }
-        uint8_t any;
-        bool half_and_split, mixed_plan = false;
-        const int32_t live = FlowScanFlags(fl, S, bases.data(), &any, &half_and_split);
-        const bool half_calls = (any & kFlowHalfCall) != 0, k_calls = K > 1;
-        if (live == 0) {
-            (void)FlowRouteTick(lag, 0, S, span, force_sparse != 0);
-            kernel_out[t] = 0;
-        } else {
-            const FlowTickRoute route = FlowRouteTickMixed(lag, live, S, span, force_sparse != 0 || k_calls, half_calls, other_rates > 0, &mixed_plan);
-            const int kernel = k_calls ? (mixed_plan ? 5 : 4) : !route.sparse_plan ? 1 : mixed_plan ? 3 : 2;
-            kernel_out[t] = kernel;
-            const bool live_list_wanted = k_calls || (kernel != 1 && route.sparse_tick);
+        // the host: check, plan, commit
+        TickArgs args;
+        args.flags_per_session = fl;
+        args.n = n;
+        args.calls = K;
+        args.packets = kind[t] == 2;
+        uint32_t near_pos;
+        const TickPlan plan = obj.Tick(args, &near_pos);
+        if (plan.code) {
+            detail[0] = 8;
+            detail[1] = plan.code;
+            return t;
+        }
+        (void)TickCodes(ms + (size_t)t * S, 0, fl, S, codes.data());
+        const TickFamily kernel = plan.family;
+        kernel_out[t] = kernel;
+        if (kernel != kTickFamily_nothing) {
+            const FlowTickRoute &route = plan.route;
+            const bool k_calls = plan.k_calls;
+            const std::vector<uint32_t> &bases = obj.Bases(plan);
+            const bool live_list_wanted = k_calls || (kernel != kTickFamily_dense && route.sparse_tick);
             if (live_list_wanted) {
                 // the device half of the live list: ballots per wavefront, counts per workgroup, FlowLiveSlot per lane
                 std::fill(live_list.begin(), live_list.end(), 0xffffffffu);
@@ -253,7 +264,7 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
                 Session &x = sess[(size_t)s];
                 g_marks = mrow + (size_t)s * kFlowDecisions;
                 const int f = fl[s], m = ms[(size_t)t * S + s];
-                if (kernel != 1) {
+                if (kernel != kTickFamily_dense) {
                     const bool is_live = (f & kFlowIdle) == 0;
                     AECM_FLOW_MARK(FD_K_LIVE, is_live);
                     if (!is_live) {
@@ -270,8 +281,8 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
                     }
                 }
                 // the session's own samples of the tick: K calls of n_s samples at the start of its rows, junk behind them
-                const int session_fs = kernel == 1 || kernel == 2 || kernel == 4 ? object_fs : x.fs;
-                const bool half = (f & kFlowHalfCall) != 0 && n == 2 * kFlowFrame && (kernel == 3 || kernel == 5);
+                const int session_fs = kernel == kTickFamily_dense || kernel == kTickFamily_sparse || kernel == kTickFamily_calls ? object_fs : x.fs;
+                const bool half = (f & kFlowHalfCall) != 0 && n == 2 * kFlowFrame && (kernel == kTickFamily_mixed || kernel == kTickFamily_packets);
                 const int n_s = half ? kFlowFrame : n, own = K * n_s;
                 far_in.assign((size_t)span, kJunk);
                 near_in.assign((size_t)span, kJunk);
@@ -291,13 +302,13 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
                     n_cont += p.n_calls == 2 ? !p.frame[0].active + !p.frame[1].active : !p.frame[0].active;
                     x.Execute(p, far_in.data() + c * n_s, near_in.data() + c * n_s, out_dev.data() + c * n_s, &dfar, &dnear);
                 };
-                if (kernel == 4) {
+                if (kernel == kTickFamily_calls) {
                     FlowTickCalls(x.regs, session_fs, n, K, m, f, near_pos, sink);
-                } else if (kernel == 5) {
+                } else if (kernel == kTickFamily_packets) {
                     FlowTickPackets(x.regs, session_fs, n, K, m, f, near_pos, sink);
                 } else {
                     FlowPlan p;
-                    if (kernel == 3) FlowTickMixed(x.regs, session_fs, n, m, f, near_pos, p);
+                    if (kernel == kTickFamily_mixed) FlowTickMixed(x.regs, session_fs, n, m, f, near_pos, p);
                     else FlowTick(x.regs, session_fs, n, m, f, near_pos, p);
                     sink(0, p);
                 }
@@ -307,7 +318,7 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
                 const bool split = (f & kFlowSplitCalls) != 0 && n_s == 2 * kFlowFrame && K == 1;
                 const int ref_calls = split ? 2 : K, ref_len = split ? kFlowFrame : n_s;
                 const int32_t rc_ref = x.RefCalls(ref_calls, ref_len, farend, m, far_in.data(), near_in.data(), out_ref.data(), &rfar, &rnear);
-                const int32_t rc_dev = (m < 0 || m > 500) ? kWarnBadParameter : 0;
+                const int32_t rc_dev = codes[(size_t)s];
                 int what = 0;
                 int32_t words[kFlowWords] = {0};
                 for (int k = 0; k < kFlowFieldsUsed; ++k) words[k] = x.regs.v[k];
@@ -324,7 +335,6 @@ int64_t flowcov_run(int S, int T, int object_fs, int force_sparse, const int32_t
                 }
             }
         }
-        near_pos += (uint32_t)span;
         for (int s = 0; s < S; ++s)
             for (int k = 0; k < kFlowFieldsUsed; ++k) regs_out[((size_t)t * S + s) * kFlowFieldsUsed + k] = sess[(size_t)s].regs.v[k];
     }

@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE: an OBJECT of sessions of both sampling rates and both call sizes (WebRtcAecmSessions_InitRates,
 // AECM_SESSION_HALF_CALL) on sample TAGS -- the method of sim_sparse.cpp, with the whole object instead of one session of it.
-// The device side is what SessionBatch::Enqueue (FlowScanFlags, FlowTickFlagsValid, FlowRouteTickMixed), the three planning
+// The device side is what the host's tick planner (aecm_tick_plan.h: check, plan, commit), the three planning
 // kernels (aecm_flow_plan_kernel, aecm_flow_plan_sparse_kernel, aecm_flow_plan_mixed_kernel: FlowResync, FlowMoveNear, FlowTick,
 // FlowTickMixed), the tick kernels' body (it appends ALL of a tick's near-end samples at the object's position, a half call's
 // unconsumed second half included) and aecm_buffer_farend_kernel do; the reference side is one SessionFlow<T> per session
@@ -16,6 +16,7 @@
 #include "aecm_flow_plan.h"
 #include "aecm_ops.h"
 #include "aecm_session_flow.h"
+#include "aecm_tick_plan.h"
 
 namespace {
 
@@ -147,20 +148,22 @@ int64_t sim_mixed_fuzz(uint64_t seed, int n_sessions, int n_ticks, int rates_mod
     const int obj_fs = (seed & 1) ? 16000 : 8000;
     const bool has_clean = (seed & 2) != 0;
     std::vector<std::unique_ptr<Session>> ss;
-    int other_rates = 0;
+    TickObject obj;                                                             // what the host keeps for the object
+    obj.Init(n_sessions, obj_fs);
     for (int s = 0; s < n_sessions; ++s) {
         const int fs = rates_mode == 0 ? (rng.chance(50) ? 16000 : 8000) : obj_fs;
-        other_rates += fs != obj_fs;
+        obj.SetRate(s, fs);
         ss.emplace_back(new Session(fs));
         const uint32_t p0 = rng.chance(50) ? 0u : rng.next() * 7u;                 // positions that wrap
         ss[s]->regs.v[F_FAR_RP] = ss[s]->regs.v[F_FAR_WP] = (int32_t)p0;
         ss[s]->regs.v[F_FRM_POS] = ss[s]->regs.v[F_BLK_POS] = ss[s]->regs.v[F_OUT_RP] = (int32_t)(p0 * 3u);
     }
-    uint32_t near_pos = start_pos;
-    FlowObjectLag lag;
+    obj.near_pos = start_pos;
     std::vector<uint8_t> flags((size_t)n_sessions), calls((size_t)n_sessions);
     std::vector<int> ms((size_t)n_sessions);
-    std::vector<uint32_t> bases((size_t)(n_sessions + kFlowPlanBlock - 1) / kFlowPlanBlock), bases_ref(bases.size());
+    std::vector<uint32_t> bases_ref(obj.live_bases.size());
+    std::vector<int16_t> ms16((size_t)n_sessions);
+    std::vector<int32_t> codes((size_t)n_sessions);
     const auto fail = [&](int what, int s) { detail[D_WHAT] = what; detail[D_SESSION] = s; };
     for (int64_t tick = 0; tick < n_ticks; ++tick) {
         const int n = rng.chance(85) ? 160 : 80;
@@ -195,19 +198,21 @@ int64_t sim_mixed_fuzz(uint64_t seed, int n_sessions, int n_ticks, int rates_mod
             ms[s] = rng.range(0, 300);
             if (rng.chance(4)) ms[s] = rng.chance(50) ? -300 : 700;
         }
-        // ---- the host (SessionBatch::Enqueue)
-        uint8_t any = 0;
-        bool both = false;
-        const int32_t live = FlowScanFlags(flags.data(), n_sessions, bases.data(), &any, &both);
-        if (live != FlowLiveBlockBases(flags.data(), n_sessions, bases_ref.data()) || bases != bases_ref || !FlowTickFlagsValid(n, any, both)) {
+        // ---- the host (aecm_tick_plan.h): check, plan, commit
+        TickArgs args;
+        args.flags_per_session = flags.data();
+        args.n = n;
+        args.has_clean = has_clean;
+        uint32_t tick_pos;
+        const TickPlan plan = obj.Tick(args, &tick_pos);
+        if (plan.code || plan.live != FlowLiveBlockBases(flags.data(), n_sessions, bases_ref.data()) || obj.live_bases != bases_ref) {
             fail(11, -1);
             return tick;
         }
-        const bool half_calls = (any & kFlowHalfCall) != 0;
-        bool mixed_plan = false;
-        const FlowTickRoute route = FlowRouteTickMixed(lag, live, n_sessions, n, false, half_calls, other_rates > 0, &mixed_plan);
-        const uint32_t tick_pos = near_pos;
-        near_pos += (uint32_t)n;
+        const bool mixed_plan = plan.mixed_plan;
+        const FlowTickRoute route = plan.route;
+        for (int s = 0; s < n_sessions; ++s) ms16[(size_t)s] = (int16_t)ms[s];
+        (void)TickCodes(ms16.data(), 0, flags.data(), n_sessions, codes.data());
         if (!route.launch) {
             detail[D_NOBODY_TICKS]++;
             continue;
@@ -263,7 +268,7 @@ int64_t sim_mixed_fuzz(uint64_t seed, int n_sessions, int n_ticks, int rates_mod
             q.near_offered += n_eff;
             std::vector<int64_t> dfar, dnear, dclean, rfar, rnear, rclean;
             q.TickBody(planned, has_clean, n, tick_pos, far_in, near_in, clean_in, out_dev, &dfar, &dnear, &dclean);
-            const int32_t dev_code = (ms[s] < 0 || ms[s] > 500) ? kWarnBadParameter : 0;      // the host's code_of
+            const int32_t dev_code = codes[(size_t)s];                      // the host's
             int32_t ref_code = 0;
             for (int c = 0; c < n_calls; ++c) {
                 if (!(flags[s] & kFlowNoFarend)) q.ref.BufferFarend(far_in + c * len, (size_t)len);
@@ -320,31 +325,41 @@ int64_t sim_mixed_route_uniform(uint64_t seed, int n_sessions, int n_ticks) {
     return -1;
 }
 
-// One routing decision: out[0..5] = launch, sparse_plan, sparse_tick, deferred_lag, mixed_plan, may_lag after; the object's
-// state goes in and out through lag_state[2] = {deferred_lag, may_lag}.
+// One tick of an object of n_sessions of which the first `live` call (half_calls: the first of them makes a half call; other_rates:
+// session 0 runs at another rate than the object), through the host's planner: out[0..5] = launch, sparse_plan, sparse_tick,
+// deferred_lag, mixed_plan, may_lag after; the object's lags go in and out through lag_state[2] = {deferred_lag, may_lag}.
 void sim_mixed_route(int32_t *lag_state, int32_t live, int32_t n_sessions, int n, int force_sparse, int half_calls, int other_rates, int32_t *out) {
-    FlowObjectLag o;
-    o.deferred_lag = lag_state[0];
-    o.may_lag = lag_state[1] != 0;
-    bool mixed = false;
-    const FlowTickRoute r = FlowRouteTickMixed(o, live, n_sessions, n, force_sparse != 0, half_calls != 0, other_rates != 0, &mixed);
-    out[0] = r.launch; out[1] = r.sparse_plan; out[2] = r.sparse_tick; out[3] = r.deferred_lag; out[4] = mixed; out[5] = o.may_lag;
-    lag_state[0] = o.deferred_lag;
-    lag_state[1] = o.may_lag;
+    TickObject o;
+    o.Init(n_sessions, 16000);
+    o.lag.deferred_lag = lag_state[0];
+    o.lag.may_lag = lag_state[1] != 0;
+    o.force_sparse = force_sparse != 0;
+    if (other_rates) o.SetRate(0, 8000);
+    std::vector<uint8_t> flags((size_t)n_sessions, (uint8_t)kFlowIdle);
+    for (int32_t s = 0; s < live; ++s) flags[(size_t)s] = s == 0 && half_calls ? kFlowHalfCall : 0;
+    TickArgs a;
+    a.flags_per_session = flags.data();
+    a.n = n;
+    const TickPlan p = o.Tick(a);
+    out[0] = p.route.launch; out[1] = p.route.sparse_plan; out[2] = p.route.sparse_tick; out[3] = p.route.deferred_lag; out[4] = p.mixed_plan; out[5] = o.lag.may_lag;
+    lag_state[0] = o.lag.deferred_lag;
+    lag_state[1] = o.lag.may_lag;
 }
 
-// The host's argument check of a tick's flags (SessionBatch::Enqueue): 0 = accepted, 1 = AECM_BAD_PARAMETER_ERROR.  Also hands
-// back what the pass found: result[0] = live sessions, [1] = OR of the calling sessions' bytes, [2] = FlowLiveBlockBases agrees
-// (count and every base).
+// The host's check of a tick's flags (aecm_tick_plan.h): 0 = accepted, 1 = AECM_BAD_PARAMETER_ERROR.  Also hands back what the pass
+// found: result[0] = live sessions, [1] = OR of the calling sessions' bytes, [2] = FlowLiveBlockBases agrees (count and every base).
 int sim_mixed_check_flags(const uint8_t *flags, int32_t n_sessions, int n, int32_t *result) {
-    std::vector<uint32_t> bases((size_t)(n_sessions + kFlowPlanBlock - 1) / kFlowPlanBlock), ref(bases.size());
-    uint8_t any = 0;
-    bool both = false;
-    const int32_t live = FlowScanFlags(flags, n_sessions, bases.data(), &any, &both);
-    result[0] = live;
-    result[1] = any;
-    result[2] = live == FlowLiveBlockBases(flags, n_sessions, ref.data()) && bases == ref;
-    return FlowTickFlagsValid(n, any, both) ? 0 : 1;
+    TickObject o;
+    o.Init(n_sessions, 16000);
+    std::vector<uint32_t> ref(o.live_bases.size());
+    TickArgs a;
+    a.flags_per_session = flags;
+    a.n = n;
+    const TickPlan p = o.Plan(a);
+    result[0] = p.live;
+    result[1] = p.any;
+    result[2] = p.live == FlowLiveBlockBases(flags, n_sessions, ref.data()) && o.live_bases == ref;
+    return p.code ? 1 : 0;
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: packet ticks (WebRtcAecmSessions_TickPackets) on sample TAGS -- the method of sim_mixed.cpp, whose whole
-// OBJECT of sessions of both rates this unit takes over.  The device side is what SessionBatch::Enqueue (packets), the planning
+// OBJECT of sessions of both rates this unit takes over.  The device side is what the host's tick planner (packets), the planning
 // kernels (aecm_flow_plan_packets_kernel: FlowTickPackets at the lane's rate; aecm_flow_plan_calls_kernel where the routing falls
 // back to the K-call tick) and aecm_tick_packets_kernel do, in the kernel's own order per call -- spill, far framing (fresh samples
 // from call c's piece of the PACKED row, everything older from the ring), append of the call's n_s samples at near position
@@ -16,11 +16,21 @@ namespace {
 
 struct Object {
     std::vector<std::unique_ptr<Session>> ss;
-    uint32_t near_pos = 0;
-    FlowObjectLag lag;
-    int obj_fs = 16000, other_rates = 0;
+    TickObject host;               // what the host keeps for the object (aecm_tick_plan.h)
     bool has_clean = false;
 };
+
+// The host's side of a tick: check, plan, commit.  False: refused.  *tick_pos: the object's near position before the tick.
+bool HostTick(Object &o, int n, int calls, bool packets, const uint8_t *flags, TickPlan *plan, uint32_t *tick_pos) {
+    TickArgs a;
+    a.flags_per_session = flags;
+    a.n = n;
+    a.calls = calls;
+    a.packets = packets;
+    a.has_clean = o.has_clean;
+    *plan = o.host.Tick(a, tick_pos);
+    return plan->code == 0;
+}
 
 enum PacketsDetail : int {
     P_WHAT = 0, P_SESSION, P_FIELD, P_BLOCKS, P_PACKET_TICKS, P_CALLS_SHAPED, P_ORDINARY, P_BURSTS, P_NOBODY, P_LONGEST_IDLE, P_HALF_SPILL_LATER,
@@ -37,19 +47,15 @@ struct Fail {
     explicit operator bool() const { return what != 0; }
 };
 
-// One ORDINARY tick of the object: SessionBatch::Enqueue (calls == 1) and the three planning kernels + the tick kernels' body, as
+// One ORDINARY tick of the object: the host's plan (calls == 1) and the three planning kernels + the tick kernels' body, as
 // sim_mixed.cpp's fuzz does it.  rows[s]: n samples.
 Fail OrdinaryTick(Object &o, int n, const uint8_t *flags, const int *ms, std::vector<Rows> &rows, int64_t *detail) {
     const int S = (int)o.ss.size();
-    std::vector<uint32_t> bases((size_t)(S + kFlowPlanBlock - 1) / kFlowPlanBlock);
-    uint8_t any = 0;
-    bool both = false;
-    const int32_t live = FlowScanFlags(flags, S, bases.data(), &any, &both);
-    if (!FlowTickFlagsValid(n, any, both)) return Fail{11, -1, 0};
-    bool mixed_plan = false;
-    const FlowTickRoute route = FlowRouteTickMixed(o.lag, live, S, n, false, (any & kFlowHalfCall) != 0, o.other_rates > 0, &mixed_plan);
-    const uint32_t tick_pos = o.near_pos;
-    o.near_pos += (uint32_t)n;
+    TickPlan plan;
+    uint32_t tick_pos;
+    if (!HostTick(o, n, 1, false, flags, &plan, &tick_pos)) return Fail{11, -1, 0};
+    const bool mixed_plan = plan.mixed_plan;
+    const FlowTickRoute route = plan.route;
     if (!route.launch) {
         if (detail) detail[P_NOBODY]++;
         return Fail{};
@@ -59,15 +65,15 @@ Fail OrdinaryTick(Object &o, int n, const uint8_t *flags, const int *ms, std::ve
         const bool idle = (flags[s] & kFlowIdle) != 0, half = !idle && (flags[s] & kFlowHalfCall) != 0;
         FlowPlan planned;
         if (!route.sparse_plan) {
-            if (q.regs.v[F_NEAR_LAG] != 0 || idle || half || q.fs != o.obj_fs) return Fail{8, s, 0};
+            if (q.regs.v[F_NEAR_LAG] != 0 || idle || half || q.fs != o.host.fs) return Fail{8, s, 0};
             FlowRegs r = q.regs;
-            FlowTick(r, o.obj_fs, n, ms[s], flags[s], tick_pos, planned);
+            FlowTick(r, o.host.fs, n, ms[s], flags[s], tick_pos, planned);
             for (int k = 0; k < kFlowTickFields; ++k) q.regs.v[k] = r.v[k];
         } else if (idle) {
             q.regs.v[F_NEAR_LAG] = FlowIdleTick(FlowIdleTick(q.regs.v[F_NEAR_LAG], route.deferred_lag), n);
             continue;
         } else {
-            if (!mixed_plan && (half || q.fs != o.obj_fs)) return Fail{8, s, 0};
+            if (!mixed_plan && (half || q.fs != o.host.fs)) return Fail{8, s, 0};
             q.regs.v[F_NEAR_LAG] = FlowIdleTick(q.regs.v[F_NEAR_LAG], route.deferred_lag);
             if (q.regs.v[F_NEAR_LAG] != 0) {
                 FlowNearMove m;
@@ -76,7 +82,7 @@ Fail OrdinaryTick(Object &o, int n, const uint8_t *flags, const int *ms, std::ve
                 if (o.has_clean) FlowMoveNear(q.clean_ring.data(), (uint32_t)(kRingLen - 1), m);
             }
             if (mixed_plan) FlowTickMixed(q.regs, q.fs, n, ms[s], flags[s], tick_pos, planned);
-            else FlowTick(q.regs, o.obj_fs, n, ms[s], flags[s], tick_pos, planned);
+            else FlowTick(q.regs, o.host.fs, n, ms[s], flags[s], tick_pos, planned);
         }
         if (const int field = q.StateDefect()) return Fail{100, s, field};
         Rows &w = rows[s];
@@ -141,26 +147,22 @@ void PacketBody(Session &q, bool has_clean, int calls, const int32_t (*words)[kF
     }
 }
 
-// One PACKET tick of the object: SessionBatch::Enqueue with `packets`, then the planning and tick kernels it routes to.
+// One PACKET tick of the object: the host's plan with `packets`, then the planning and tick kernels it names.
 // rows[s]: calls * n samples, packed.  idle_before[s]: the session sat out the tick before this one.
 Fail PacketTick(Object &o, int n, int calls, const uint8_t *flags, const int *ms, std::vector<Rows> &rows, const std::vector<int> &idle_before,
                 int64_t *detail) {
     if (calls == 1) return OrdinaryTick(o, n, flags, ms, rows, detail);       // the same launches, the same kernels
     const int S = (int)o.ss.size(), span = calls * n;
-    std::vector<uint32_t> bases((size_t)(S + kFlowPlanBlock - 1) / kFlowPlanBlock);
-    uint8_t any = 0;
-    bool both = false;
-    const int32_t live = FlowScanFlags(flags, S, bases.data(), &any, &both);
-    if (!FlowTickFlagsValid(n, any, both) || (any & kFlowSplitCalls) != 0) return Fail{11, -1, 0};
-    bool mixed_plan = false;
-    const FlowTickRoute route = FlowRouteTickMixed(o.lag, live, S, span, true, (any & kFlowHalfCall) != 0, o.other_rates > 0, &mixed_plan);
-    const uint32_t tick_pos = o.near_pos;
-    o.near_pos += (uint32_t)span;
+    TickPlan plan;
+    uint32_t tick_pos;
+    if (!HostTick(o, n, calls, true, flags, &plan, &tick_pos) || plan.span != span) return Fail{11, -1, 0};
+    const bool mixed_plan = plan.mixed_plan;
+    const FlowTickRoute route = plan.route;
     if (!route.launch) {
         detail[P_NOBODY]++;
         return Fail{};
     }
-    if (!route.sparse_plan) return Fail{12, -1, 0};                            // a K-call tick always goes by the live list
+    if (!route.sparse_plan || !route.sparse_tick || plan.family != (mixed_plan ? kTickFamily_packets : kTickFamily_calls)) return Fail{12, -1, 0};      // a K-call tick always goes by the live list
     detail[mixed_plan ? P_PACKET_TICKS : P_CALLS_SHAPED]++;
     bool live_half = false, live_full = false;
     for (int s = 0; s < S; ++s) {
@@ -195,8 +197,8 @@ Fail PacketTick(Object &o, int n, int calls, const uint8_t *flags, const int *ms
         if (mixed_plan) {
             FlowTickPackets(q.regs, q.fs, n, calls, ms[s], flags[s], tick_pos, sink);
         } else {
-            if (half || q.fs != o.obj_fs) return Fail{8, s, 0};
-            FlowTickCalls(q.regs, o.obj_fs, n, calls, ms[s], flags[s], tick_pos, sink);
+            if (half || q.fs != o.host.fs) return Fail{8, s, 0};
+            FlowTickCalls(q.regs, o.host.fs, n, calls, ms[s], flags[s], tick_pos, sink);
         }
         if (defect) return Fail{100, s, defect};
         if (const int field = q.StateDefect()) return Fail{100, s, field};
@@ -214,7 +216,7 @@ std::vector<int64_t> SnapshotModel(const Object &o, const Session &q) {
     std::vector<int64_t> v;
     for (int k = 0; k < kFlowFieldsUsed; ++k) v.push_back(k == F_NEAR_LAG ? 0 : q.regs.v[k]);
     v.insert(v.end(), q.far_ring.begin(), q.far_ring.end());
-    const uint32_t own = o.near_pos - (uint32_t)q.regs.v[F_NEAR_LAG] - (uint32_t)o.lag.deferred_lag, mask = (uint32_t)(kRingLen - 1);
+    const uint32_t own = (uint32_t)o.host.near_pos - (uint32_t)q.regs.v[F_NEAR_LAG] - (uint32_t)o.host.lag.deferred_lag, mask = (uint32_t)(kRingLen - 1);
     for (uint32_t k = 0; k < 256; ++k) v.push_back(q.out_ring[((uint32_t)q.regs.v[F_BLK_POS] - 256u + k) & mask]);
     for (uint32_t k = 0; k < 64; ++k) v.push_back(q.near_ring[(own - 64u + k) & mask]);
     for (uint32_t k = 0; k < 64; ++k) v.push_back(o.has_clean ? q.clean_ring[(own - 64u + k) & mask] : 0);
@@ -246,15 +248,15 @@ int64_t sim_packets_fuzz(uint64_t seed, int n_sessions, int n_ticks, int rates_m
     const uint32_t starts[3] = {0u, 0xffffffffu - 0xffffffffu % 80u - 800u, (uint32_t)kFlowLagPeriod * 1000u - 400u};
     const int S = n_sessions;
     for (Object *o : {&dev, &twin}) {
-        o->obj_fs = (seed & 1) ? 16000 : 8000;
+        o->host.Init(n_sessions, (seed & 1) ? 16000 : 8000);
         o->has_clean = (seed & 2) != 0;
-        o->near_pos = starts[(seed / 4) % 3];
+        o->host.near_pos = starts[(seed / 4) % 3];
     }
     for (int s = 0; s < S; ++s) {
-        const int fs = rates_mode == 0 ? (rng.chance(50) ? 16000 : 8000) : dev.obj_fs;
+        const int fs = rates_mode == 0 ? (rng.chance(50) ? 16000 : 8000) : dev.host.fs;
         const uint32_t p0 = rng.chance(50) ? 0u : rng.next() * 7u;
         for (Object *o : {&dev, &twin}) {
-            o->other_rates += fs != o->obj_fs;
+            o->host.SetRate(s, fs);
             o->ss.emplace_back(new Session(fs));
             Session &q = *o->ss.back();
             q.regs.v[F_FAR_RP] = q.regs.v[F_FAR_WP] = (int32_t)p0;
@@ -267,7 +269,7 @@ int64_t sim_packets_fuzz(uint64_t seed, int n_sessions, int n_ticks, int rates_m
     const auto fail = [&](const Fail &f) { detail[P_WHAT] = f.what; detail[P_SESSION] = f.session; detail[P_FIELD] = f.field; };
     for (int64_t tick = 0; tick < n_ticks; ++tick) {
         // the object's tick size: an 8 kHz object mostly ticks 80, a 16 kHz object mostly 160
-        const int n = rng.chance(dev.obj_fs == 16000 ? 90 : 30) ? 160 : 80;
+        const int n = rng.chance(dev.host.fs == 16000 ? 90 : 30) ? 160 : 80;
         int calls = rng.range(1, kFlowMaxTickCalls);
         const bool ordinary = rng.chance(25);
         if (ordinary) calls = 1;
@@ -376,7 +378,7 @@ int64_t sim_packets_fuzz(uint64_t seed, int n_sessions, int n_ticks, int rates_m
             if (const int field = q.StateDefect()) { fail(Fail{100, s, field}); return tick; }
             for (int k = 0; k < kFlowTickFields; ++k)
                 if (q.regs.v[k] != t.regs.v[k]) { fail(Fail{20, s, k + 1}); return tick; }
-            if (dev.near_pos != twin.near_pos) { fail(Fail{20, s, F_NEAR_LAG + 1}); return tick; }
+            if (dev.host.near_pos != twin.host.near_pos) { fail(Fail{20, s, F_NEAR_LAG + 1}); return tick; }
             if (SnapshotModel(dev, q) != SnapshotModel(twin, t)) { fail(Fail{21, s, 0}); return tick; }
             if (w.out != tall[s].out || w.bfar != tall[s].bfar || w.bnear != tall[s].bnear || w.bclean != tall[s].bclean) { fail(Fail{6, s, 0}); return tick; }
             idle_before[s] = n_s[s] == 0;

@@ -1,5 +1,5 @@
 // TEST INFRASTRUCTURE: sessions that sit out ticks (AECM_SESSION_IDLE) on sample TAGS -- the method of sim_flow.cpp.  The
-// device side is what SessionBatch::Enqueue, aecm_flow_plan_kernel / aecm_flow_plan_sparse_kernel and the tick kernels do for
+// device side is what the host's tick planner (aecm_tick_plan.h), aecm_flow_plan_kernel / aecm_flow_plan_sparse_kernel and the tick kernels do for
 // ONE session of an object whose other sessions may or may not call (webrtc_aecm_amd/csrc/aecm_flow_plan.h: FlowIdleTick,
 // FlowResync, FlowMoveNear, FlowTick); the reference side is SessionFlow<T> (aecm_session_flow.h), which in an idle tick is
 // simply not called.  Also: the live list of a tick (host half + device half) and FlowStateDefect's view of the lag.
@@ -11,6 +11,7 @@
 #include "aecm_flow_plan.h"
 #include "aecm_ops.h"
 #include "aecm_session_flow.h"
+#include "aecm_tick_plan.h"
 
 namespace {
 
@@ -32,15 +33,30 @@ struct Rng {
 struct DeviceSide {
     FlowRegs regs;
     std::vector<int64_t> far_ring, near_ring, out_ring, far_frames, far_old;
-    uint32_t near_pos = 0;                 // SessionBatch::near_pos_
-    FlowObjectLag lag;                     // SessionBatch::lag_
+    TickObject obj;                        // what the host keeps for the object (its near position, its lags)
     int64_t blocks_done = 0, moves = 0, moved_samples = 0, dense_ticks = 0, deferred_ticks = 0;
-    int fault = 0;                         // 1: a dense tick met a session that lags (the host's routing is wrong)
+    int fault = 0;                         // 1: a dense tick met a session that lags (the host's routing is wrong); 2: the host refused the
+                                           // tick, or a K-call tick did not go by the live list
     DeviceSide() : far_ring(kRingLen, kNone), near_ring(kRingLen, kNone), out_ring(kRingLen, kNone), far_frames(kFlowFarFrameRing, kNone),
                    far_old(2 * kFlowFrame, kNone) {
         int32_t words[kFlowWords];
         FlowInit(words);
         for (int k = 0; k < kFlowFieldsUsed; ++k) regs.v[k] = words[k];
+        obj.Init(3, 16000);
+    }
+    // The host's side of one tick -- check, plan, commit -- of an object of three sessions: this one, one that calls when the caller
+    // says so (others_live) and one that sits out when the caller says so (others_idle); either of the two otherwise does as this
+    // one does.  *tick_pos: the object's near position before the tick.
+    TickPlan HostTick(int n, int calls, int flags, bool idle, bool others_live, bool others_idle, uint32_t *tick_pos) {
+        const uint8_t follows = idle ? (uint8_t)kFlowIdle : (uint8_t)0;
+        const uint8_t f[3] = {idle ? (uint8_t)kFlowIdle : (uint8_t)flags, others_live ? (uint8_t)0 : follows, others_idle ? (uint8_t)kFlowIdle : follows};
+        TickArgs a;
+        a.flags_per_session = f;
+        a.n = n;
+        a.calls = calls;
+        const TickPlan plan = obj.Tick(a, tick_pos);
+        if (plan.code) fault = 2;
+        return plan;
     }
     // aecm_buffer_farend_kernel (as in sim_flow.cpp)
     void BufferFarend(int fs, int len, int calls, const int64_t *far_in) {
@@ -66,19 +82,18 @@ struct DeviceSide {
     bool Tick(int fs, int n, int ms, int flags, bool idle, bool others_live, bool others_idle, const int64_t *far_in, const int64_t *near_in,
               int64_t *out, std::vector<int64_t> *blk_far, std::vector<int64_t> *blk_near) {
         const int64_t mask = kRingLen - 1;
-        // the object: this session, and one other session each that calls / sits out when the caller says so; which launches the
-        // tick takes is the host's own decision (SessionBatch::Enqueue calls the same function)
-        const int n_sessions = 1 + (others_live ? 1 : 0) + (others_idle ? 1 : 0), live = (idle ? 0 : 1) + (others_live ? 1 : 0);
-        const FlowTickRoute route = FlowRouteTick(lag, live, n_sessions, n, false);
+        // which launches the tick takes is the host's own decision
+        uint32_t near_pos;
+        const TickPlan plan = HostTick(n, 1, flags, idle, others_live, others_idle, &near_pos);
+        const FlowTickRoute &route = plan.route;
         if (!route.launch) {                                            // nobody calls: nothing is launched
-            near_pos += (uint32_t)n;
             ++deferred_ticks;
             return false;
         }
         const int32_t deferred_lag = route.deferred_lag;
         FlowPlan planned, p;
         if (!route.sparse_plan) {                                       // aecm_flow_plan_kernel: knows no lags
-            if (regs.v[F_NEAR_LAG] != 0 || lag.deferred_lag != 0) fault = 1;
+            if (regs.v[F_NEAR_LAG] != 0 || obj.lag.deferred_lag != 0) fault = 1;
             FlowRegs r = regs;
             r.v[F_NEAR_LAG] = 0x5a5a5a5a;                               // (not loaded)
             FlowTick(r, fs, n, ms, flags, near_pos, planned);
@@ -99,9 +114,8 @@ struct DeviceSide {
                 FlowTick(regs, fs, n, ms, flags, near_pos, planned);
             }
         }
-        near_pos += (uint32_t)n;
         if (idle) return false;
-        const uint32_t tick_pos = near_pos - (uint32_t)n;
+        const uint32_t tick_pos = near_pos;
         // the tick kernel (dense or sparse: the same body)
         int32_t words[kFlowPlanWords];
         FlowPackPlan(planned, words);
@@ -162,7 +176,7 @@ int64_t sim_sparse_fuzz(uint64_t seed, int fs, int n_ticks, int pattern, int idl
     DeviceSide dev;
     dev.regs.v[F_FAR_RP] = dev.regs.v[F_FAR_WP] = (int32_t)start_pos;
     dev.regs.v[F_FRM_POS] = dev.regs.v[F_BLK_POS] = dev.regs.v[F_OUT_RP] = (int32_t)(start_pos * 3u);
-    dev.near_pos = start_pos * 80u;
+    dev.obj.near_pos = start_pos * 80u;
     SessionFlow<int64_t> ref(kNone);
     ref.Init(fs);
     int64_t far_offered = 0, near_offered = 0, ref_blocks = 0;

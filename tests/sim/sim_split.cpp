@@ -2,7 +2,7 @@
 //   - the two live lists of a split tick: the host's pass over the flags (FlowScanFlagsClean) and the planning kernel's half,
 //     simulated lane by lane -- ballots per wavefront of 64, counts per workgroup of 256, FlowSplitSlot, the kernel's store guard
 //     (aecm_tick_split_plan_kernels.hip);
-//   - the history rule: SessionBatch::Enqueue's order of FlowScanFlags, FlowCleanHistory::Check and Commit, as an object of its own.
+//   - the history rule as the host's planner applies it (aecm_tick_plan.h: the object and the ticks are the product's own).
 // Built as a library for tests/split_sim.py, or (-DSIM_SPLIT_MAIN) as a program of its own, the only form built with sanitizers.
 #include <stdint.h>
 #include <stdio.h>
@@ -10,7 +10,7 @@
 
 #include <vector>
 
-#include "aecm_flow_clean.h"
+#include "aecm_tick_plan.h"
 
 using namespace aecm;
 
@@ -55,32 +55,19 @@ void Lists(const uint8_t *flags, int32_t S, uint32_t *list, int32_t res[4]) {
     res[3] = dropped;
 }
 
-struct Object {
-    int32_t S;
-    FlowCleanHistory h;
-    int64_t position = 0;        // what an accepted tick moves (SessionBatch::near_pos_)
-};
-
-// SessionBatch::Enqueue as far as the clean input goes: 0 accepted, 1 AECM_BAD_PARAMETER_ERROR, 2 AECM_UNSUPPORTED_FUNCTION_ERROR.
-int Tick(Object &o, const uint8_t *flags, int has_clean, int calls, int n, int32_t route[3]) {
-    std::vector<uint32_t> bases((size_t)((o.S + kFlowPlanBlock - 1) / kFlowPlanBlock));
-    int32_t live = o.S;
-    uint8_t any = 0;
-    bool half_and_split = false;
-    if (flags) live = FlowScanFlags(flags, o.S, bases.data(), &any, &half_and_split);
-    if (!FlowTickFlagsValid(n, any, half_and_split)) return 1;
-    FlowCleanTick tick;
-    if (const FlowCleanVerdict v = o.h.Check(flags, any, has_clean != 0, calls, &tick)) return (int)v;
-    int32_t clean_count = 0, plain_count = 0;
-    if (tick.split) {
-        std::vector<uint32_t> cb(bases.size()), pb(bases.size());
-        FlowScanFlagsClean(flags, o.S, cb.data(), pb.data(), &clean_count, &plain_count);
-    }
-    route[0] = tick.split && clean_count > 0;                       // the split launches
-    route[1] = has_clean && !(tick.split && clean_count == 0);      // the tick's kernels take a clean input
-    route[2] = tick.checked;
-    o.position += (int64_t)n * calls;
-    if (live > 0) o.h.Commit(flags, has_clean != 0, tick);
+// A tick of SessionBatch::Enqueue's as far as the host goes -- check, plan, commit: 0 accepted, 1 AECM_BAD_PARAMETER_ERROR,
+// 2 AECM_UNSUPPORTED_FUNCTION_ERROR.
+int Tick(TickObject &o, const uint8_t *flags, int has_clean, int calls, int n, int32_t route[3]) {
+    TickArgs a;
+    a.flags_per_session = flags;
+    a.n = n;
+    a.calls = calls;
+    a.has_clean = has_clean != 0;
+    const TickPlan plan = o.Tick(a);
+    if (plan.code) return plan.code == kTickUnsupported ? 2 : 1;
+    route[0] = plan.split_tick;                  // the split launches
+    route[1] = plan.clean_plane;                 // the tick's kernels take a clean input
+    route[2] = plan.clean_tick.checked;
     return 0;
 }
 
@@ -108,17 +95,18 @@ int SelfCheck() {
                 if (list[(size_t)res[2] + i] != want_plain[i]) return __LINE__;
         }
     }
-    Object o{8, {}};
-    o.h.Reset(8);
+    TickObject o;
+    o.Init(8, 16000);
+    const FlowCleanHistory &h = o.history;
     int32_t route[3];
     const uint8_t mixed[8] = {0, 16, 0, 16, 4, 4 | 16, 0, 16}, swapped[8] = {16, 0, 4, 4, 4, 4, 4, 4};
-    if (Tick(o, nullptr, 1, 1, 160, route) != 0 || o.h.Get(1) != kCleanAlways) return __LINE__;
-    if (Tick(o, mixed, 1, 1, 160, route) != 1 || o.position != 160 || o.h.split_used) return __LINE__;
-    o.h.Reset(8);
-    if (Tick(o, mixed, 1, 1, 160, route) != 0 || !route[0] || o.h.Get(1) != kCleanNever || o.h.Get(4) != kCleanNone) return __LINE__;
+    if (Tick(o, nullptr, 1, 1, 160, route) != 0 || h.Get(1) != kCleanAlways) return __LINE__;
+    if (Tick(o, mixed, 1, 1, 160, route) != 1 || o.near_pos != 160 || h.split_used) return __LINE__;
+    o.Init(8, 16000);
+    if (Tick(o, mixed, 1, 1, 160, route) != 0 || !route[0] || h.Get(1) != kCleanNever || h.Get(4) != kCleanNone) return __LINE__;
     if (Tick(o, swapped, 1, 1, 160, route) != 1 || Tick(o, nullptr, 1, 1, 160, route) != 1 || Tick(o, mixed, 1, 2, 160, route) != 2) return __LINE__;
-    o.h.ResetSession(1);
-    if (o.h.Get(1) != kCleanNone || o.h.Get(3) != kCleanNever) return __LINE__;
+    o.InitSession(1, 16000);
+    if (h.Get(1) != kCleanNone || h.Get(3) != kCleanNever) return __LINE__;
     return 0;
 }
 
@@ -130,26 +118,28 @@ void sim_split_lists(const uint8_t *flags, int32_t n_sessions, uint32_t *list, i
 int32_t sim_split_list_entries(int32_t n_sessions) { return (int32_t)FlowSplitListEntries((uint32_t)n_sessions); }
 
 void *sim_split_object_new(int32_t n_sessions) {
-    Object *o = new Object{n_sessions, {}};
-    o->h.Reset((size_t)n_sessions);
+    TickObject *o = new TickObject();
+    o->Init(n_sessions, 16000);
     return o;
 }
-void sim_split_object_free(void *o) { delete static_cast<Object *>(o); }
+void sim_split_object_free(void *o) { delete static_cast<TickObject *>(o); }
 void sim_split_object_init(void *o) {
-    Object *p = static_cast<Object *>(o);
-    p->h.Reset((size_t)p->S);
-    p->position = 0;
+    TickObject *p = static_cast<TickObject *>(o);
+    p->Init(p->n_sessions, p->fs);
 }
 int32_t sim_split_object_tick(void *o, const uint8_t *flags, int32_t has_clean, int32_t calls, int32_t n, int32_t *route) {
-    return Tick(*static_cast<Object *>(o), flags, has_clean, calls, n, route);
+    return Tick(*static_cast<TickObject *>(o), flags, has_clean, calls, n, route);
 }
-void sim_split_object_reset_session(void *o, int32_t session) { static_cast<Object *>(o)->h.ResetSession(session); }
+void sim_split_object_reset_session(void *o, int32_t session) {
+    TickObject *p = static_cast<TickObject *>(o);
+    p->InitSession(session, p->fs);
+}
 // modes[S], then what else an observer could see: {position, split_used}
 void sim_split_object_state(void *o, uint8_t *modes, int64_t *rest) {
-    Object *p = static_cast<Object *>(o);
-    for (int32_t s = 0; s < p->S; ++s) modes[s] = p->h.Get(s);
-    rest[0] = p->position;
-    rest[1] = p->h.split_used;
+    TickObject *p = static_cast<TickObject *>(o);
+    for (int32_t s = 0; s < p->n_sessions; ++s) modes[s] = p->history.Get(s);
+    rest[0] = p->near_pos;
+    rest[1] = p->history.split_used;
 }
 int32_t sim_split_self_check(void) { return SelfCheck(); }
 

@@ -17,7 +17,7 @@ _lib = None
 
 
 def build():
-    deps = [SRC, simlib.CSRC / "aecm_flow_plan.h", simlib.CSRC / "aecm_session_flow.h", simlib.CSRC / "aecm_ops.h"]
+    deps = [SRC, simlib.CSRC / "aecm_flow_plan.h", simlib.CSRC / "aecm_flow_clean.h", simlib.CSRC / "aecm_tick_plan.h", simlib.CSRC / "aecm_session_flow.h", simlib.CSRC / "aecm_ops.h"]
     if SO.exists() and all(SO.stat().st_mtime >= d.stat().st_mtime for d in deps):
         return
     SO.parent.mkdir(parents=True, exist_ok=True)

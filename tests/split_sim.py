@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE: tests/_build/libaecm_sim_split.so -- tests/sim/sim_split.cpp: the two live lists of a tick with
 AECM_SESSION_NO_CLEAN sessions (host half + the planning kernel's half, lane by lane) and the per-session clean history as
-SessionBatch::Enqueue applies it.  Header-only on the product's side (webrtc_aecm_amd/csrc/aecm_flow_clean.h, aecm_flow_plan.h),
+the host's tick planner (aecm_tick_plan.h) applies it.  Header-only on the product's side (webrtc_aecm_amd/csrc/aecm_tick_plan.h, aecm_flow_clean.h, aecm_flow_plan.h),
 like tests/mixed_sim.py.  standalone(): the same source as a program with its own main, the only form ever built with sanitizers."""
 from __future__ import annotations
 
@@ -14,7 +14,7 @@ import simlib
 
 SRC = simlib.ROOT / "tests" / "sim" / "sim_split.cpp"
 SO = simlib.SIM_SO.parent / "libaecm_sim_split.so"
-DEPS = [SRC, simlib.CSRC / "aecm_flow_clean.h", simlib.CSRC / "aecm_flow_plan.h"]
+DEPS = [SRC, simlib.CSRC / "aecm_tick_plan.h", simlib.CSRC / "aecm_flow_clean.h", simlib.CSRC / "aecm_flow_plan.h"]
 ACCEPTED, BAD_PARAMETER, UNSUPPORTED = 0, 1, 2
 _lib = None
 
@@ -79,7 +79,7 @@ def lists(flags):
 
 
 class Object:
-    """The clean history of an object of S sessions, ticked as SessionBatch::Enqueue ticks it."""
+    """An object of S sessions as the host keeps it, ticked by the host's planner."""
 
     def __init__(self, n_sessions):
         self.S = n_sessions

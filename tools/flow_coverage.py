@@ -5,7 +5,7 @@ The sibling of tools/decision_coverage.py for webrtc_aecm_amd/csrc/aecm_flow_pla
 FlowDelayComp, FlowMoveFarReadPtr, FlowFarendCall, FlowBurstBegin, FlowResync, FlowMoveNear, FlowTickMixed / Calls / Packets,
 FlowPacketCallSize, FlowLiveSlot).  Builds the host harness tests/sim/sim_flowcov.cpp with -O0 --coverage into a library of its own under
 tests/_build/flowcov/, drives whole objects of sessions through it in a child python process (the counters are written when it
-exits) the way the planning kernels drive them -- one lane per session, routed as SessionBatch::Enqueue routes a tick to the dense,
+exits) the way the planning kernels drive them -- one lane per session, planned by the host's own planner (aecm_tick_plan.h), which takes a tick to the dense,
 sparse, mixed, K-call or packets planner, far-end bursts in between -- and reads `gcov -b -c --json-format`.  Every run is a parity
 run: the plans, executed as the tick kernels execute them, must move the sample tags SessionFlow<T> moves.
 
@@ -49,10 +49,9 @@ ROOT = Path(__file__).resolve().parent.parent
 CSRC = ROOT / "webrtc_aecm_amd" / "csrc"
 OUT = ROOT / "tests" / "_build" / "flowcov"
 SRC = ROOT / "tests" / "sim" / "sim_flowcov.cpp"
-DEPS = [SRC, CSRC / "aecm_flow_plan.h", CSRC / "aecm_session_flow.h", CSRC / "aecm_state.h"]
+DEPS = [SRC, CSRC / "aecm_flow_plan.h", CSRC / "aecm_flow_clean.h", CSRC / "aecm_tick_plan.h", CSRC / "aecm_session_flow.h", CSRC / "aecm_state.h"]
 FLOW_FUNCTIONS = {"FlowTick", "FlowStartup", "FlowEstBufDelay", "FlowDelayComp", "FlowMoveFarReadPtr", "FlowFarendCall", "FlowBurstBegin", "FlowResync",
                   "FlowMoveNear", "FlowTickMixed", "FlowTickCalls", "FlowTickPackets", "FlowPacketCallSize", "FlowLiveSlot"}
-KERNELS = ("none", "dense", "sparse", "mixed", "calls", "packets")
 WAVE = 64
 SHARDS = 10                                     # child processes of a measurement (each runs every tenth object)
 # evaluated once per iteration of a constant loop with a wave-uniform operand (FlowLiveSlot: w < wave, the lane's wavefront within its
@@ -81,6 +80,15 @@ def build(coverage=True):
     subprocess.check_call(["g++", *(["--coverage"] if coverage else []), "-shared", str(obj), "-o", str(tmp)])
     os.replace(tmp, so)
     return so
+
+
+def family_names():
+    """The kernel families of a tick by number: the one list, AECM_TICK_FAMILIES of aecm_tick_plan.h (TickFamily), read from the source."""
+    line = re.search(r"^#define AECM_TICK_FAMILIES\(X\)(.*)$", (CSRC / "aecm_tick_plan.h").read_text(), re.M).group(1)
+    return tuple(re.findall(r"X\((\w+)\)", line))
+
+
+KERNELS = family_names()
 
 
 class Harness:
@@ -116,7 +124,7 @@ class Harness:
 
 
 # ---- the record of outcomes -----------------------------------------------------------------------------------------------------
-PLANNERS = KERNELS[1:]
+PLANNERS = tuple(k for k in KERNELS if k not in ("nothing", "split"))      # (the harness passes no clean plane: no split tick)
 
 
 def tally(res, K):        # K[T]: call pairs per tick and session (an ordinary tick: 1, though a split tick makes two)

@@ -13,6 +13,7 @@
 #ifndef AECM_AMD_FLOW_CLEAN_H_
 #define AECM_AMD_FLOW_CLEAN_H_
 
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -73,8 +74,9 @@ struct FlowCleanTick {
 };
 
 struct FlowCleanHistory {
-    std::vector<uint8_t> mode;      // [S] FlowCleanMode
-    uint8_t pending = 0;            // what ticks WITHOUT a flags array gave every session since `mode` was last brought up to date:
+    // (mode and pending are mutable for Fold alone: bringing the one up to date with the other changes nothing Get can tell)
+    mutable std::vector<uint8_t> mode;      // [S] FlowCleanMode
+    mutable uint8_t pending = 0;            // what ticks WITHOUT a flags array gave every session since `mode` was last brought up to date:
                                     // such a tick must not cost a pass over the sessions, so it leaves its mark here
     bool split_used = false;        // the object has accepted a split tick since its last Init: every tick is checked from then on
 
@@ -83,7 +85,7 @@ struct FlowCleanHistory {
         pending = 0;
         split_used = false;
     }
-    void Fold() {
+    void Fold() const {
         if (!pending) return;
         for (uint8_t &m : mode) m |= pending;
         pending = 0;
@@ -101,7 +103,7 @@ struct FlowCleanHistory {
     // May the tick be made?  flags: the per-session bytes or null (then everybody calls with no bit of interest set), any = the OR of
     // the calling sessions' bytes (FlowScanFlags), calls = call pairs per session.  Changes nothing that can be observed (it may bring
     // `mode` up to date with `pending`).
-    FlowCleanVerdict Check(const uint8_t *flags, uint8_t any, bool has_clean, int32_t calls, FlowCleanTick *tick) {
+    FlowCleanVerdict Check(const uint8_t *flags, uint8_t any, bool has_clean, int32_t calls, FlowCleanTick *tick) const {
         tick->split = has_clean && flags != nullptr && (any & (uint8_t)kFlowNoClean) != 0;
         tick->checked = tick->split || split_used;
         if (tick->split && calls > 1) return kCleanUnsupported;

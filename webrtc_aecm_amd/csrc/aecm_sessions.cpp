@@ -14,6 +14,11 @@ namespace aecm {
 
 #define AECM_HIP_OK(expr) ((expr) == hipSuccess)
 
+static_assert(kTickUnspecified == AECM_UNSPECIFIED_ERROR && kTickUnsupported == AECM_UNSUPPORTED_FUNCTION_ERROR &&
+                  kTickUninitialized == AECM_UNINITIALIZED_ERROR && kTickNullPointer == AECM_NULL_POINTER_ERROR &&
+                  kTickBadParameter == AECM_BAD_PARAMETER_ERROR && kTickWarning == AECM_BAD_PARAMETER_WARNING,
+              "aecm_tick_plan.h returns the AECM_* codes");
+
 SessionBatch *SessionBatch::Create(int num_streams, int device_id) {
     BatchEngine *e = BatchEngine::Create(num_streams, device_id);
     if (!e) return nullptr;
@@ -33,7 +38,6 @@ SessionBatch *SessionBatch::Create(int num_streams, int device_id) {
                     AECM_HIP_OK(hipMalloc((void **)&b->far_old_, S * 2 * kFlowFrame * 2));
     bool slots = ok;
     const size_t plan_blocks = (S + kFlowPlanBlock - 1) / kFlowPlanBlock;
-    b->live_bases_.assign(plan_blocks, 0u);
     for (int k = 0; k < kArgSlots && slots; ++k)
         slots = AECM_HIP_OK(hipHostMalloc((void **)&b->ms_host_[k], S * sizeof(int16_t), hipHostMallocMapped)) &&
                 AECM_HIP_OK(hipHostMalloc((void **)&b->flags_host_[k], S, hipHostMallocMapped)) &&
@@ -78,7 +82,7 @@ SessionBatch::~SessionBatch() {
 // WebRtcAecm_Init of the wrapper side of sessions [first, first + count): one launch (aecm_kernels.h).
 bool SessionBatch::ResetFlowRows(int first, int count) {
     TickIo tio{nullptr, nullptr, nullptr, nullptr, 0, 0, far_ring_, near_ring_, clean_ring_, out_ring_, kRing, 0};
-    TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, nullptr, nullptr, 0, 0, fs_};
+    TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, nullptr, nullptr, 0, 0, tick_.fs};
     return AECM_HIP_OK(LaunchResetSessions(tio, fio, engine_->num_streams(), first, count, engine_->stream()));
 }
 
@@ -90,12 +94,7 @@ int32_t SessionBatch::Init(int32_t samp_freq) {
     if (!AECM_HIP_OK(hipMemsetAsync(near_ring_, 0, bytes, engine_->stream())) ||
         (clean_ring_ && !AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, engine_->stream()))) || !ResetFlowRows(0, S))
         return AECM_UNSPECIFIED_ERROR;
-    near_pos_ = 0;
-    lag_ = FlowObjectLag();
-    fs_ = samp_freq;
-    rates_.assign((size_t)S, samp_freq);
-    clean_history_.Reset((size_t)S);
-    other_rates_ = 0;
+    tick_.Init(S, samp_freq);
     poisoned_ = false;
     return 0;
 }
@@ -107,27 +106,22 @@ int32_t SessionBatch::InitRates(int32_t samp_freq, const int32_t *rates) {
     for (int s = 0; s < S; ++s)
         if (rates[s] != 8000 && rates[s] != 16000) return AECM_BAD_PARAMETER_ERROR;
     if (int32_t rc = Init(samp_freq)) return rc;
-    if (!engine_->InitStreamsOfOtherRate(rates)) { fs_ = 0; return AECM_UNSPECIFIED_ERROR; }      // (the wrapper state knows no rate)
-    for (int s = 0; s < S; ++s) SetRate(s, rates[s]);
+    if (!engine_->InitStreamsOfOtherRate(rates)) { tick_.Forget(); return AECM_UNSPECIFIED_ERROR; }      // (the wrapper state knows no rate)
+    for (int s = 0; s < S; ++s) tick_.SetRate(s, rates[s]);
     return 0;
-}
-
-void SessionBatch::SetRate(int session, int32_t fs) {
-    other_rates_ += (fs != fs_) - (rates_[(size_t)session] != fs_);
-    rates_[(size_t)session] = fs;
 }
 
 int32_t SessionBatch::GetSessionRate(int session, int32_t *samp_freq) const {
     if (samp_freq == nullptr) return AECM_NULL_POINTER_ERROR;
     if (int32_t rc = CheckSession(session)) return rc;
-    *samp_freq = rates_[(size_t)session];
+    *samp_freq = tick_.rates[(size_t)session];
     return 0;
 }
 
 int32_t SessionBatch::GetSessionCleanMode(int session, int32_t *mode) const {
     if (mode == nullptr) return AECM_NULL_POINTER_ERROR;
     if (int32_t rc = CheckSession(session)) return rc;
-    *mode = clean_history_.Get(session);
+    *mode = tick_.history.Get(session);
     return 0;
 }
 
@@ -146,7 +140,7 @@ bool SessionBatch::SplitTickTwoLaunches(int calling) const {
 }
 
 int32_t SessionBatch::CheckSession(int session) const {
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
     if (session < 0 || session >= engine_->num_streams()) return AECM_BAD_PARAMETER_ERROR;
     return 0;
@@ -155,17 +149,16 @@ int32_t SessionBatch::CheckSession(int session) const {
 // WebRtcAecm_Init of ONE session (same sampling rate as the batch): fresh core state, fresh wrapper state, and rings
 // that read as never written (a fresh jitter buffer's read pointer can be moved back over never-written memory, the
 // output ring is stuffed from it: ring_buffer.c:75-82).
-int32_t SessionBatch::InitSession(int session) { return InitSessionRate(session, fs_); }
+int32_t SessionBatch::InitSession(int session) { return InitSessionRate(session, tick_.fs); }
 
 // The same at a rate of the caller's choice; the slot then runs at that rate (InitSession: back at the object's own).
 int32_t SessionBatch::InitSessionRate(int session, int32_t samp_freq) {
-    if (int32_t rc = CheckSession(session)) return rc;              // (an uninitialised object: fs_ == 0 never gets further)
+    if (int32_t rc = CheckSession(session)) return rc;              // (an uninitialised object: tick_.fs == 0 never gets further)
     if (samp_freq != 8000 && samp_freq != 16000) return AECM_BAD_PARAMETER_ERROR;
     // two launches, ordered before the next tick on the object's stream: no synchronisation with the host
     const bool ok = AECM_HIP_OK(hipSetDevice(device_)) && engine_->InitStreamsAtRate(session, 1, samp_freq) && ResetFlowRows(session, 1);
     if (!ok) { poisoned_ = true; return AECM_UNSPECIFIED_ERROR; }
-    SetRate(session, samp_freq);
-    clean_history_.ResetSession(session);
+    tick_.InitSession(session, samp_freq);
     return 0;
 }
 
@@ -199,7 +192,7 @@ int32_t SessionBatch::GetEchoPathSession(int session, void *path, size_t size_by
 }
 
 int32_t SessionBatch::SetConfig(int16_t cng_mode, int16_t echo_mode) {
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
     if (cng_mode != AecmFalse && cng_mode != AecmTrue) return AECM_BAD_PARAMETER_ERROR;
     if (echo_mode < 0 || echo_mode > 4) {
@@ -245,7 +238,7 @@ int SessionBatch::AcquireArgSlot(bool needed, bool *ok) {
 int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_samples, int32_t calls, const uint8_t *calls_per_session,
                                    bool host_pointers, bool wait, void *wait_event, void *done_event) {
     if (far == nullptr) return AECM_NULL_POINTER_ERROR;                                  // the order of WebRtcAecm_GetBufferFarendError (:195-213)
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (n_samples != 80 && n_samples != 160) return AECM_BAD_PARAMETER_ERROR;
     if (calls < 0 || calls > 255 || stride < (int64_t)n_samples * calls) return AECM_BAD_PARAMETER_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
@@ -261,11 +254,8 @@ int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_
         const int slot = AcquireArgSlot(calls_per_session != nullptr, &slot_ok);
         if (!slot_ok) return Fail();
         if (calls_per_session) memcpy(flags_host_[slot], calls_per_session, (size_t)S);     // pinned + mapped: the kernel reads it in place
-        if (wait_event && !AECM_HIP_OK(hipStreamWaitEvent(st, static_cast<hipEvent_t>(wait_event), 0))) {
-            (void)hipGetLastError();
-            return AECM_BAD_PARAMETER_ERROR;                                              // nothing has been enqueued: no poison
-        }
-        TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, nullptr, nullptr, 0, 0, fs_};
+        if (!WaitForCallerEvent(wait_event)) return AECM_BAD_PARAMETER_ERROR;             // nothing has been enqueued: no poison
+        TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, nullptr, nullptr, 0, 0, tick_.fs};
         const uint8_t *calls_dev = calls_per_session ? flags_dev_[slot] : nullptr;
         bool ok = true;
         if (!host_pointers) {
@@ -293,140 +283,96 @@ int32_t SessionBatch::BufferFarend(const int16_t *far, int64_t stride, size_t n_
     return 0;
 }
 
+// The kernels wait for the caller's event first.  False: the handle was refused -- nothing has been enqueued for it, no poison.
+bool SessionBatch::WaitForCallerEvent(void *wait_event) {
+    if (!wait_event || AECM_HIP_OK(hipStreamWaitEvent(engine_->stream(), static_cast<hipEvent_t>(wait_event), 0))) return true;
+    (void)hipGetLastError();
+    return false;
+}
+
+// A grow-only device buffer of `*have` units: at least `need` afterwards, contents not kept.
+int32_t SessionBatch::Grow(void **buf, size_t *have, size_t need, size_t unit) {
+    if (need <= *have) return 0;
+    if (*buf && !AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return Fail();      // (nothing enqueued may still use the old one)
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    if (!AECM_HIP_OK(hipMalloc(buf, need * unit))) { *buf = nullptr; return AECM_UNSPECIFIED_ERROR; }
+    *have = need;
+    return 0;
+}
+// The same for a buffer of one size, allocated by the first call that needs it.
+int32_t SessionBatch::GrowOnce(void **buf, size_t bytes) {
+    size_t have = *buf ? bytes : 0;
+    return Grow(buf, &have, bytes, 1);
+}
+
+// The clean near-end ring, allocated and zeroed (a ring that may hold anything is no ring) by the first call that needs it.
+int32_t SessionBatch::EnsureCleanRing() {
+    if (clean_ring_) return 0;
+    const size_t bytes = (size_t)engine_->num_streams() * kRing * 2;
+    if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
+    if (AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, engine_->stream()))) return 0;
+    (void)hipFree(clean_ring_);
+    clean_ring_ = nullptr;
+    return Fail();
+}
+
+// Check -> plan -> prepare -> commit -> launch.  The first two are host logic without a device (aecm_tick_plan.h) on either side
+// of the one device call between them; a tick refused by either has changed nothing.
 int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out, int64_t stride, size_t n_samples,
                               int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes,
                               bool host_pointers, void *wait_event, void *done_event, int flags, int32_t calls, bool packets) {
-    if (near == nullptr || out == nullptr) return AECM_NULL_POINTER_ERROR;
-    if (far == nullptr) {                 // only a tick in which nobody makes a WebRtcAecm_BufferFarend call needs no far rows
-        bool nobody = flags_per_session ? true : (flags & kNoFarend) != 0;
-        if (flags_per_session && fs_ != 0)
-            for (int s = 0; s < engine_->num_streams() && nobody; ++s) nobody = (flags_per_session[s] & (kNoFarend | kIdle)) != 0;
-        if (!nobody) return AECM_NULL_POINTER_ERROR;
-    }
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
-    if (n_samples != 80 && n_samples != 160) return AECM_BAD_PARAMETER_ERROR;       // compared as size_t: 2^32 + 80 is not 80
-    // calls: the call pairs of n_samples every session that calls makes in this tick (TickCalls; 1: the tick of old, by the
-    // launches and kernels of old) -- call c on samples [c n, (c + 1) n) of every row
-    if (calls < 1 || calls > kFlowMaxTickCalls) return AECM_BAD_PARAMETER_ERROR;
-    if (stride < (int64_t)n_samples * calls) return AECM_BAD_PARAMETER_ERROR;
-    if (poisoned_) return AECM_UNSPECIFIED_ERROR;
-    // the tick kernel exists for the fast cross-lane primitives only: a batch switched to the safe variant is told so (and
-    // stays usable after switching back) instead of being poisoned
-    if (engine_->variant() != kVariantFast) return AECM_UNSUPPORTED_FUNCTION_ERROR;
-    // K calls per row of a session of the other rate (K half calls, for an 8 kHz session of a 16 kHz object) is a layout of its own:
-    // the packed rows of a packet tick (packets; TickPackets), which TickCalls keeps refusing
-    if (calls > 1 && other_rates_ > 0 && !packets) return AECM_UNSUPPORTED_FUNCTION_ERROR;
-    const int n = (int)n_samples, span = n * calls;          // span: the samples of the tick in every row
-    const bool k_calls = calls > 1;
+    // ---- check
+    if (const int32_t rc = tick_.CheckArgs(far != nullptr, near != nullptr && out != nullptr, flags_per_session, flags, n_samples, calls, stride, packets,
+                                           poisoned_, engine_->variant() == kVariantFast))
+        return rc;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
-    const int S = engine_->num_streams();
-    hipStream_t st = engine_->stream();
     if (!EventUsable(wait_event) || !EventUsable(done_event)) return AECM_BAD_PARAMETER_ERROR;
-    // Who calls in this tick (kIdle: neither call; the other bits of an idle session's byte mean nothing).  One pass over the
-    // flags: the live count, and per planning workgroup the live sessions before it (what the device needs for the live list).
-    int live = S;
-    uint8_t any = flags_per_session ? 0 : (uint8_t)flags;
-    bool half_and_split = false;
-    if (flags_per_session) live = FlowScanFlags(flags_per_session, S, live_bases_.data(), &any, &half_and_split);
-    if (!FlowTickFlagsValid(n, any, half_and_split)) return AECM_BAD_PARAMETER_ERROR;     // two 80-sample calls, or 80 of 160, need 160 samples
-    // a K-call tick's calls are whole calls of n samples; a packet tick's are whole calls of the session's own size (80 with kHalfCall)
-    if (k_calls && (any & (packets ? kSplitCalls : kSplitCalls | kHalfCall)) != 0) return AECM_BAD_PARAMETER_ERROR;
-    const bool half_calls = flags_per_session && (any & kHalfCall) != 0;                  // some session that calls makes a half call
-    // kNoClean (aecm_flow_clean.h): a tick that gives a calling session another kind of Process call than it has had is refused; the
-    // two lists of a tick that has callers of both kinds.  All callers flagged: the tick without a clean input, by its launches.
-    FlowCleanTick clean_tick;
-    if (const FlowCleanVerdict v = clean_history_.Check(flags_per_session, any, clean != nullptr, calls, &clean_tick))
-        return v == kCleanUnsupported ? AECM_UNSUPPORTED_FUNCTION_ERROR : AECM_BAD_PARAMETER_ERROR;
-    const bool had_clean = clean != nullptr;
-    int32_t clean_count = 0, plain_count = 0;
-    if (clean_tick.split) {
-        split_bases_.resize(2 * live_bases_.size());
-        FlowScanFlagsClean(flags_per_session, S, split_bases_.data(), split_bases_.data() + live_bases_.size(), &clean_count, &plain_count);
-        if (clean_count == 0) clean = nullptr;
-    }
-    const bool split_tick = clean_tick.split && clean_count > 0;
-    const auto idle = [&](int s) { return flags_per_session && (flags_per_session[s] & kIdle) != 0; };
-    if (live == 0) {
-        // Nobody calls: nothing is launched.  The object's position moves on all the same; the sessions learn of it with the
-        // next tick somebody makes (aecm_flow_plan.h: FlowRouteTick).
-        if (wait_event && !AECM_HIP_OK(hipStreamWaitEvent(st, static_cast<hipEvent_t>(wait_event), 0))) {
-            (void)hipGetLastError();
-            return AECM_BAD_PARAMETER_ERROR;
-        }
-        near_pos_ += span;
-        (void)FlowRouteTick(lag_, 0, S, span, force_sparse_);
+    // ---- plan
+    TickArgs args;
+    args.flags_per_session = flags_per_session;
+    args.flags = flags;
+    args.n = (int)n_samples;
+    args.calls = calls;
+    args.packets = packets;
+    args.has_clean = clean != nullptr;
+    args.host_pointers = host_pointers;
+    args.ms_per_session = ms_per_session != nullptr;
+    const TickPlan plan = tick_.Plan(args);
+    if (plan.code) return plan.code;
+    const int S = engine_->num_streams(), n = args.n, span = plan.span;
+    hipStream_t st = engine_->stream();
+    if (plan.family == kTickFamily_nothing) {
+        // Nobody calls: nothing is launched and no slot rotates, but the caller's events are honoured, and the object's position
+        // moves on all the same; the sessions learn of it with the next tick somebody makes (aecm_flow_plan.h: FlowRouteTick).
+        if (!WaitForCallerEvent(wait_event)) return AECM_BAD_PARAMETER_ERROR;
+        tick_.Commit(plan);
         if (codes) memset(codes, 0, (size_t)S * sizeof(int32_t));
-        if (host_pointers)
+        if (plan.zero_out)
             for (int s = 0; s < S; ++s) memset(out + (size_t)s * stride, 0, (size_t)span * 2);
         if (done_event && !AECM_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(done_event), st))) return Fail();
         return 0;
     }
-    // (as FlowRouteTick will say below, once the tick is certain to be enqueued; a K-call tick always goes by the live list)
-    const bool sparse_tick = live < S || force_sparse_ || k_calls || split_tick;
-    if (split_tick && !split_live_dev_ && !AECM_HIP_OK(hipMalloc((void **)&split_live_dev_, FlowSplitListEntries((uint32_t)S) * sizeof(uint32_t)))) {
-        split_live_dev_ = nullptr;
-        return AECM_UNSPECIFIED_ERROR;
-    }
-    if (k_calls && !calls_plans_ &&
-        !AECM_HIP_OK(hipMalloc((void **)&calls_plans_, (size_t)S * kFlowMaxTickCalls * kFlowPlanWords * sizeof(int32_t)))) {
-        calls_plans_ = nullptr;
-        return AECM_UNSPECIFIED_ERROR;
-    }
-    // host audio of a K-call tick: the staging planes grow to calls * n samples per row (grow-only)
-    if (host_pointers && (size_t)span > io_row_) {
-        if (!AECM_HIP_OK(hipStreamSynchronize(st))) return Fail();      // (nothing enqueued may still use the old planes)
-        int16_t *grown = nullptr;
-        if (!AECM_HIP_OK(hipMalloc((void **)&grown, 4 * (size_t)S * span * 2))) return AECM_UNSPECIFIED_ERROR;
-        (void)hipFree(io_dev_);
-        io_dev_ = grown;
-        io_row_ = (size_t)span;
-    }
-    if (clean && !clean_ring_) {
-        const size_t bytes = (size_t)S * kRing * 2;
-        if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
-        if (!AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, st))) {
-            (void)hipFree(clean_ring_);
-            clean_ring_ = nullptr;
-            return Fail();
-        }
-    }
-    auto fail = [&]() -> int32_t { return Fail(); };
-    // this tick's argument slot
+    // ---- prepare.  What the tick's kind needs for the first time is allocated first: a failure here returns before anything is
+    // committed and before the slot rotates.
+    if (plan.split_tick)
+        if (const int32_t rc = GrowOnce((void **)&split_live_dev_, FlowSplitListEntries((uint32_t)S) * sizeof(uint32_t))) return rc;
+    if (plan.k_calls)
+        if (const int32_t rc = GrowOnce((void **)&calls_plans_, (size_t)S * kFlowMaxTickCalls * kFlowPlanWords * sizeof(int32_t))) return rc;
+    if (host_pointers)      // host audio of a K-call tick: the staging planes grow to calls * n samples per row
+        if (const int32_t rc = Grow((void **)&io_dev_, &io_row_, (size_t)span, 4 * (size_t)S * 2)) return rc;
+    if (!plan.clean_plane) clean = nullptr;      // (every caller carries kNoClean: the tick without a clean input)
+    if (clean)
+        if (const int32_t rc = EnsureCleanRing()) return rc;
+    // This tick's argument slot, acquired before the caller's event is waited for.
     bool slot_ok;
-    const int slot = AcquireArgSlot(ms_per_session || flags_per_session || sparse_tick, &slot_ok);
-    if (!slot_ok) return fail();
-    auto code_of = [](int16_t v) -> int32_t { return (v < 0 || v > 500) ? AECM_BAD_PARAMETER_WARNING : 0; };
-    int32_t first_rc = 0;
-    if (ms_per_session) {
-        int lo = ms_per_session[0], hi = lo;                                // one vectorisable pass; the per-session codes
-        for (int s = 1; s < S; ++s) {                                       // only need a second one when somebody is out of range
-            lo = std::min<int>(lo, ms_per_session[s]);
-            hi = std::max<int>(hi, ms_per_session[s]);
-        }
-        if (lo < 0 || hi > 500) {
-            for (int s = 0; s < S; ++s) {
-                const int32_t rc = idle(s) ? 0 : code_of(ms_per_session[s]);      // an idle session makes no call: no code
-                if (codes) codes[s] = rc;
-                if (rc != 0 && first_rc == 0) first_rc = rc;
-            }
-        } else if (codes) {
-            memset(codes, 0, (size_t)S * sizeof(int32_t));
-        }
-        memcpy(ms_host_[slot], ms_per_session, (size_t)S * sizeof(int16_t));      // pinned + mapped
-    } else {
-        first_rc = code_of(ms);
-        if (codes)
-            for (int s = 0; s < S; ++s) codes[s] = idle(s) ? 0 : first_rc;
-    }
-    if (flags_per_session) {
-        memcpy(flags_host_[slot], flags_per_session, (size_t)S);
-    }
-    if (sparse_tick) {
-        if (!flags_per_session)
-            for (size_t b = 0; b < live_bases_.size(); ++b) live_bases_[b] = (uint32_t)(b * kFlowPlanBlock);
-        if (split_tick) memcpy(bases_host_[slot], split_bases_.data(), split_bases_.size() * sizeof(uint32_t));      // both lists' bases, one behind the other
-        else memcpy(bases_host_[slot], live_bases_.data(), live_bases_.size() * sizeof(uint32_t));
-    }
+    const int slot = AcquireArgSlot(plan.need_slot, &slot_ok);
+    if (!slot_ok) return Fail();
+    const int32_t first_rc = TickCodes(ms_per_session, ms, flags_per_session, S, codes);
+    if (ms_per_session) memcpy(ms_host_[slot], ms_per_session, (size_t)S * sizeof(int16_t));      // pinned + mapped
+    if (flags_per_session) memcpy(flags_host_[slot], flags_per_session, (size_t)S);
+    if (plan.route.sparse_tick) memcpy(bases_host_[slot], tick_.Bases(plan).data(), tick_.Bases(plan).size() * sizeof(uint32_t));
     // without far rows (nobody buffers a far frame in this tick) the kernel's far row pointer is never used for a sample that
     // counts; it still has to be an address: the near rows
     if (far == nullptr) far = near;
@@ -446,58 +392,63 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         if (!copy_rows(f, (size_t)span * 2, far, (size_t)stride * 2, hipMemcpyHostToDevice) ||
             !copy_rows(d, (size_t)span * 2, near, (size_t)stride * 2, hipMemcpyHostToDevice) ||
             (clean && !copy_rows(c, (size_t)span * 2, clean, (size_t)stride * 2, hipMemcpyHostToDevice)))
-            return fail();
+            return Fail();
         dfar = f;
         dnear = d;
         dout = io_dev_ + 2 * plane;
         if (clean) dclean = c;
         // whole planes travel back: the rows of sessions that sit out, which no kernel writes, as zeros
         // (and the second halves of the rows of sessions that make a half call)
-        if ((live < S || half_calls) && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * span * 2, st))) return fail();
+        if (plan.zero_out && !AECM_HIP_OK(hipMemsetAsync(dout, 0, (size_t)S * span * 2, st))) return Fail();
     }
-    TickIo tio{dfar, dnear, dclean, dout, dstride, n, far_ring_, near_ring_, clean_ring_, out_ring_, kRing, near_pos_};
+    TickIo tio{dfar, dnear, dclean, dout, dstride, n, far_ring_, near_ring_, clean_ring_, out_ring_, kRing, tick_.near_pos};
     TickFlowIo fio{flow_state_, flow_plans_, far_frames_, far_old_, ms_per_session ? ms_dev_[slot] : nullptr,
-                   flags_per_session ? flags_dev_[slot] : nullptr, ms, flags & (kNoFarend | kSplitCalls), fs_};      // (fs: the object's; mixed planning goes by the session's)
-    if (wait_event && !AECM_HIP_OK(hipStreamWaitEvent(st, static_cast<hipEvent_t>(wait_event), 0))) {
-        (void)hipGetLastError();
-        return AECM_BAD_PARAMETER_ERROR;      // nothing of this tick has been enqueued (device pointers: no staging copies): no poison
-    }
-    bool ok;
-    bool mixed_plan;
-    // (a K-call tick: no half calls, no other rates -- FlowRouteTick itself, told the whole tick's samples and that the tick goes by the
-    // live list; a packet tick: half calls leave their sessions calls * 80 behind, the object out of step)
-    const FlowTickRoute route = FlowRouteTickMixed(lag_, live, S, span, force_sparse_ || k_calls || split_tick, half_calls, other_rates_ > 0, &mixed_plan);
-    clean_history_.Commit(flags_per_session, had_clean, clean_tick);
-    if (split_tick) {
-        const TickSparseIo sp{near_ring_, clean_ring_, kRing, split_live_dev_, bases_dev_[slot], route.deferred_lag};
-        const TickSplitIo split{bases_dev_[slot] + live_bases_.size(), clean_count, plain_count, FlowPlainListStart((uint32_t)clean_count)};
-        ok = AECM_HIP_OK(LaunchTickSplit(engine_->state_ptrs(), tio, fio, sp, split, S, mixed_plan, SplitTickTwoLaunches(live), st));
-    } else if (k_calls) {
-        fio.plans = calls_plans_;
-        const TickSparseIo sp{near_ring_, clean_ring_, kRing, live_dev_, bases_dev_[slot], route.deferred_lag};
-        // (mixed_plan with K calls: a packet tick in which somebody makes half calls or runs at another rate -- the packed layout and
-        // its kernels; a packet tick of a uniform object without half calls IS the K-call tick)
-        if (mixed_plan) {
-            fio.flags = flags & kNoFarend;
-            ok = AECM_HIP_OK(LaunchTickPackets(engine_->state_ptrs(), tio, fio, sp, S, live, calls, st));
-        } else {
-            ok = AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, live, calls, st));
-        }
-    } else if (!route.sparse_plan) {
+                   flags_per_session ? flags_dev_[slot] : nullptr, ms, flags & (kNoFarend | kSplitCalls), tick_.fs};      // (fs: the object's; mixed planning goes by the session's)
+    // nothing of this tick has been enqueued (device pointers: no staging copies): a refused event leaves no poison
+    if (!WaitForCallerEvent(wait_event)) return AECM_BAD_PARAMETER_ERROR;
+    // ---- commit: the tick is certain to be enqueued.  Behind the accepted wait, before the first launch: the position has moved
+    // even when a launch fails (the object is then poisoned).
+    tick_.Commit(plan);
+    // ---- launch
+    const FlowTickRoute &route = plan.route;
+    const TickSparseIo sp{near_ring_, clean_ring_, kRing, live_dev_, bases_dev_[slot], route.deferred_lag};
+    bool ok = false;
+    switch (plan.family) {
+    case kTickFamily_dense:
         ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
-    } else {
-        const TickSparseIo sp{near_ring_, clean_ring_, kRing, route.sparse_tick ? live_dev_ : nullptr, route.sparse_tick ? bases_dev_[slot] : nullptr,
-                              route.deferred_lag};
-        ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, sp, S, live, st, mixed_plan));
+        break;
+    case kTickFamily_sparse:
+    case kTickFamily_mixed: {
+        // (a sparse plan for a tick everybody makes -- the lags are brought up to date --: the dense tick kernel, no live list)
+        const TickSparseIo dense_tick{near_ring_, clean_ring_, kRing, nullptr, nullptr, route.deferred_lag};
+        ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, route.sparse_tick ? sp : dense_tick, S, plan.live, st, plan.mixed_plan));
+        break;
     }
-    near_pos_ += span;
-    if (!ok) return fail();
-    if (ms_per_session || flags_per_session || sparse_tick) {            // both launches of the tick are behind this event; only the first reads the slot
-        if (!AECM_HIP_OK(hipEventRecord(slot_read_[slot], st))) return fail();
+    case kTickFamily_calls:
+        fio.plans = calls_plans_;
+        ok = AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, plan.live, calls, st));
+        break;
+    case kTickFamily_packets:      // the packed layout and its kernels
+        fio.plans = calls_plans_;
+        fio.flags = flags & kNoFarend;
+        ok = AECM_HIP_OK(LaunchTickPackets(engine_->state_ptrs(), tio, fio, sp, S, plan.live, calls, st));
+        break;
+    case kTickFamily_split: {
+        TickSparseIo lists = sp;
+        lists.live = split_live_dev_;
+        const TickSplitIo split{bases_dev_[slot] + tick_.live_bases.size(), plan.clean_count, plan.plain_count, FlowPlainListStart((uint32_t)plan.clean_count)};
+        ok = AECM_HIP_OK(LaunchTickSplit(engine_->state_ptrs(), tio, fio, lists, split, S, plan.mixed_plan, SplitTickTwoLaunches(plan.live), st));
+        break;
+    }
+    default: break;      // (kTickFamily_nothing has returned above)
+    }
+    if (!ok) return Fail();
+    if (plan.need_slot) {            // both launches of the tick are behind this event; only the first reads the slot
+        if (!AECM_HIP_OK(hipEventRecord(slot_read_[slot], st))) return Fail();
         slot_busy_[slot] = true;
     }
-    if (host_pointers && !copy_rows(out, (size_t)stride * 2, dout, (size_t)span * 2, hipMemcpyDeviceToHost)) return fail();
-    if (done_event && !AECM_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(done_event), st))) return fail();
+    if (host_pointers && !copy_rows(out, (size_t)stride * 2, dout, (size_t)span * 2, hipMemcpyDeviceToHost)) return Fail();
+    if (done_event && !AECM_HIP_OK(hipEventRecord(static_cast<hipEvent_t>(done_event), st))) return Fail();
     return first_rc;
 }
 
@@ -531,7 +482,7 @@ int32_t SessionBatch::ExportSession(int session, void *buf) {
     const int S = engine_->num_streams();
     const SessionOffsets at;
     uint8_t *p = static_cast<uint8_t *>(buf);
-    const SessionSnapshotHeader h{kSessionMagic, kSessionVersion, (uint32_t)rates_[(size_t)session], clean_ring_ ? 1u : 0u, (uint32_t)kFlowWords, (uint32_t)kRing,
+    const SessionSnapshotHeader h{kSessionMagic, kSessionVersion, (uint32_t)tick_.rates[(size_t)session], clean_ring_ ? 1u : 0u, (uint32_t)kFlowWords, (uint32_t)kRing,
                                   (uint32_t)kOutTail, (uint32_t)kNearTail};
     memcpy(p, &h, sizeof h);
     if (!engine_->ExportState(session, p + at.state)) return Fail();
@@ -547,7 +498,7 @@ int32_t SessionBatch::ExportSession(int session, void *buf) {
                                       hipMemcpyDeviceToHost));
     // The session's own near position: the object's, less what the session has sat out (its lag on the device + the all-idle
     // ticks not yet added to it).  The snapshot itself is in step -- lag 0, as every snapshot before there were idle ticks.
-    const uint32_t own_near_pos = (uint32_t)near_pos_ - (uint32_t)flow[F_NEAR_LAG] - (uint32_t)lag_.deferred_lag;
+    const uint32_t own_near_pos = (uint32_t)tick_.near_pos - (uint32_t)flow[F_NEAR_LAG] - (uint32_t)tick_.lag.deferred_lag;
     flow[F_NEAR_LAG] = 0;
     memcpy(p + at.flow, flow, sizeof flow);
     ok = ok && AECM_HIP_OK(hipMemcpy(p + at.far, far_ring_ + (size_t)session * kRing, kRing * 2, hipMemcpyDeviceToHost)) &&
@@ -567,7 +518,7 @@ int32_t SessionBatch::ImportSession(int session, const void *buf, bool any_rate)
     const uint8_t *p = static_cast<const uint8_t *>(buf);
     SessionSnapshotHeader h;
     memcpy(&h, p, sizeof h);
-    if (h.magic != kSessionMagic || h.version != kSessionVersion || (any_rate ? h.fs != 8000u && h.fs != 16000u : h.fs != (uint32_t)fs_) || h.has_clean > 1u || h.flow_words != (uint32_t)kFlowWords ||
+    if (h.magic != kSessionMagic || h.version != kSessionVersion || (any_rate ? h.fs != 8000u && h.fs != 16000u : h.fs != (uint32_t)tick_.fs) || h.has_clean > 1u || h.flow_words != (uint32_t)kFlowWords ||
         h.far_ring != (uint32_t)kRing || h.out_tail != (uint32_t)kOutTail || h.near_tail != (uint32_t)kNearTail)
         return AECM_BAD_PARAMETER_ERROR;
     int32_t flow[kFlowWords];
@@ -586,23 +537,15 @@ int32_t SessionBatch::ImportSession(int session, const void *buf, bool any_rate)
     if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
     const int S = engine_->num_streams();
     hipStream_t st = engine_->stream();
-    if (h.has_clean && !clean_ring_) {                      // as the first tick that carries a clean near end would
-        const size_t bytes = (size_t)S * kRing * 2;
-        if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
-        if (!AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, st))) {      // a ring that may hold anything is no ring
-            (void)hipFree(clean_ring_);
-            clean_ring_ = nullptr;
-            return Fail();
-        }
-    }
+    if (h.has_clean)                                        // as the first tick that carries a clean near end would
+        if (const int32_t rc = EnsureCleanRing()) return rc;
     // (ImportState validates the blob once more and is the first thing that writes)
     if (const int32_t rc = engine_->ImportState(session, p + at.state)) return rc;
-    SetRate(session, (int32_t)h.fs);
-    clean_history_.ResetSession(session);      // the caller continues the session as it was exported
+    tick_.InitSession(session, (int32_t)h.fs);      // (its clean history starts anew: the caller continues the session as it was exported)
     // The session arrives in step with this object: its tail goes behind the object's near position, its lag is 0 -- behind
     // the position the device takes for the object's while all-idle ticks are still to be added to the lags, that is.
     flow[F_NEAR_LAG] = 0;
-    const uint32_t own_near_pos = (uint32_t)near_pos_ - (uint32_t)lag_.deferred_lag;
+    const uint32_t own_near_pos = (uint32_t)tick_.near_pos - (uint32_t)tick_.lag.deferred_lag;
     std::vector<int16_t> row(kRing, 0);
     auto place_tail = [&](int16_t *ring_row, uint32_t end_pos, int n, const uint8_t *src, bool zero_rest) -> bool {
         if (!zero_rest && !AECM_HIP_OK(hipMemcpy(row.data(), ring_row, kRing * 2, hipMemcpyDeviceToHost))) return false;
@@ -626,7 +569,7 @@ int32_t SessionBatch::ImportSession(int session, const void *buf, bool any_rate)
 // ---- bulk session snapshots: a list of sessions, one or two launches, no per-session host work ---------------
 SessionView SessionBatch::View() const {
     return SessionView{engine_->state_ptrs(), flow_state_, (int64_t)engine_->num_streams(), far_ring_, near_ring_, clean_ring_, out_ring_,
-                       far_frames_, far_old_, (uint32_t)near_pos_, lag_.deferred_lag};
+                       far_frames_, far_old_, (uint32_t)tick_.near_pos, tick_.lag.deferred_lag};
 }
 
 // In range and distinct, or nothing is touched.
@@ -642,32 +585,22 @@ int32_t SessionBatch::CheckSessionList(const int32_t *sessions, int count) const
     return 0;
 }
 
-bool SessionBatch::EnsureSnapshotBuffers(int list_entries, int stage_sessions, int info_words) {
-    const auto grow = [&](void **buf, size_t *have, size_t need, size_t unit) {
-        if (need <= *have) return true;
-        if (!AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return false;      // (nothing enqueued may still use the old one)
-        (void)hipFree(*buf);
-        *buf = nullptr;
-        *have = 0;
-        if (!AECM_HIP_OK(hipMalloc(buf, need * unit))) { *buf = nullptr; return false; }
-        *have = need;
-        return true;
-    };
-    return grow((void **)&snap_list_, &snap_list_entries_, (size_t)list_entries, sizeof(int32_t)) &&
-           grow((void **)&snap_stage_, &snap_stage_bytes_, (size_t)std::min(stage_sessions, kSnapshotStageSessions) * kSessionBytes, 1) &&
-           grow((void **)&snap_verdict_, &snap_verdict_words_, info_words > 0 ? (size_t)info_words + 1 : 0, sizeof(uint32_t));
+int32_t SessionBatch::EnsureSnapshotBuffers(int list_entries, int stage_sessions, int info_words) {
+    if (const int32_t rc = Grow((void **)&snap_list_, &snap_list_entries_, (size_t)list_entries, sizeof(int32_t))) return rc;
+    if (const int32_t rc = Grow((void **)&snap_stage_, &snap_stage_bytes_, (size_t)std::min(stage_sessions, kSnapshotStageSessions) * kSessionBytes, 1)) return rc;
+    return Grow((void **)&snap_verdict_, &snap_verdict_words_, info_words > 0 ? (size_t)info_words + 1 : 0, sizeof(uint32_t));
 }
 
 int32_t SessionBatch::ExportSessions(const int32_t *sessions, int count, void *snapshots, bool device) {
     if (count < 0) return AECM_BAD_PARAMETER_ERROR;
     if (count == 0) return 0;
     if (snapshots == nullptr) return AECM_NULL_POINTER_ERROR;
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
     if (int32_t rc = CheckSessionList(sessions, count)) return rc;
     if (device && (reinterpret_cast<uintptr_t>(snapshots) & 3)) return AECM_BAD_PARAMETER_ERROR;      // the kernels move 32-bit words at least
     if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
-    if (!EnsureSnapshotBuffers(sessions ? count : 0, device ? 0 : count, 0)) return AECM_UNSPECIFIED_ERROR;
+    if (const int32_t rc = EnsureSnapshotBuffers(sessions ? count : 0, device ? 0 : count, 0)) return rc;
     hipStream_t st = engine_->stream();
     if (sessions && !AECM_HIP_OK(hipMemcpyAsync(snap_list_, sessions, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st))) return Fail();
     const SessionView view = View();
@@ -690,12 +623,12 @@ int32_t SessionBatch::ImportSessions(const int32_t *sessions, int count, const v
     if (count < 0) return AECM_BAD_PARAMETER_ERROR;
     if (count == 0) return 0;
     if (snapshots == nullptr) return AECM_NULL_POINTER_ERROR;
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
     if (int32_t rc = CheckSessionList(sessions, count)) return rc;
     if (device && (reinterpret_cast<uintptr_t>(snapshots) & 3)) return AECM_BAD_PARAMETER_ERROR;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return AECM_UNSPECIFIED_ERROR;
-    if (!EnsureSnapshotBuffers(sessions ? count : 0, device ? 0 : count, device ? count : 0)) return AECM_UNSPECIFIED_ERROR;
+    if (const int32_t rc = EnsureSnapshotBuffers(sessions ? count : 0, device ? 0 : count, device ? count : 0)) return rc;
     hipStream_t st = engine_->stream();
     const bool wide = (reinterpret_cast<uintptr_t>(snapshots) & 15) == 0;
     const uint8_t *src = static_cast<const uint8_t *>(snapshots);
@@ -704,7 +637,7 @@ int32_t SessionBatch::ImportSessions(const int32_t *sessions, int count, const v
     if (device) {
         static const uint32_t preset = 0xffffffffu;           // the verdict word; the info words follow it
         if (!AECM_HIP_OK(hipMemcpyAsync(snap_verdict_, &preset, sizeof preset, hipMemcpyHostToDevice, st)) ||
-            !AECM_HIP_OK(LaunchValidateSessions(snapshots, count, fs_, any_rate, snap_verdict_, snap_verdict_ + 1, st)) ||
+            !AECM_HIP_OK(LaunchValidateSessions(snapshots, count, tick_.fs, any_rate, snap_verdict_, snap_verdict_ + 1, st)) ||
             !AECM_HIP_OK(hipMemcpyAsync(info.data(), snap_verdict_, ((size_t)count + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st)) ||
             !AECM_HIP_OK(hipStreamSynchronize(st))) {
             (void)hipStreamSynchronize(st);                   // (the read-back into `info` may still be in flight)
@@ -715,25 +648,17 @@ int32_t SessionBatch::ImportSessions(const int32_t *sessions, int count, const v
         for (int i = 0; i < count; ++i) {
             const uint8_t *blob = src + (size_t)i * kSessionBytes;
             for (int t = 0; t < kLanes; ++t)
-                if (SessionBlobDefect(blob, fs_, any_rate, t) != 0) return AECM_BAD_PARAMETER_ERROR;
+                if (SessionBlobDefect(blob, tick_.fs, any_rate, t) != 0) return AECM_BAD_PARAMETER_ERROR;
             info[(size_t)i + 1] = SessionBlobWord(blob, 0, 2) | (SessionBlobWord(blob, 0, 3) << 31);
         }
     }
-    const int S = engine_->num_streams();
     bool has_clean = false, other_rate = false;
     for (int i = 0; i < count; ++i) {
         has_clean = has_clean || (info[(size_t)i + 1] >> 31) != 0;
-        other_rate = other_rate || (int32_t)(info[(size_t)i + 1] & 0x7fffffffu) != fs_;
+        other_rate = other_rate || (int32_t)(info[(size_t)i + 1] & 0x7fffffffu) != tick_.fs;
     }
-    if (has_clean && !clean_ring_) {                        // as the first tick that carries a clean near end would
-        const size_t bytes = (size_t)S * kRing * 2;
-        if (!AECM_HIP_OK(hipMalloc((void **)&clean_ring_, bytes))) { clean_ring_ = nullptr; return AECM_UNSPECIFIED_ERROR; }
-        if (!AECM_HIP_OK(hipMemsetAsync(clean_ring_, 0, bytes, st))) {
-            (void)hipFree(clean_ring_);
-            clean_ring_ = nullptr;
-            return Fail();
-        }
-    }
+    if (has_clean)                                          // as the first tick that carries a clean near end would
+        if (const int32_t rc = EnsureCleanRing()) return rc;
     if (sessions && !AECM_HIP_OK(hipMemcpyAsync(snap_list_, sessions, (size_t)count * sizeof(int32_t), hipMemcpyHostToDevice, st))) return Fail();
     const SessionView view = View();
     bool ok = true;
@@ -747,16 +672,13 @@ int32_t SessionBatch::ImportSessions(const int32_t *sessions, int count, const v
         }
     }
     if (!ok || !AECM_HIP_OK(hipStreamSynchronize(st))) return Fail();      // sessions half written are no sessions: the object is poisoned
-    for (int i = 0; i < count; ++i) {
-        SetRate(sessions ? sessions[i] : i, (int32_t)(info[(size_t)i + 1] & 0x7fffffffu));
-        clean_history_.ResetSession(sessions ? sessions[i] : i);
-    }
+    for (int i = 0; i < count; ++i) tick_.InitSession(sessions ? sessions[i] : i, (int32_t)(info[(size_t)i + 1] & 0x7fffffffu));
     if (other_rate) engine_->NoteStreamOfOtherRate();
     return 0;
 }
 
 int32_t SessionBatch::Synchronize() {
-    if (fs_ == 0) return AECM_UNINITIALIZED_ERROR;
+    if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
     if (!AECM_HIP_OK(hipSetDevice(device_)) || !AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return Fail();
     return 0;

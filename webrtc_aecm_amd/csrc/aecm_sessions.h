@@ -15,8 +15,8 @@
 #include <vector>
 
 #include "aecm_engine.h"
-#include "aecm_flow_clean.h"
 #include "aecm_kernels.h"
+#include "aecm_tick_plan.h"
 
 namespace aecm {
 
@@ -33,7 +33,7 @@ public:
     // Sessions of both rates in one object.  samp_freq stays the OBJECT's rate (what InitSession and ImportSession mean by "the
     // same rate"); every session runs at its own: on the device that is its core state's S_MULT (what the block engine, the
     // mixed planning kernel and the burst kernel read), the host keeps a mirror for argument checks, snapshot headers and the
-    // launch routing (FlowRouteTickMixed: an object that holds a session of another rate plans every tick per session).
+    // launch routing (aecm_tick_plan.h: TickObject::Plan -- an object that holds a session of another rate plans every tick per session).
     int32_t InitRates(int32_t samp_freq, const int32_t *rates);          // Init, then WebRtcAecm_Init(inst_k, rates[k]) where rates[k] differs: one launch
     int32_t InitSessionRate(int session, int32_t samp_freq);             // InitSession at that rate
     int32_t GetSessionRate(int session, int32_t *samp_freq) const;
@@ -105,7 +105,7 @@ public:
     //     session's kind is refused (bad parameter) and changes nothing, and so is every later tick or Process of an object that has
     //     accepted a tick with the bit, an object that never uses it is never refused for it.  Nobody flagged among the callers: the
     //     tick without the bit, by its launches; everybody: the launches of the tick without `clean`; else aecm_tick_split_kernels.hip,
-    //     always by the live lists.  Ignored without `clean` and in an idle session's byte; with calls > 1: unsupported function.
+    //     always by the live lists (which of them: aecm_tick_plan.h, TickPlan::family).  Ignored without `clean` and in an idle session's byte; with calls > 1: unsupported function.
     static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle, kHalfCall = kFlowHalfCall, kNoClean = kFlowNoClean;
     // 0 no Process call since the session's last initialisation, 1 every one carried a clean input, 2 none did, 3 both
     int32_t GetSessionCleanMode(int session, int32_t *mode) const;
@@ -114,7 +114,7 @@ public:
     void SplitCleanTwoLaunches(int mode) { split_two_launches_ = mode < 0 ? -1 : mode > 0 ? 1 : 0; }
     // Diagnostics (tools/bench_sessions.py): every tick through the live list and the sparse tick kernel, idle sessions or
     // not -- what the indirection itself costs.
-    void ForceSparseTicks(bool on) { force_sparse_ = on; }
+    void ForceSparseTicks(bool on) { tick_.force_sparse = on; }
 
     // Snapshot of ONE live session (checkpoint; migration into another object, on another GPU): everything the reference
     // keeps per instance -- AecMobile's wrapper members and jitter buffer (echo_control_mobile.cc:42-79), the core's frame
@@ -156,25 +156,17 @@ private:
     bool ResetFlowRows(int first, int count);
     static constexpr int64_t kRing = kFlowFarRing;   // >= 4000 (jitter buffer) + a tick + the window a replayed frame may age in
     std::unique_ptr<BatchEngine> engine_;
-    int fs_ = 0;                               // 0: not initialised
-    std::vector<int32_t> rates_;               // [S] every session's own rate (mirror of the core states' S_MULT)
-    int other_rates_ = 0;                      // sessions whose rate is not fs_
-    void SetRate(int session, int32_t fs);
-    FlowCleanHistory clean_history_;           // [S] next to rates_: what every session's Process calls carried (kNoClean)
+    // What the host keeps per object and decides a tick by -- the rates (mirror of the core states' S_MULT; fs == 0: not initialised),
+    // the near position, the lags, the clean history -- and the planner of a tick: aecm_tick_plan.h.  Only TickObject's own
+    // methods write it.
+    TickObject tick_;
     int split_two_launches_ = -1;
     bool SplitTickTwoLaunches(int calling) const;
     uint32_t *split_live_dev_ = nullptr;       // [FlowSplitListEntries(S)] the two lists of a split tick; allocated by the first one
     // A tick that failed on the device leaves the rings and the wrapper state out of step: every later call is refused
     // (AECM_UNSPECIFIED_ERROR) until Init.
     bool poisoned_ = false;
-    int64_t near_pos_ = 0;                     // near-end samples ticked so far = ring position of the next tick's first one
-    // Sessions that sat out ticks lag behind near_pos_ (aecm_flow_plan.h: F_NEAR_LAG) until their next call; what the object
-    // itself keeps about that, and which launches a tick takes by it: FlowObjectLag / FlowRouteTick.
-    FlowObjectLag lag_;
-    bool force_sparse_ = false;
     uint32_t *live_dev_ = nullptr;             // [S] the tick's live sessions, ascending (written by the planning launch)
-    std::vector<uint32_t> live_bases_;         // [ceil(S / kFlowPlanBlock)] FlowLiveBlockBases of the tick's flags
-    std::vector<uint32_t> split_bases_;        // [2][ceil(S / kFlowPlanBlock)] FlowScanFlagsClean of a split tick's flags
     int16_t *far_ring_ = nullptr, *near_ring_ = nullptr, *out_ring_ = nullptr;   // [S][kRing]
     int16_t *clean_ring_ = nullptr;            // [S][kRing], allocated by the first tick that carries a clean near-end
     int16_t *io_dev_ = nullptr;                // [4][S][io_row_] staging when the caller passes host pointers
@@ -198,11 +190,15 @@ private:
                     int16_t ms, const int16_t *ms_per_session, const uint8_t *flags_per_session, int32_t *codes, bool host_pointers,
                     void *wait_event, void *done_event, int flags, int32_t calls = 1, bool packets = false);
     bool EventUsable(void *ev) const;
+    bool WaitForCallerEvent(void *wait_event);
+    int32_t Grow(void **buf, size_t *have, size_t need, size_t unit);
+    int32_t GrowOnce(void **buf, size_t bytes);
+    int32_t EnsureCleanRing();
     int AcquireArgSlot(bool needed, bool *ok);
     int32_t Fail();
     // bulk snapshots: the list on the device, the host forms' stage, the validation verdict (word 0) + info words; all grow-only
     int32_t CheckSessionList(const int32_t *sessions, int count) const;
-    bool EnsureSnapshotBuffers(int list_entries, int stage_sessions, int info_words);
+    int32_t EnsureSnapshotBuffers(int list_entries, int stage_sessions, int info_words);
     SessionView View() const;
     int32_t *snap_list_ = nullptr;
     size_t snap_list_entries_ = 0;
