@@ -2211,44 +2211,100 @@ def test_session_migrates_mid_call_between_session_batches(fs, frame, with_clean
     sb.close()
 
 
-@pytest.mark.parametrize("clean_opt_in", [False, True])
-@pytest.mark.parametrize("S,T,pad", [(8, 4, 0), (8, 48, 64), (2 * 8192, 3, 0)])
-def test_host_entry_points_launch_what_the_device_entry_point_launches(S, T, pad, clean_opt_in):
-    """The three host paths of WebRtcAecmBatch_ProcessBlocksHost each make the launch plan of their own launches: the mapped path
-    (the buffers fit 64 KB), the staged path (above it; here with a stream stride that is not dense) and the chunked host pipeline
-    (dense, from 2 x 8 192 streams).  From a fresh Init each must write the bytes and leave the states WebRtcAecmBatch_ProcessBlocks
-    does on device pointers -- without a clean input, and with one on a batch that has opted in to pipelining such launches."""
+OUT_SENTINEL = 0x5a5a
+
+
+def strided_planes(S, T, layout):
+    """(stream_stride, block_stride, pos) of a caller's plane: pos[s, b * 64 + i] is where sample i of block b of stream s lives, the
+    plane ends with the last of them.  layout: a number of pad samples behind each stream's T x 64 (0: dense); "tick-major"
+    ([T][S][64]: strides 64, S x 64); "padded-blocks" (32 samples behind every block and 16 more behind every stream)."""
+    if layout == "tick-major":
+        stream_stride, block_stride = 64, S * 64
+    elif layout == "padded-blocks":
+        stream_stride, block_stride = T * 96 + 16, 96
+    else:
+        stream_stride, block_stride = T * 64 + layout, 64
+    pos = np.arange(S)[:, None, None] * stream_stride + np.arange(T)[None, :, None] * block_stride + np.arange(64)[None, None, :]
+    return stream_stride, block_stride, pos.reshape(S, T * 64)
+
+
+def host_and_device_twins(S, T, layout, fs, with_clean, run_host, run_device, live_blocks=None):
+    """The same audio in the same strided layout through a host entry point (run_host(batch, far, near, clean, out, strides): numpy
+    planes) and through its device twin (run_device(...): device pointers) on two fresh batches.  Every byte of the two out planes
+    must be equal; the blocks that ran (live_blocks[s] of stream s; None: all T) hold output and every other sample of the host's
+    out plane -- pads, blocks at or beyond a stream's length -- still holds the caller's sentinel.  Returns the two batches."""
     import torch
-    fs, K = 16000, 8
+    K = 8
     far_u, near_u = synth_streams(list(range(900, 900 + K)), max(T, 16), fs)      # (the synthesiser's echo taps need some 10 blocks)
     idx = np.arange(S) % K
-    stride = T * 64 + pad
+    stream_stride, block_stride, pos = strided_planes(S, T, layout)
+    extent = int(pos.max()) + 1
 
-    def rows(a):
-        full = np.zeros((S, stride), dtype=np.int16)
-        full[:, :T * 64] = a[idx, :T * 64]
+    def plane(a):
+        full = np.zeros(extent, dtype=np.int16)
+        full[pos] = a[idx, :T * 64]
         return full
-    far, near = rows(far_u), rows(near_u)
-    clean = rows(synth_clean(near_u)) if clean_opt_in else None
-    batches = []
-    for _ in range(2):
-        b = aecm.AecmBatch(S, fs)
-        if clean_opt_in:
-            b.set_clean_pipelining(True)
-        batches.append(b)
-    host, dev = batches
-    out_host = np.zeros_like(near)
-    assert host.lib.WebRtcAecmBatch_ProcessBlocksHost(host.h, far.ctypes.data, near.ctypes.data, None if clean is None else clean.ctypes.data,
-                                                      out_host.ctypes.data, stride, 64, T) == 0
+    far, near = plane(far_u), plane(near_u)
+    clean = plane(synth_clean(near_u)) if with_clean else None
+    out_host = np.full(extent, OUT_SENTINEL, dtype=np.int16)
+    host, dev = aecm.AecmBatch(S, fs), aecm.AecmBatch(S, fs)
+    run_host(host, far, near, clean, out_host, stream_stride, block_stride)
     dfar, dnear = torch.from_numpy(far).cuda(), torch.from_numpy(near).cuda()
     dclean = None if clean is None else torch.from_numpy(clean).cuda()
-    dout = torch.zeros_like(dnear)
+    dout = torch.full_like(dnear, OUT_SENTINEL)
     torch.cuda.synchronize()
-    dev.process_device(dfar.data_ptr(), dnear.data_ptr(), dout.data_ptr(), stride, 64, T, None if dclean is None else dclean.data_ptr())
+    run_device(dev, dfar.data_ptr(), dnear.data_ptr(), None if dclean is None else dclean.data_ptr(), dout.data_ptr(), stream_stride, block_stride)
     dev.synchronize()
     assert np.array_equal(out_host, dout.cpu().numpy())
-    assert out_host[:, :T * 64].any()
-    for s in sorted(set(range(min(S, K))) | {S // 2 - 1, S // 2, S - 1}):
+    written = np.zeros(extent, dtype=bool)
+    lens = np.full(S, T) if live_blocks is None else np.asarray(live_blocks)
+    written[pos[np.arange(T * 64)[None, :] < lens[:, None] * 64]] = True
+    assert (out_host[~written] == OUT_SENTINEL).all()
+    assert out_host[written].any() and (out_host[written] != OUT_SENTINEL).any()
+    return host, dev
+
+
+@pytest.mark.parametrize("clean_opt_in", [False, True])
+@pytest.mark.parametrize("S,T,layout", [(8, 4, 0), (8, 48, 64), (2 * 8192, 3, 0), (2, 3, "tick-major"), (2, 3, "padded-blocks"),
+                                        (8, 48, "tick-major"), (8, 48, "padded-blocks")])
+def test_host_entry_points_launch_what_the_device_entry_point_launches(S, T, layout, clean_opt_in):
+    """The three host paths of WebRtcAecmBatch_ProcessBlocksHost each make the launch plan of their own launches: the mapped path
+    (the buffers fit 64 KB: 8 x 4 dense, 2 x 3 tick-major and with padded blocks), the staged path (above it: 8 x 48 with a padded
+    stream stride, tick-major and with padded blocks) and the chunked host pipeline (dense, from 2 x 8 192 streams).  From a fresh
+    Init each must write the bytes and leave the states WebRtcAecmBatch_ProcessBlocks does on device pointers of the same layout --
+    without a clean input, and with one on a batch that has opted in to pipelining such launches -- and nothing but the blocks."""
+    def run_host(b, far, near, clean, out, stream_stride, block_stride):
+        b.set_clean_pipelining(clean_opt_in)
+        assert b.lib.WebRtcAecmBatch_ProcessBlocksHost(b.h, far.ctypes.data, near.ctypes.data, None if clean is None else clean.ctypes.data,
+                                                       out.ctypes.data, stream_stride, block_stride, T) == 0
+
+    def run_device(b, far, near, clean, out, stream_stride, block_stride):
+        b.set_clean_pipelining(clean_opt_in)
+        b.process_device(far, near, out, stream_stride, block_stride, T, clean)
+    host, dev = host_and_device_twins(S, T, layout, 16000, clean_opt_in, run_host, run_device)
+    for s in sorted(set(range(min(S, 8))) | {S // 2 - 1, S // 2, S - 1}):
+        assert np.array_equal(host.digest(s), dev.digest(s)), s
+    host.close()
+    dev.close()
+
+
+@pytest.mark.parametrize("with_clean", [False, True])
+@pytest.mark.parametrize("layout", ["padded-blocks", "tick-major"])
+def test_ragged_host_entry_point_launches_what_the_device_entry_point_launches(layout, with_clean):
+    """WebRtcAecmBatch_ProcessBlocksRaggedHost (always the staged path) against WebRtcAecmBatch_ProcessBlocksRagged on device
+    pointers of the same strided layout, lengths from 0 to T: the same out bytes, the same states, and the blocks at or beyond a
+    stream's length -- like every pad sample -- still hold the caller's sentinel."""
+    S, T = 8, 5
+    lens = np.array([5, 0, 3, 5, 1, 0, 2, 4], dtype=np.int32)
+
+    def run_host(b, far, near, clean, out, stream_stride, block_stride):
+        assert b.lib.WebRtcAecmBatch_ProcessBlocksRaggedHost(b.h, far.ctypes.data, near.ctypes.data, None if clean is None else clean.ctypes.data,
+                                                             out.ctypes.data, stream_stride, block_stride, T, lens.ctypes.data) == 0
+
+    def run_device(b, far, near, clean, out, stream_stride, block_stride):
+        b.process_ragged_device(far, near, out, stream_stride, block_stride, T, lens, clean)
+    host, dev = host_and_device_twins(S, T, layout, 16000, with_clean, run_host, run_device, live_blocks=lens)
+    for s in range(S):
         assert np.array_equal(host.digest(s), dev.digest(s)), s
     host.close()
     dev.close()

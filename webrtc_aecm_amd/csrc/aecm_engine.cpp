@@ -1,5 +1,6 @@
 #include "aecm_engine.h"
 
+#include "aecm_host_rows.h"
 #include "aecm_session_flow.h"
 #include "aecm_state_check.h"
 
@@ -16,6 +17,17 @@
 namespace aecm {
 
 #define AECM_HIP_OK(expr) ((expr) == hipSuccess)
+
+bool GrowDeviceBuffer(void **buf, size_t *have, size_t need, size_t unit, hipStream_t stream) {
+    if (need <= *have) return true;
+    if (*buf && !AECM_HIP_OK(hipStreamSynchronize(stream))) return false;      // (nothing enqueued may still use the old one)
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *have = 0;
+    if (!AECM_HIP_OK(hipMalloc(buf, need * unit))) { *buf = nullptr; return false; }
+    *have = need;
+    return true;
+}
 
 // (kDefaultQueueChunk: launches of more streams than the chip holds waves are cut into chunks of that many blocks and scheduled from
 // a queue -- aecm_block_kernels.hip: aecm_process_queue_kernel; measured: profiles/r04_experiments.md section 1.)
@@ -668,44 +680,32 @@ int32_t BatchEngine::ProcessBlocksRaggedRange(const IoView &io, int num_blocks, 
     return TimedLaunch(io, first, plan) ? 0 : kErrUnspecified;
 }
 
-// Host audio: the live blocks are packed into dense device rows, run, and the blocks that were written are copied back.
+// Host audio: the live blocks are packed into dense device rows (zeros behind a stream's length), run, and the blocks that
+// were written are copied back.
 int32_t BatchEngine::ProcessBlocksRaggedHost(const IoView &io, int num_blocks, const int32_t *lens) {
     if (num_blocks < 0 || !lens) return kErrBadParameter;
     for (int s = 0; s < num_streams_; ++s)
         if (lens[s] < 0 || lens[s] > num_blocks) return kErrBadParameter;
     if (num_blocks == 0) return 0;
     if (!AECM_HIP_OK(hipSetDevice(device_))) return kErrUnspecified;
-    const size_t row = (size_t)num_blocks * kBlock, per = (size_t)num_streams_ * row;
-    const int n_in = io.near_clean ? 3 : 2;
-    const size_t need = per * (n_in + 1);
-    if (need > stage_elems_) {
-        if (!AECM_HIP_OK(hipStreamSynchronize(stream_))) return kErrUnspecified;
-        (void)hipFree(stage_dev_);
-        stage_dev_ = nullptr;
-        stage_elems_ = 0;
-        if (!AECM_HIP_OK(hipMalloc((void **)&stage_dev_, need * sizeof(int16_t)))) return kErrUnspecified;
-        stage_elems_ = need;
-    }
+    const RowLayout rows{num_streams_, num_blocks, io.stream_stride, io.block_stride};
+    const size_t per = rows.per(), bytes = per * sizeof(int16_t);
+    const bool has_clean = io.near_clean != nullptr;
+    if (!GrowDeviceBuffer((void **)&stage_dev_, &stage_elems_, StagedSamples(per, has_clean), sizeof(int16_t), stream_)) return kErrUnspecified;
+    const IoView dev = StagedIo(stage_dev_, rows.row(), per, has_clean);
     std::vector<int16_t> tmp(per, 0);
-    auto upload = [&](const int16_t *src, int16_t *dst) -> bool {
-        for (int s = 0; s < num_streams_; ++s)
-            for (int b = 0; b < lens[s]; ++b)
-                memcpy(&tmp[(size_t)s * row + (size_t)b * kBlock], src + s * io.stream_stride + b * io.block_stride, kBlock * sizeof(int16_t));
-        return AECM_HIP_OK(hipMemcpy(dst, tmp.data(), per * sizeof(int16_t), hipMemcpyHostToDevice));
+    auto upload = [&](const int16_t *src, const int16_t *dst) -> bool {
+        PackRows(rows, src, tmp.data(), lens);
+        return AECM_HIP_OK(hipMemcpy(const_cast<int16_t *>(dst), tmp.data(), bytes, hipMemcpyHostToDevice));
     };
-    IoView dev{stage_dev_, stage_dev_ + per, io.near_clean ? stage_dev_ + 2 * per : nullptr, stage_dev_ + (size_t)n_in * per, (int64_t)row, kBlock};
-    if (!upload(io.far, const_cast<int16_t *>(dev.far)) || !upload(io.near, const_cast<int16_t *>(dev.near)) ||
-        (io.near_clean && !upload(io.near_clean, const_cast<int16_t *>(dev.near_clean))))
-        return kErrUnspecified;
+    if (!upload(io.far, dev.far) || !upload(io.near, dev.near) || (has_clean && !upload(io.near_clean, dev.near_clean))) return kErrUnspecified;
     if (const int32_t rc = ProcessBlocksRagged(dev, num_blocks, lens)) return rc;
-    if (!AECM_HIP_OK(hipMemcpyAsync(tmp.data(), dev.out, per * sizeof(int16_t), hipMemcpyDeviceToHost, stream_))) {
+    if (!AECM_HIP_OK(hipMemcpyAsync(tmp.data(), dev.out, bytes, hipMemcpyDeviceToHost, stream_))) {
         (void)Drain();                                                // tmp goes out of scope
         return kErrUnspecified;
     }
     if (!Drain()) return kErrUnspecified;
-    for (int s = 0; s < num_streams_; ++s)
-        for (int b = 0; b < lens[s]; ++b)
-            memcpy(io.out + s * io.stream_stride + b * io.block_stride, &tmp[(size_t)s * row + (size_t)b * kBlock], kBlock * sizeof(int16_t));
+    UnpackRows(rows, tmp.data(), io.out, lens);
     return 0;
 }
 
@@ -802,25 +802,16 @@ bool BatchEngine::ProcessBlocksHostMapped(const IoView &io, int num_blocks) {
         mapped_host_ = host;
         mapped_dev_ = static_cast<int16_t *>(dev);
     }
-    const size_t row = (size_t)num_blocks * kBlock, per = (size_t)num_streams_ * row;
-    const int n_in = io.near_clean ? 3 : 2;
-    auto rows = [&](const int16_t *src, int16_t *dst, bool to_mapped) {     // src / dst: the caller's side, the mapped side
-        for (int s = 0; s < num_streams_; ++s)
-            for (int b = 0; b < num_blocks; ++b) {
-                const int16_t *user = src + s * io.stream_stride + b * io.block_stride;
-                int16_t *ours = dst + (size_t)s * row + (size_t)b * kBlock;
-                if (to_mapped) memcpy(ours, user, kBlock * sizeof(int16_t));
-                else memcpy(const_cast<int16_t *>(user), ours, kBlock * sizeof(int16_t));
-            }
-    };
-    rows(io.far, mapped_host_, true);
-    rows(io.near, mapped_host_ + per, true);
-    if (io.near_clean) rows(io.near_clean, mapped_host_ + 2 * per, true);
-    IoView dev{mapped_dev_, mapped_dev_ + per, io.near_clean ? mapped_dev_ + 2 * per : nullptr, mapped_dev_ + (size_t)n_in * per,
-               (int64_t)row, kBlock};
-    if (!LaunchBlocks(st_, dev, PlanLaunch(policy_, switches_, num_streams_, num_blocks, io.near_clean != nullptr))) return false;
+    const RowLayout rows{num_streams_, num_blocks, io.stream_stride, io.block_stride};
+    const bool has_clean = io.near_clean != nullptr;
+    const IoView ours = StagedIo(mapped_host_, rows.row(), rows.per(), has_clean);      // the same planes as the host and as the device see them
+    const IoView dev = StagedIo(mapped_dev_, rows.row(), rows.per(), has_clean);
+    PackRows(rows, io.far, const_cast<int16_t *>(ours.far));
+    PackRows(rows, io.near, const_cast<int16_t *>(ours.near));
+    if (has_clean) PackRows(rows, io.near_clean, const_cast<int16_t *>(ours.near_clean));
+    if (!LaunchBlocks(st_, dev, PlanLaunch(policy_, switches_, num_streams_, num_blocks, has_clean))) return false;
     if (!Drain()) return false;
-    rows(io.out, mapped_host_ + (size_t)n_in * per, false);
+    UnpackRows(rows, ours.out, io.out);
     return true;
 }
 
@@ -829,7 +820,7 @@ bool BatchEngine::ProcessBlocksHostMapped(const IoView &io, int num_blocks) {
 // so both directions of the link are busy.
 bool BatchEngine::ProcessBlocksHostPipelined(const IoView &io, int num_blocks) {
     const size_t row = (size_t)num_blocks * kBlock;                       // samples per stream
-    const int n_in = io.near_clean ? 3 : 2;
+    const bool has_clean = io.near_clean != nullptr;
     const size_t per = (size_t)num_streams_ * row;
     if (!download_stream_ && !AECM_HIP_OK(hipStreamCreateWithFlags(&download_stream_, hipStreamNonBlocking))) return false;
     if (!FlushTimers()) return false;
@@ -837,7 +828,7 @@ bool BatchEngine::ProcessBlocksHostPipelined(const IoView &io, int num_blocks) {
     std::vector<hipEvent_t> done(n_chunks, nullptr);
     bool ok = true;
     for (auto &e : done) ok = ok && AECM_HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    int16_t *dfar = stage_dev_, *dnear = stage_dev_ + per, *dclean = stage_dev_ + 2 * per, *dout = stage_dev_ + (size_t)n_in * per;
+    const int16_t *dout = StagedIo(stage_dev_, row, per, has_clean).out;
     std::atomic<int> launched{0};
     std::atomic<bool> failed{!ok};
     std::thread downloader([&] {
@@ -862,16 +853,13 @@ bool BatchEngine::ProcessBlocksHostPipelined(const IoView &io, int num_blocks) {
         const size_t first = (size_t)k * kHostChunkStreams;
         const size_t count = std::min<size_t>(kHostChunkStreams, num_streams_ - first);
         const size_t off = first * row, bytes = count * row * sizeof(int16_t);
-        bool up = AECM_HIP_OK(hipMemcpyAsync(dfar + off, io.far + off, bytes, hipMemcpyHostToDevice, stream_)) &&
-                  AECM_HIP_OK(hipMemcpyAsync(dnear + off, io.near + off, bytes, hipMemcpyHostToDevice, stream_)) &&
-                  (!io.near_clean || AECM_HIP_OK(hipMemcpyAsync(dclean + off, io.near_clean + off, bytes, hipMemcpyHostToDevice, stream_)));
-        StatePtrs st = st_;
-        st.vec += first * kVecWordsPerStream;
-        st.scal += first * kNumScal;
-        st.hist += first * kHistWordsPerStream;
-        IoView dev{dfar + off, dnear + off, io.near_clean ? dclean + off : nullptr, dout + off, (int64_t)row, kBlock};
-        up = up && LaunchBlocks(st, dev, PlanLaunch(policy_, switches_, (int)count, num_blocks, io.near_clean != nullptr)) &&
-             AECM_HIP_OK(hipEventRecord(done[k], stream_));
+        const IoView dev = StagedIo(stage_dev_ + off, row, per, has_clean);      // the chunk's streams in the batch's planes
+        auto upload = [&](const int16_t *src, const int16_t *dst) {
+            return AECM_HIP_OK(hipMemcpyAsync(const_cast<int16_t *>(dst), src + off, bytes, hipMemcpyHostToDevice, stream_));
+        };
+        const bool up = upload(io.far, dev.far) && upload(io.near, dev.near) && (!has_clean || upload(io.near_clean, dev.near_clean)) &&
+                        LaunchBlocks(OffsetToStream(st_, first), dev, PlanLaunch(policy_, switches_, (int)count, num_blocks, has_clean)) &&
+                        AECM_HIP_OK(hipEventRecord(done[k], stream_));
         if (!up) failed = true;
         launched.store(k + 1, std::memory_order_release);
     }
@@ -885,21 +873,8 @@ bool BatchEngine::ProcessBlocksHostPipelined(const IoView &io, int num_blocks) {
 
 // Grow-only device scratch shared by the recording batches (no hipMalloc / hipFree per call).
 bool BatchEngine::EnsureRecordingScratch(size_t map_elems, size_t sample_elems) {
-    if (map_elems > rec_maps_elems_) {
-        (void)hipFree(rec_maps_);
-        rec_maps_ = nullptr;
-        rec_maps_elems_ = 0;
-        if (!AECM_HIP_OK(hipMalloc((void **)&rec_maps_, map_elems * sizeof(int32_t)))) return false;
-        rec_maps_elems_ = map_elems;
-    }
-    if (sample_elems > rec_scratch_elems_) {
-        (void)hipFree(rec_scratch_);
-        rec_scratch_ = nullptr;
-        rec_scratch_elems_ = 0;
-        if (!AECM_HIP_OK(hipMalloc((void **)&rec_scratch_, sample_elems * sizeof(int16_t)))) return false;
-        rec_scratch_elems_ = sample_elems;
-    }
-    return true;
+    return GrowDeviceBuffer((void **)&rec_maps_, &rec_maps_elems_, map_elems, sizeof(int32_t), stream_) &&
+           GrowDeviceBuffer((void **)&rec_scratch_, &rec_scratch_elems_, sample_elems, sizeof(int16_t), stream_);
 }
 
 bool BatchEngine::ProcessRecordings(const int16_t *far, const int16_t *near, const int16_t *clean, int16_t *out,

@@ -129,6 +129,11 @@ LaunchPlan PlanRaggedLaunch(const LaunchPolicy &policy, const LaunchSwitches &sw
 // The reporting arithmetic (grid, residency, rounds, evenness): O(workgroups) for a pipelined plan, so never on the launch path.
 LaunchDescription DescribePlan(const LaunchPolicy &policy, const LaunchPlan &plan);
 
+// A grow-only device allocation (the recording scratch, ProcessBlocksRaggedHost's stage, SessionBatch::Grow): a buffer of `*have` units of `unit` bytes has at least `need` afterwards, contents not
+// kept.  Work enqueued on `stream` may still use the old buffer, so the stream is synchronised before a non-null one is freed.
+// false: the stream failed (the old buffer stays: *buf is not null) or there is no memory (*buf is null, *have 0).
+bool GrowDeviceBuffer(void **buf, size_t *have, size_t need, size_t unit, hipStream_t stream);
+
 class BatchEngine {
 public:
     // Returns nullptr if the device cannot be used or memory cannot be allocated.
@@ -156,7 +161,9 @@ public:
     // in the signature because the engine's CPU double (tests/sim/sim_engine.cpp) defines this member as it has always been declared.
     bool ProcessBlocks(const IoView &io_dev, int num_blocks, const int32_t *retired = nullptr);
     bool ProcessBlocksRange(const IoView &io_dev, int num_blocks, int first, int count);
-    bool ProcessBlocksHost(const IoView &io_host, int num_blocks);     // sync
+    // sync.  One of three paths (aecm_engine.cpp): buffers that fit kMappedBytes through the mapped buffer;
+    // else dense rows of at least 2 x kHostChunkStreams streams through the chunked pipeline; else staged.
+    bool ProcessBlocksHost(const IoView &io_host, int num_blocks);
     // Ragged launches: stream s runs its first blocks_per_stream_host[s] blocks only (host array, read before the call returns;
     // the Range form's array and io are indexed from `first`).  Its state afterwards is the state after exactly that many blocks,
     // its out blocks beyond that are not written.  Every length equal to num_blocks: exactly ProcessBlocks.  async like ProcessBlocks.
@@ -281,7 +288,7 @@ private:
     float last_ms_ = 0.f;
     double total_ms_ = 0.0;
     int64_t launches_ = 0;
-    // staging for ProcessBlocksHost
+    // staging for ProcessBlocksHost and ProcessBlocksRaggedHost: far | near | [clean] | out (aecm_host_rows.h: StagedIo)
     int16_t *stage_dev_ = nullptr;
     size_t stage_elems_ = 0;
     static constexpr int kHostChunkStreams = 8192;

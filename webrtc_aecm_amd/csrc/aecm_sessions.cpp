@@ -290,16 +290,11 @@ bool SessionBatch::WaitForCallerEvent(void *wait_event) {
     return false;
 }
 
-// A grow-only device buffer of `*have` units: at least `need` afterwards, contents not kept.
+// A grow-only device buffer of `*have` units: at least `need` afterwards, contents not kept (aecm_engine.h: GrowDeviceBuffer).
+// A stream that could not be synchronised poisons the object; no memory does not.
 int32_t SessionBatch::Grow(void **buf, size_t *have, size_t need, size_t unit) {
-    if (need <= *have) return 0;
-    if (*buf && !AECM_HIP_OK(hipStreamSynchronize(engine_->stream()))) return Fail();      // (nothing enqueued may still use the old one)
-    (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    if (!AECM_HIP_OK(hipMalloc(buf, need * unit))) { *buf = nullptr; return AECM_UNSPECIFIED_ERROR; }
-    *have = need;
-    return 0;
+    if (GrowDeviceBuffer(buf, have, need, unit, engine_->stream())) return 0;
+    return *buf ? Fail() : AECM_UNSPECIFIED_ERROR;
 }
 // The same for a buffer of one size, allocated by the first call that needs it.
 int32_t SessionBatch::GrowOnce(void **buf, size_t bytes) {

@@ -105,6 +105,13 @@ struct StatePtrs {
     uint16_t *hist;
     const uint32_t *consts;   // kConstBlobWords words
 };
+// The same state from stream `first` on: what a launch over streams [first, first + count) indexes from 0.
+inline StatePtrs OffsetToStream(StatePtrs st, size_t first) {
+    st.vec += first * kVecWordsPerStream;
+    st.scal += first * kNumScal;
+    st.hist += first * kHistWordsPerStream;
+    return st;
+}
 
 // Strided view of the audio I/O of one launch: sample (stream s, block b, i) lives at
 // base[s * stream_stride + b * block_stride + i].  Stream-major files are (T*64, 64); a tick-major
