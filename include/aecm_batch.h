@@ -152,6 +152,44 @@ int32_t WebRtcAecmBatch_ImportStatesDevice(AecmBatch *b, int32_t first, int32_t 
 /* 24-word digest of one stream's complete state (canonical order: oracle/aecm_oracle.c). */
 int32_t WebRtcAecmBatch_GetDigest(AecmBatch *b, int32_t stream, uint32_t digest[AECM_BATCH_DIGEST_WORDS]);
 
+/* ---- Block trace: what every block decided ------------------------------------------------------------
+ * Opt-in.  While a trace buffer is attached to a batch, every block that a device-pointer block launch processes
+ * (WebRtcAecmBatch_ProcessBlocks, WebRtcAecmBatch_ProcessBlocksRagged; with and without near_clean_dev) also writes one 32-byte
+ * record: the estimated echo delay, the far-end activity, the suppression gain ... of that stream directly after that block -- every
+ * field the value WebRtcAecmBatch_ExportState / GetDigest would show there, i.e. the named member of the reference's state after its
+ * WebRtcAecm_ProcessBlock for that block.  Little endian; the digest word each field is read from in brackets.
+ * Audio, state and digests are identical with and without a trace; with none attached nothing changes at all. */
+typedef struct AecmBlockTrace {
+    uint32_t tot_count;             /*  0  AecmCore::totCount                        [0]        */
+    int16_t delay;                  /*  4  BinaryDelayEstimator::last_delay; -2: none yet  [13] */
+    int16_t startup_state;          /*  6  startupState                              [2, low]   */
+    int16_t vad;                    /*  8  currentVADValue                           [7, low]   */
+    int16_t vad_update_count;       /* 10  vadUpdateCount                            [7, high]  */
+    int16_t far_log_energy;         /* 12  farLogEnergy                              [4, low]   */
+    int16_t far_energy_min;         /* 14  farEnergyMin                              [4, high]  */
+    int16_t far_energy_max;         /* 16  farEnergyMax                              [5, low]   */
+    int16_t far_energy_vad;         /* 18  farEnergyVAD                              [6, low]   */
+    int16_t sup_gain;               /* 20  supGain                                   [12, low]  */
+    int16_t near_q;                 /* 22  dfaNoisyQDomain                           [3, low]   */
+    int32_t delay_min_probability;  /* 24  BinaryDelayEstimator::minimum_probability [14]       */
+    int32_t delay_last_probability; /* 28  BinaryDelayEstimator::last_delay_probability [15]    */
+} AecmBlockTrace;
+size_t WebRtcAecmBatch_block_trace_size_bytes(void);      /* 32 */
+/* Attaches trace_dev (device memory; NULL detaches).  Strides are in records: block k of a launch, for the stream at position s of
+ * that launch, is written at trace_dev + 32 * (s * stream_stride + k * block_stride).  k counts from 0 in every launch -- the
+ * convention of the audio's strides, so a stream-major buffer [S][T] is (T, 1) and a tick-major one [T][S] is (1, S).  A ragged stream
+ * of length L writes exactly its records 0 .. L - 1, one of length 0 none; everything else in the buffer is untouched.  The caller owns
+ * the buffer and its size, as for out_dev.
+ * Returns 0, or AECM_BAD_PARAMETER_ERROR with nothing changed for a NULL batch, a pointer that is not 4-byte aligned, or a stride <= 0.
+ * While a trace is attached:
+ *  - the host-pointer forms -- WebRtcAecmBatch_ProcessBlocksHost, WebRtcAecmBatch_ProcessBlocksRaggedHost -- and the whole
+ *    WebRtcAecmBatch_ProcessRecordings* family (whose call-to-block map is not block-aligned) return
+ *    AECM_UNSUPPORTED_FUNCTION_ERROR with nothing run and nothing changed;
+ *  - a launch never takes the pipelined form (the traced values live in four different role waves there): a size that would be
+ *    pipelined -- by default 2 .. 4 096 streams -- runs one wavefront per stream; the chunk queue and the one-wave forms are chosen
+ *    as always.  Results do not depend on the launch form.  WebRtcAecmBatch_DescribeLaunch answers for the traced launch. */
+int32_t WebRtcAecmBatch_SetBlockTrace(AecmBatch *b, void *trace_dev, int64_t stream_stride, int64_t block_stride);
+
 /* ---- Streaming batch of sessions --------------------------------------------------------------------
  * S independent WebRtcAecm_* sessions that share one call pattern (a media server's 10 ms clock):
  * every WebRtcAecmSessions_Tick is, for each stream s,
@@ -640,6 +678,10 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetail(const AecmLaunchPolicy *policy, int
  * the switch is a property of the batch, not of the policy.) */
 int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
                                                int32_t has_clean_input, int32_t clean_pipelining, AecmLaunchDescription *out);
+/* The same for a launch of a batch with a block trace attached (WebRtcAecmBatch_SetBlockTrace), no device needed: never form 3 -- where
+ * WebRtcAecmBatch_DescribeLaunchDetail says pipelined this says one wavefront per stream -- and that call's answer everywhere else. */
+int32_t WebRtcAecmBatch_DescribeTracedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
+                                             int32_t has_clean_input, AecmLaunchDescription *out);
 /* The same for a ragged launch (WebRtcAecmBatch_ProcessBlocksRagged) of num_streams streams with these lengths, no device needed: form,
  * chunk and grid as above -- the chunk queue when more streams than the queue's threshold have blocks to run and the longest has at
  * least two chunks, else one wavefront per stream; never pipelined (this call describes a batch that has not opted in:

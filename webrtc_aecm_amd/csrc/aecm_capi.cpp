@@ -139,6 +139,7 @@ int32_t WebRtcAecmBatch_ProcessBlocksHost(AecmBatch *b, const int16_t *far_host,
                                           const int16_t *near_clean_host, int16_t *out_host, int64_t stream_stride,
                                           int64_t block_stride, int32_t num_blocks) {
     if (int32_t rc = CheckIo(b, far_host, near_host, out_host, num_blocks)) return rc;
+    if (b->engine->block_trace_attached()) return AECM_UNSUPPORTED_FUNCTION_ERROR;      // the block trace is for device-pointer launches
     if (num_blocks == 0) return 0;
     aecm::IoView io{far_host, near_host, near_clean_host, out_host, stream_stride, block_stride};
     return b->engine->ProcessBlocksHost(io, num_blocks) ? 0 : AECM_UNSPECIFIED_ERROR;
@@ -148,6 +149,7 @@ static int32_t ProcessRecordings(AecmBatch *b, const int16_t *far_p, const int16
                                  int16_t *out_p, int64_t stream_stride, int32_t samples_per_call, int32_t num_calls, int16_t ms,
                                  bool host) {
     if (int32_t rc = CheckIo(b, far_p, near_p, out_p, num_calls)) return rc;
+    if (b->engine->block_trace_attached()) return AECM_UNSUPPORTED_FUNCTION_ERROR;      // (a recording's call-to-block map is not block-aligned)
     if (samples_per_call != 80 && samples_per_call != 160) return AECM_BAD_PARAMETER_ERROR;
     if (stream_stride < (int64_t)samples_per_call * num_calls) return AECM_BAD_PARAMETER_ERROR;
     if (num_calls == 0) return 0;
@@ -193,6 +195,7 @@ int32_t WebRtcAecmBatch_ProcessBlocksRaggedHost(AecmBatch *b, const int16_t *far
                                                 int16_t *out_host, int64_t stream_stride, int64_t block_stride, int32_t num_blocks,
                                                 const int32_t *blocks_per_stream_host) {
     if (int32_t rc = CheckIo(b, far_host, near_host, out_host, num_blocks)) return rc;
+    if (b->engine->block_trace_attached()) return AECM_UNSUPPORTED_FUNCTION_ERROR;
     if (int32_t rc = CheckLengths(b, blocks_per_stream_host, num_blocks)) return rc;
     if (num_blocks == 0) return 0;
     aecm::IoView io{far_host, near_host, near_clean_host, out_host, stream_stride, block_stride};
@@ -203,6 +206,7 @@ static int32_t ProcessRecordingsRagged(AecmBatch *b, const int16_t *far_p, const
                                        int64_t stream_stride, int32_t samples_per_call, int32_t num_calls, const int32_t *calls, int16_t ms,
                                        int32_t *codes, bool host) {
     if (int32_t rc = CheckIo(b, far_p, near_p, out_p, num_calls)) return rc;
+    if (b->engine->block_trace_attached()) return AECM_UNSUPPORTED_FUNCTION_ERROR;      // (a recording's call-to-block map is not block-aligned)
     if (samples_per_call != 80 && samples_per_call != 160) return AECM_BAD_PARAMETER_ERROR;
     if (stream_stride < (int64_t)samples_per_call * num_calls) return AECM_BAD_PARAMETER_ERROR;
     if (int32_t rc = CheckLengths(b, calls, num_calls)) return rc;
@@ -333,6 +337,14 @@ int32_t WebRtcAecmBatch_GetDigest(AecmBatch *b, int32_t stream, uint32_t digest[
     if (!b->engine->initialized()) return AECM_UNINITIALIZED_ERROR;
     if (stream < 0 || stream >= b->engine->num_streams()) return AECM_BAD_PARAMETER_ERROR;
     return b->engine->Digest(stream, digest) ? 0 : AECM_UNSPECIFIED_ERROR;
+}
+
+static_assert(sizeof(AecmBlockTrace) == aecm::kTraceWords * sizeof(uint32_t), "the block trace record is eight words");
+size_t WebRtcAecmBatch_block_trace_size_bytes(void) { return sizeof(AecmBlockTrace); }
+
+int32_t WebRtcAecmBatch_SetBlockTrace(AecmBatch *b, void *trace_dev, int64_t stream_stride, int64_t block_stride) {
+    if (!b) return AECM_BAD_PARAMETER_ERROR;
+    return b->engine->SetBlockTrace(trace_dev, stream_stride, block_stride);
 }
 
 int32_t WebRtcAecmBatch_SetKernelVariant(AecmBatch *b, int32_t variant) {
@@ -487,6 +499,18 @@ int32_t WebRtcAecmBatch_DescribeLaunchDetailEx(const AecmLaunchPolicy *policy, i
     aecm::LaunchPolicy p;
     if (const int32_t rc = ResolvePolicy(policy, compute_units, &p)) return rc;
     const aecm::LaunchSwitches sw{aecm::kVariantFast, false, clean_pipelining != 0};
+    DescriptionToAbi(aecm::DescribePlan(p, aecm::PlanLaunch(p, sw, num_streams, num_blocks, has_clean_input != 0)), out);
+    return 0;
+}
+
+int32_t WebRtcAecmBatch_DescribeTracedLaunch(const AecmLaunchPolicy *policy, int32_t compute_units, int32_t num_streams, int32_t num_blocks,
+                                             int32_t has_clean_input, AecmLaunchDescription *out) {
+    if (!out) return AECM_NULL_POINTER_ERROR;
+    if (num_streams <= 0 || num_blocks <= 0) return AECM_BAD_PARAMETER_ERROR;
+    aecm::LaunchPolicy p;
+    if (const int32_t rc = ResolvePolicy(policy, compute_units, &p)) return rc;
+    aecm::LaunchSwitches sw;
+    sw.trace = true;
     DescriptionToAbi(aecm::DescribePlan(p, aecm::PlanLaunch(p, sw, num_streams, num_blocks, has_clean_input != 0)), out);
     return 0;
 }

@@ -326,11 +326,12 @@ LaunchPlan UndecidedPlan(int variant, int count, int num_blocks, bool has_clean)
 
 LaunchPlan PlanLaunch(const LaunchPolicy &p, const LaunchSwitches &sw, int count, int num_blocks, bool has_clean) {
     LaunchPlan plan = UndecidedPlan(sw.variant, count, num_blocks, has_clean);
+    plan.trace = sw.trace;
     const int chunk = QueueChunkFor(p, count);
     if (QueueLaunchApplies(count, num_blocks, sw.variant, chunk, QueueMinStreams(p))) {
         plan.form = 2;
         plan.chunk_blocks = chunk;
-    } else if (PipelinedLaunchApplies(p, sw.variant, count, num_blocks, has_clean, sw.clean_pipelining)) {
+    } else if (!sw.trace && PipelinedLaunchApplies(p, sw.variant, count, num_blocks, has_clean, sw.clean_pipelining)) {      // (no traced pipelined form)
         plan.form = 3;
         plan.shape = has_clean ? PipelinedCleanShapeFor(count, num_blocks, p.compute_units, p.pipe) : PipelinedShapeFor(count, num_blocks, p.compute_units, p.pipe);
     } else {
@@ -502,6 +503,7 @@ LaunchPlan PlanRaggedLaunch(const LaunchPolicy &p, const LaunchSwitches &sw, int
     } else {
         plan = UndecidedPlan(sw.variant, count, longest, has_clean);      // (longest 0: nothing to launch)
         plan.is_ragged = true;
+        plan.trace = sw.trace;
         // the queue over the live streams; else -- the opt-in -- a launch the chip holds at once pipelined, by the LIVE streams, not the
         // batch's size; else one wavefront per stream of the whole range, each with its own count (a wave of a zero-length stream leaves at once)
         const int chunk = QueueChunkFor(p, live);
@@ -511,7 +513,7 @@ LaunchPlan PlanRaggedLaunch(const LaunchPolicy &p, const LaunchSwitches &sw, int
         } else if (longest > 0) {
             plan.form = WavePerStreamForm(p, sw.variant, count);
             // (a clean input: by a switch of its own, in the clean shapes -- the other two switches leave such a launch as it is)
-            const bool opted_in = has_clean ? sw.ragged_clean_pipelining : sw.ragged_pipelining;
+            const bool opted_in = !sw.trace && (has_clean ? sw.ragged_clean_pipelining : sw.ragged_pipelining);      // (no traced pipelined form)
             if (opted_in && PipelinedLaunchApplies(p, sw.variant, live, longest, has_clean, has_clean)) {
                 plan.shape = has_clean ? PipelinedCleanShapeFor(live, longest, p.compute_units, p.pipe) : RaggedPipeShapeFor(live, longest, p.compute_units, p.pipe);
                 if (BuildRaggedPipePlan(lens, count, plan.shape, p.compute_units, &plan.pipe)) plan.form = 3;
@@ -583,6 +585,7 @@ bool BatchEngine::UploadPlanWords(const std::vector<uint32_t> &plan_words, uint3
 bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, const LaunchPlan &plan) {
     if (launch_failed_) return false;                 // streams half processed by an abandoned launch: nothing runs until Init
     if (plan.form < 0 || plan.has_clean != (io.near_clean != nullptr)) return false;      // not the plan of this launch
+    if (plan.trace && (plan.form == 3 || !trace_.records)) return false;                  // (PlanLaunch never makes the first; the second: detached since)
     const int count = plan.count, num_blocks = plan.num_blocks;
     const int32_t *lens_dev = nullptr;
     if (plan.is_ragged) {
@@ -600,6 +603,12 @@ bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, const Laun
         if (!plan.is_ragged && !EnsureLaunchControl(QueueControlBytes(count))) return false;
         if (!EnsureLaunchErrorWord()) return false;
         queue_unchecked_ = true;
+        if (plan.trace) {
+            if (plan.is_ragged)
+                return AECM_HIP_OK(LaunchTraceBlocksRaggedQueued(st, io, trace_, count, plan.ragged.live_streams, (uint32_t)plan.ragged.items, plan.chunk_blocks,
+                                                                 policy_.resident_waves, queue_ctl_, queue_err_, stream_));
+            return AECM_HIP_OK(LaunchTraceBlocksQueued(st, io, trace_, count, num_blocks, plan.chunk_blocks, policy_.resident_waves, queue_ctl_, queue_err_, stream_));
+        }
         if (plan.is_ragged)
             return AECM_HIP_OK(LaunchProcessBlocksRaggedQueued(st, io, count, plan.ragged.live_streams, (uint32_t)plan.ragged.items, plan.chunk_blocks,
                                                                policy_.resident_waves, queue_ctl_, queue_err_, stream_));
@@ -615,8 +624,22 @@ bool BatchEngine::LaunchBlocks(const StatePtrs &st, const IoView &io, const Laun
         return AECM_HIP_OK(LaunchProcessBlocksPipelined(st, io, count, num_blocks, plan.shape, need_ctl ? queue_ctl_ : nullptr, stream_));
     }
     default:
+        if (plan.trace) return AECM_HIP_OK(LaunchTraceBlocks(st, io, trace_, count, num_blocks, plan.variant, plan.form == 1, stream_, lens_dev));
         return AECM_HIP_OK(LaunchProcessBlocks(st, io, count, num_blocks, plan.variant, plan.form == 1, stream_, lens_dev));
     }
+}
+
+int32_t BatchEngine::SetBlockTrace(void *trace_dev, int64_t stream_stride, int64_t block_stride) {
+    if (!trace_dev) {
+        trace_ = TraceView{nullptr, 0, 0};
+        switches_.trace = false;
+        return 0;
+    }
+    // the kernels store the records as 32-bit words: a pointer that is not a multiple of 4 would fault on the GPU
+    if ((reinterpret_cast<uintptr_t>(trace_dev) & 3) || stream_stride <= 0 || block_stride <= 0) return kErrBadParameter;
+    trace_ = TraceView{static_cast<uint32_t *>(trace_dev), stream_stride, block_stride};
+    switches_.trace = true;
+    return 0;
 }
 
 int BatchEngine::DescribeLaunch(int num_blocks, bool has_clean, int *chunk_blocks) const {
@@ -683,6 +706,7 @@ int32_t BatchEngine::ProcessBlocksRaggedRange(const IoView &io, int num_blocks, 
 // Host audio: the live blocks are packed into dense device rows (zeros behind a stream's length), run, and the blocks that
 // were written are copied back.
 int32_t BatchEngine::ProcessBlocksRaggedHost(const IoView &io, int num_blocks, const int32_t *lens) {
+    if (switches_.trace) return kErrUnsupported;      // the block trace is for device-pointer launches
     if (num_blocks < 0 || !lens) return kErrBadParameter;
     for (int s = 0; s < num_streams_; ++s)
         if (lens[s] < 0 || lens[s] > num_blocks) return kErrBadParameter;
@@ -730,6 +754,7 @@ bool BatchEngine::TimedLaunch(const IoView &io, int first, const LaunchPlan &pla
 }
 
 bool BatchEngine::ProcessBlocksHost(const IoView &io, int num_blocks) {
+    if (switches_.trace) return false;                // the block trace is for device-pointer launches (the C ABI answers AECM_UNSUPPORTED_FUNCTION_ERROR)
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
     // Dense repack on the device side: [S][T*64] for each of far / near / (clean) / out.
     const size_t per = (size_t)num_streams_ * num_blocks * kBlock;
@@ -889,6 +914,7 @@ bool BatchEngine::ProcessRecordingsRagged(const int16_t *far, const int16_t *nea
                                           int frame, int n_calls, const int32_t *calls, int16_t ms, bool host_pointers, int32_t *rc,
                                           int32_t *codes) {
     if (!AECM_HIP_OK(hipSetDevice(device_))) return false;
+    if (switches_.trace) { *rc = kErrUnsupported; return true; }     // the recording's call-to-block map is not block-aligned: no block trace of it
     if (mixed_rates_) { *rc = kErrUnsupported; return true; }        // an imported stream runs at another rate than fs_
     const RecordingSchedule sch = BuildRecordingSchedule(fs_, frame, n_calls, ms);
     std::vector<int32_t> lens, limits;                                // per stream: blocks to run, output samples to assemble

@@ -101,6 +101,9 @@ struct LaunchSwitches {
     bool ragged_pipelining = false;   // BatchEngine::set_ragged_pipelining: ragged launches the chip holds at once are pipelined
     bool clean_pipelining = false;    // BatchEngine::set_clean_pipelining: equal-length launches WITH a clean input are pipelined too
     bool ragged_clean_pipelining = false;      // BatchEngine::set_ragged_clean_pipelining: ragged launches WITH a clean input are pipelined too
+    // BatchEngine::SetBlockTrace: a block trace is attached.  The launch runs the traced kernels (aecm_trace_kernels.hip) and never takes
+    // the pipelined form -- there the traced values live in four role waves: a size that would be pipelined runs one wavefront per stream
+    bool trace = false;
 };
 // Everything one launch of the block kernels runs by.  PlanLaunch and PlanRaggedLaunch (pure host logic) are the only places that
 // decide it; BatchEngine launches a plan as it stands and DescribePlan reports it, so what is reported is what runs.
@@ -109,6 +112,7 @@ struct LaunchPlan {
     int variant = kVariantFast;
     int count = 0, num_blocks = 0;    // streams of the launch; blocks of each (ragged: of the longest; 0: nothing to launch)
     bool has_clean = false;
+    bool trace = false;               // the traced twin of the form's kernel (never form 3); LaunchBlocks writes the records by the engine's TraceView
     int chunk_blocks = 0;             // form 2: blocks per item of the queue
     PipeShape shape{};                // form 3
     bool is_ragged = false;           // the lengths differ: forms 0 to 2 run by `ragged`, form 3 by `pipe`
@@ -221,6 +225,13 @@ public:
     // The session batch scattered a core state of another rate than fs() into a stream itself (bulk session import): what
     // ImportState notes when it brings one in.
     void NoteStreamOfOtherRate() { mixed_rates_ = true; }
+    // The block trace (include/aecm_batch.h: WebRtcAecmBatch_SetBlockTrace).  While a buffer is attached every block a device-pointer
+    // launch processes also writes one 32-byte record: block k of the stream at position s of the launch (ProcessBlocksRange: s from
+    // `first`) at trace_dev + 32 * (s * stream_stride + k * block_stride).  trace_dev == nullptr detaches.  The caller owns the buffer
+    // and its size, as for the output.  The host-pointer forms and ProcessRecordings refuse to run while one is attached.
+    // 0, or kErrBadParameter (nothing changed): a pointer that is not 4-byte aligned, a stride <= 0.
+    int32_t SetBlockTrace(void *trace_dev, int64_t stream_stride, int64_t block_stride);
+    bool block_trace_attached() const { return switches_.trace; }
     void set_variant(int v) { switches_.variant = v; }
     // blocks = 0: every launch in the one-stream-per-wave form.  min_streams < 0: launches of more streams than the chip
     // holds waves take the queue form (the default); otherwise launches of more than min_streams streams do (tests).
@@ -254,6 +265,7 @@ private:
     bool LaunchBlocks(const StatePtrs &st, const IoView &io, const LaunchPlan &plan);
     bool TimedLaunch(const IoView &io, int first, const LaunchPlan &plan);
     LaunchSwitches switches_;
+    TraceView trace_{nullptr, 0, 0};     // what SetBlockTrace attached (switches_.trace says whether)
     // The plan's way to the device: a pinned staging buffer (grown on first use) and the event behind its last upload -- the
     // buffer is rewritten only when that copy has run, so ragged launches queue back to back like the others.
     uint32_t *plan_host_ = nullptr;

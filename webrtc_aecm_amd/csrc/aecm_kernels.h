@@ -47,6 +47,17 @@ size_t RaggedQueueControlBytes(int n_streams, int n_chunks);
 hipError_t LaunchProcessBlocksRaggedQueued(const StatePtrs &st, const IoView &io, int n_streams, int live_streams, uint32_t n_items, int chunk_blocks,
                                            int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
 
+// The same three launches with a block trace attached (aecm_trace_kernels.hip: aecm_trace_process_kernel, aecm_trace_queue_kernel,
+// aecm_trace_ragged_queue_kernel): block k of the stream at position s of the launch also writes its 32-byte record to
+// tv.records + kTraceWords * (s * tv.stream_stride + k * tv.block_stride) (aecm_state.h: TraceView; tv.records must not be null).
+// The arguments besides tv, the control buffers and the results are those of the launches above.  There is no traced pipelined launch.
+hipError_t LaunchTraceBlocks(const StatePtrs &st, const IoView &io, const TraceView &tv, int n_streams, int n_blocks, int variant, bool phase_priority,
+                             hipStream_t stream, const int32_t *blocks_per_stream = nullptr);
+hipError_t LaunchTraceBlocksQueued(const StatePtrs &st, const IoView &io, const TraceView &tv, int n_streams, int n_blocks, int chunk_blocks,
+                                   int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
+hipError_t LaunchTraceBlocksRaggedQueued(const StatePtrs &st, const IoView &io, const TraceView &tv, int n_streams, int live_streams, uint32_t n_items,
+                                         int chunk_blocks, int resident_waves, uint32_t *ctl, uint32_t *err, hipStream_t stream);
+
 // The pipelined form of a launch the chip holds at once (aecm_block_kernels.hip): a workgroup serves four streams with one
 // "back" wave per stream and, in waves of their own, the state-independent forward transforms one block ahead (front waves)
 // and -- in some shapes -- the inverse transforms one block behind (tail waves).  Fast variant, every stream the same number of
@@ -254,6 +265,8 @@ hipError_t LaunchFft128(int16_t *data_dev, int32_t *scales_dev, int variant, int
 hipError_t ReadCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_block_kernels.hip (device symbols are per translation unit); ReadCheckCounters adds it in.  Does not synchronise.
 hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_trace_kernels.hip (the traced block kernels); ReadCheckCounters adds it in as well.  Does not synchronise.
+hipError_t ReadTraceKernelCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_calls_kernels.hip, for callers that audit K-call ticks (ReadCheckCounters does not add it in).  Does not synchronise.
 hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_packets_kernels.hip, likewise.

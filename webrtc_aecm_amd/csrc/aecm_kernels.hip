@@ -22,8 +22,11 @@ hipError_t ReadCheckCounters(uint64_t counters[2], bool reset) {
     uint64_t blocks[2] = {0, 0};
     e = ReadBlockKernelCheckCounters(blocks, reset);       // the block kernels' unit keeps its own pair
     if (e != hipSuccess) return e;
-    counters[0] = host[0] + blocks[0];
-    counters[1] = host[1] + blocks[1];
+    uint64_t traced[2] = {0, 0};
+    e = ReadTraceKernelCheckCounters(traced, reset);       // and so does the traced block kernels'
+    if (e != hipSuccess) return e;
+    counters[0] = host[0] + blocks[0] + traced[0];
+    counters[1] = host[1] + blocks[1] + traced[1];
     if (reset) {
         const unsigned long long zero[2] = {0, 0};
         e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail), zero, sizeof zero);

@@ -125,5 +125,15 @@ struct IoView {
     int64_t block_stride;
 };
 
+// The block trace of one launch (include/aecm_batch.h: AecmBlockTrace, 32 bytes = kTraceWords words per record): the record of
+// (stream at position s of the launch, block k of the launch) lives at records + kTraceWords * (s * stream_stride + k * block_stride)
+// -- strides in records, IoView's convention, so stream-major and tick-major layouts both work.
+constexpr int kTraceWords = 8;
+struct TraceView {
+    uint32_t *records;           // nullptr: no trace attached
+    int64_t stream_stride;
+    int64_t block_stride;
+};
+
 }  // namespace aecm
 #endif  // AECM_AMD_STATE_H_

@@ -1919,6 +1919,86 @@ struct BlockEngine {
         StridedIo sio{io, stream * io.stream_stride};
         run_stream_io(st, sio, stream, n_blocks);
     }
+
+    // ------------------------------------------------------------------------------------------
+    // The block trace (include/aecm_batch.h: AecmBlockTrace): what a block decided, as the eight words ExportState / GetDigest
+    // would show directly after it -- the stored form of the Uniform members (store_state writes them as they are; the 16-bit
+    // fields are their low halves, as ComputeDigest packs them).  Word w of the record in lane w, zero in the other lanes.
+    //   0 tot_count   1 last_delay | startup << 16   2 cur_vad | vad_cnt << 16   3 far_log | fe_min << 16
+    //   4 fe_max | fe_vad << 16   5 sup_gain | dfa_noisy_q << 16   6 min_prob   7 last_prob
+    // The halves are packed on the scalar side; eight v_writelane put them into one vector register.
+    // ------------------------------------------------------------------------------------------
+    static AECM_HD int trace_pack(int lo, int hi) { return zext16(lo) | shl(hi, 16); }
+    static AECM_HD vi block_trace_row(const Regs &r) {
+        const Uniform &u = r.u;
+        vi row = vi(0);
+        row = W::writelane(row, u.tot_count, 0);
+        row = W::writelane(row, trace_pack(u.last_delay, u.startup), 1);
+        row = W::writelane(row, trace_pack(u.cur_vad, u.vad_cnt), 2);
+        row = W::writelane(row, trace_pack(u.far_log, u.fe_min), 3);
+        row = W::writelane(row, trace_pack(u.fe_max, u.fe_vad), 4);
+        row = W::writelane(row, trace_pack(u.sup_gain, u.dfa_noisy_q), 5);
+        row = W::writelane(row, u.min_prob, 6);
+        row = W::writelane(row, u.last_prob, 7);
+        return row;
+    }
+
+    // StridedIo with a trace: records = the record of this stream's block 0 of this run (TraceView's base, offset by the caller),
+    // block b's record kTraceWords x record_step words further on.  Lanes 0..7 store the record as one 32-byte row -- a plain
+    // output store like the audio's (W::store_out_u32_if), whatever the policy does with state words.
+    struct TracedIo {
+        const IoView &v;
+        int64_t base;
+        uint32_t *records;
+        int64_t record_step;
+        AECM_HD vi far(const Regs &r, int b) const { return W::load_i16(v.far + base + (int64_t)b * v.block_stride, r.lane); }
+        AECM_HD vi near(const Regs &r, int b) const { return W::load_i16(v.near + base + (int64_t)b * v.block_stride, r.lane); }
+        AECM_HD vi clean(const Regs &r, int b) const { return W::load_i16(v.near_clean + base + (int64_t)b * v.block_stride, r.lane); }
+        AECM_HD void out(const Regs &r, int b, vi val) const { W::store_i16(v.out + base + (int64_t)b * v.block_stride, r.brev, val); }
+        AECM_HD void trace(const Regs &r, int b) const {
+            W::store_out_u32_if(r.lane < kTraceWords, records + (int64_t)b * record_step * kTraceWords, r.lane, block_trace_row(r));
+        }
+        AECM_HD void ready() const {}
+    };
+    // Where the record of (stream position s, block k) of a launch lies: TraceView's rule.
+    static AECM_HD TracedIo traced_io(const IoView &io, const TraceView &tv, int64_t stream, int first_block) {
+        return TracedIo{io, stream * io.stream_stride + (int64_t)first_block * io.block_stride,
+                        tv.records + (stream * tv.stream_stride + (int64_t)first_block * tv.block_stride) * kTraceWords, tv.block_stride};
+    }
+
+    // A fourth entry: run_stream_io with a record per block (Io has trace(r, b) besides: the traced kernels of
+    // aecm_trace_kernels.hip, and tests/sim/sim_trace.cpp on the lane simulator).  The block loop once more, as the other three
+    // restate it: they stay what they were.  The record is taken behind process_block and the output store, i.e. of the state the
+    // block leaves.
+    template <class Io>
+    static AECM_HD void run_stream_traced(const StatePtrs &st, Io &io, int64_t stream, int n_blocks) {
+        Regs r;
+        init_lane_constants(r, st.consts);
+        uint32_t *vec = st.vec + stream * (int64_t)kVecWordsPerStream;
+        int32_t *scal = st.scal + stream * (int64_t)kNumScal;
+        uint16_t *hist = st.hist + stream * (int64_t)kHistWordsPerStream;
+        load_state(r, vec, scal);
+        io.ready();
+        vi far_next = io.far(r, 0);
+        vi near_next = io.near(r, 0);
+        vi clean_next = kHasClean ? io.clean(r, 0) : vi(0);
+        W::begin_stream();
+        for (int blk = 0; blk < n_blocks; ++blk) {
+            vi far_cur = far_next, near_cur = near_next, clean_cur = clean_next;
+            if (blk + 1 < n_blocks) {             // prefetch the next block's 3 x 128 bytes
+                far_next = io.far(r, blk + 1);
+                near_next = io.near(r, blk + 1);
+                if (kHasClean) clean_next = io.clean(r, blk + 1);
+            }
+            W::begin_block(blk, n_blocks);
+            vi out = process_block(r, hist, far_cur, near_cur, clean_cur);
+            io.out(r, blk, out);
+            io.trace(r, blk);
+            AECM_PHASE_MARK(13, r.out_ovl, r.x_old);
+        }
+        AECM_PHASE_MARK(14, r.out_ovl, r.x_old);
+        store_state(r, vec, scal);
+    }
 };
 
 }  // namespace aecm

@@ -51,7 +51,13 @@ BATCH_SYMBOLS = [
     "WebRtcAecmBatch_DescribeRaggedLaunchOf",
     "WebRtcAecmBatch_SetCleanPipelining", "WebRtcAecmBatch_DescribeLaunchDetailEx",
     "WebRtcAecmBatch_SetRaggedCleanPipelining", "WebRtcAecmBatch_DescribeRaggedLaunchEx2",
+    "WebRtcAecmBatch_block_trace_size_bytes", "WebRtcAecmBatch_SetBlockTrace", "WebRtcAecmBatch_DescribeTracedLaunch",
 ]
+# include/aecm_batch.h: AecmBlockTrace -- the 32-byte record a block writes while a trace is attached (AecmBatch.set_block_trace)
+BLOCK_TRACE_DTYPE = np.dtype([
+    ("tot_count", "<u4"), ("delay", "<i2"), ("startup_state", "<i2"), ("vad", "<i2"), ("vad_update_count", "<i2"),
+    ("far_log_energy", "<i2"), ("far_energy_min", "<i2"), ("far_energy_max", "<i2"), ("far_energy_vad", "<i2"),
+    ("sup_gain", "<i2"), ("near_q", "<i2"), ("delay_min_probability", "<i4"), ("delay_last_probability", "<i4")])
 SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_Create", "WebRtcAecmSessions_Free", "WebRtcAecmSessions_Init", "WebRtcAecmSessions_set_config",
     "WebRtcAecmSessions_Tick", "WebRtcAecmSessions_TickHost", "WebRtcAecmSessions_TickPerSession",
@@ -174,6 +180,12 @@ def load():
         lib.WebRtcAecmBatch_DescribeRaggedLaunchEx2.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32,
                                                                 C.POINTER(AecmLaunchDescription), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                                                 C.POINTER(C.c_int32)]
+    if hasattr(lib, "WebRtcAecmBatch_SetBlockTrace"):      # (as above)
+        lib.WebRtcAecmBatch_block_trace_size_bytes.restype = C.c_size_t
+        lib.WebRtcAecmBatch_block_trace_size_bytes.argtypes = []
+        lib.WebRtcAecmBatch_SetBlockTrace.argtypes = [vp, vp, C.c_int64, C.c_int64]
+        lib.WebRtcAecmBatch_DescribeTracedLaunch.argtypes = [C.POINTER(AecmLaunchPolicy), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                             C.POINTER(AecmLaunchDescription)]
     lib.WebRtcAecmBatch_Synchronize.argtypes = [vp]
     lib.WebRtcAecmBatch_GetLastLaunchMs.argtypes = [vp, C.POINTER(C.c_float)]
     lib.WebRtcAecmBatch_GetTimers.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
@@ -398,6 +410,16 @@ class AecmBatch:
         if form < 0:
             raise AecmError(form, "WebRtcAecmBatch_DescribeLaunch")
         return form, chunk.value
+
+    def set_block_trace(self, ptr, stream_stride, block_stride):
+        """Attach a block trace (include/aecm_batch.h: WebRtcAecmBatch_SetBlockTrace): ptr = device memory for BLOCK_TRACE_DTYPE
+        records, strides in records -- block k of a launch, for the stream at position s of it, goes to record
+        s * stream_stride + k * block_stride.  From now on process_device / process_ragged_device write one record per block,
+        never run pipelined, and the host-pointer forms raise (AECM_UNSUPPORTED_FUNCTION_ERROR).  Results do not change."""
+        self._check(self.lib.WebRtcAecmBatch_SetBlockTrace(self.h, ptr, stream_stride, block_stride), "SetBlockTrace")
+
+    def clear_block_trace(self):
+        self._check(self.lib.WebRtcAecmBatch_SetBlockTrace(self.h, None, 0, 0), "SetBlockTrace")
 
     def set_config(self, cng_mode, echo_mode, first=0, count=-1):
         self._check(self.lib.WebRtcAecmBatch_set_config(self.h, AecmConfig(cng_mode, echo_mode), first, count), "set_config")
@@ -1006,6 +1028,21 @@ def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int
         rc = load().WebRtcAecmBatch_DescribeLaunchDetail(pol, compute_units, num_streams, num_blocks, 1 if clean else 0, C.byref(d))
     if rc != 0:
         raise AecmError(rc, "WebRtcAecmBatch_DescribeLaunchDetail")
+    return d.as_dict()
+
+
+def block_trace_size_bytes() -> int:
+    return load().WebRtcAecmBatch_block_trace_size_bytes()
+
+
+def describe_traced_launch(num_streams: int, num_blocks: int, compute_units: int = 0, clean: bool = False, policy=None) -> dict:
+    """describe_launch_detail for a batch with a block trace attached (AecmBatch.set_block_trace), without a device: never the
+    pipelined form -- such a size runs one wavefront per stream -- and describe_launch_detail's answer everywhere else."""
+    d = AecmLaunchDescription()
+    pol = C.byref(policy) if policy is not None else None
+    rc = load().WebRtcAecmBatch_DescribeTracedLaunch(pol, compute_units, num_streams, num_blocks, 1 if clean else 0, C.byref(d))
+    if rc != 0:
+        raise AecmError(rc, "WebRtcAecmBatch_DescribeTracedLaunch")
     return d.as_dict()
 
 
