@@ -755,6 +755,24 @@ int32_t WebRtcAecmBatch_GetCheckCounters(int32_t device_id, uint64_t counters[2]
 int32_t WebRtcAecmBatch_DebugFft128(int32_t device_id, int16_t *data_host, int32_t *scales_host, int32_t variant,
                                     int32_t kernel_variant, int32_t count);
 
+/* Diagnostics, the ops probe: one fixed-point primitive of the block DSP (an entry of webrtc_aecm_amd/csrc/aecm_ops_table.inc:
+ * the functions of aecm_ops.h and the plain-integer helpers of aecm_wave.h), alone, on n operand tuples (a[i], b[i], c[i]) -- the
+ * device definition of the function, as the kernels compile it, for comparison with its host definition.  All pointers are host
+ * memory, n words each; b and c may be NULL where the op takes fewer operands.
+ *   form 0  lane form: thread i evaluates tuple i, operands in vector registers.
+ *   form 1  uniform form: wave i evaluates tuple i with wave-uniform operands (the compiler may keep it on the scalar unit);
+ *           nonuniform[i] (may be NULL) is non-zero if a lane's result differed from lane 0's.  Lane form writes zeros there.
+ * For the ops whose last operand is wave-uniform by contract (dot2_i16_uc, mad16_lo_uc, mad16_hi_uc) lane form takes c of the
+ * first tuple of every aligned group of 64: give such groups one value.
+ * The shipped library ASSUMES each primitive's precondition (24-bit operands of mul24, ...): tuples outside it have no defined
+ * result there; the audit twin counts them (GetCheckCounters) and computes the exact result.
+ * AECM_BAD_PARAMETER_ERROR, and nothing is launched, for an op outside [0, DebugOpsCount()), a form other than 0 / 1, n <= 0,
+ * n > 2^20, or a NULL pointer the op's operand count needs.  DebugOpName: the entry's name, NULL outside the table. */
+int32_t WebRtcAecmBatch_DebugOps(int32_t device_id, int32_t op, int32_t form, const int32_t *a, const int32_t *b, const int32_t *c,
+                                 int32_t *out, int32_t *nonuniform, int32_t n);
+int32_t WebRtcAecmBatch_DebugOpsCount(void);
+const char *WebRtcAecmBatch_DebugOpName(int32_t op);
+
 /* Name, CU count and clock of the device the library would use (diagnostics). */
 int32_t WebRtcAecmBatch_DeviceInfo(int32_t device_id, char *name, size_t name_len, int32_t *compute_units,
                                    int32_t *clock_khz);

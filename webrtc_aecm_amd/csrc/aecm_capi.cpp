@@ -942,9 +942,15 @@ int32_t WebRtcAecmBatch_SelfTest(int32_t device_id, int32_t exhaustive, uint64_t
 int32_t WebRtcAecmBatch_GetCheckCounters(int32_t device_id, uint64_t counters[2], int32_t reset) {
     if (!counters) return AECM_NULL_POINTER_ERROR;
     if (hipSetDevice(device_id) != hipSuccess) return AECM_UNSPECIFIED_ERROR;
-    const hipError_t e = aecm::ReadCheckCounters(counters, reset != 0);
+    hipError_t e = aecm::ReadCheckCounters(counters, reset != 0);
     if (e == hipErrorNotSupported) return AECM_UNSUPPORTED_FUNCTION_ERROR;
-    return e == hipSuccess ? 0 : AECM_UNSPECIFIED_ERROR;
+    if (e != hipSuccess) return AECM_UNSPECIFIED_ERROR;
+    uint64_t probe[2] = {0, 0};                            // the ops probe's unit keeps a pair of its own (DebugOps)
+    e = aecm::ReadOpsProbeCheckCounters(probe, reset != 0);
+    if (e != hipSuccess) return AECM_UNSPECIFIED_ERROR;
+    counters[0] += probe[0];
+    counters[1] += probe[1];
+    return 0;
 }
 
 int32_t WebRtcAecmBatch_DebugFft128(int32_t device_id, int16_t *data_host, int32_t *scales_host, int32_t variant,
@@ -971,6 +977,40 @@ int32_t WebRtcAecmBatch_DebugFft128(int32_t device_id, int16_t *data_host, int32
     (void)hipFree(data);
     (void)hipFree(scales);
     (void)hipFree(consts);
+    return rc;
+}
+
+int32_t WebRtcAecmBatch_DebugOpsCount(void) { return aecm::OpsProbeCount(); }
+
+const char *WebRtcAecmBatch_DebugOpName(int32_t op) { return aecm::OpsProbeName(op); }
+
+int32_t WebRtcAecmBatch_DebugOps(int32_t device_id, int32_t op, int32_t form, const int32_t *a, const int32_t *b, const int32_t *c,
+                                 int32_t *out, int32_t *nonuniform, int32_t n) {
+    // everything is refused before a device is touched
+    const int arity = aecm::OpsProbeArity(op);
+    if (arity == 0 || (form != 0 && form != 1) || n <= 0 || n > aecm::kOpsProbeMaxTuples) return AECM_BAD_PARAMETER_ERROR;
+    if (!a || (arity >= 2 && !b) || (arity >= 3 && !c) || !out) return AECM_BAD_PARAMETER_ERROR;
+    if (hipSetDevice(device_id) != hipSuccess) return AECM_UNSPECIFIED_ERROR;
+    const int32_t *host[3] = {a, arity >= 2 ? b : nullptr, arity >= 3 ? c : nullptr};
+    int32_t *dev[3] = {nullptr, nullptr, nullptr}, *out_dev = nullptr;
+    const size_t bytes = (size_t)n * sizeof(int32_t), out_bytes = form == 0 ? bytes : 2 * bytes;
+    bool ok = hipMalloc((void **)&out_dev, out_bytes) == hipSuccess && hipMemset(out_dev, 0, out_bytes) == hipSuccess;
+    for (int k = 0; ok && k < 3; ++k) {
+        if (!host[k]) continue;
+        ok = hipMalloc((void **)&dev[k], bytes) == hipSuccess && hipMemcpy(dev[k], host[k], bytes, hipMemcpyHostToDevice) == hipSuccess;
+    }
+    int32_t rc = AECM_UNSPECIFIED_ERROR;
+    if (ok && aecm::LaunchOpsProbe(op, form, dev[0], dev[1], dev[2], out_dev, n, nullptr) == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+        hipMemcpy(out, out_dev, bytes, hipMemcpyDeviceToHost) == hipSuccess) {
+        rc = 0;
+        if (nonuniform) {
+            if (form == 0) memset(nonuniform, 0, bytes);
+            else if (hipMemcpy(nonuniform, out_dev + n, bytes, hipMemcpyDeviceToHost) != hipSuccess) rc = AECM_UNSPECIFIED_ERROR;
+        }
+    }
+    for (int k = 0; k < 3; ++k)
+        if (dev[k]) (void)hipFree(dev[k]);
+    if (out_dev) (void)hipFree(out_dev);
     return rc;
 }
 

@@ -279,5 +279,19 @@ hipError_t ReadTickSplitCheckCounters(uint64_t counters[2], bool reset);
 //  6 isqrt31 (exhaustive over [0, 2^31) when exhaustive != 0, else 2^24 samples), 7 table upload.
 hipError_t LaunchSelfTest(uint64_t *counters_dev, int exhaustive, const uint32_t *consts_dev, hipStream_t stream);
 
+// Diagnostics, the ops probe (aecm_ops_probe_kernels.hip): entry `op` of aecm_ops_table.inc -- one primitive of aecm_ops.h or
+// plain-integer helper of aecm_wave.h -- on n operand tuples (a_dev, b_dev, c_dev: n words each; those above the op's arity may
+// be null).  form 0: thread i evaluates tuple i, out_dev[n]; form 1: wave w evaluates tuple w with wave-uniform operands,
+// out_dev[2 n] = the results, then per tuple 0 or kOpsProbeNonUniform (a lane disagreed with lane 0).
+// hipErrorInvalidValue, and no launch, for an op or form there is none of, n <= 0 or n > kOpsProbeMaxTuples.
+constexpr int kOpsProbeMaxTuples = 1 << 20;
+constexpr int kOpsProbeNonUniform = 0x5E471E1;
+hipError_t LaunchOpsProbe(int op, int form, const int *a_dev, const int *b_dev, const int *c_dev, int *out_dev, int n, hipStream_t stream);
+int OpsProbeCount();
+const char *OpsProbeName(int op);      // null outside [0, OpsProbeCount())
+int OpsProbeArity(int op);             // 1..3; 0 outside the table
+// The share of aecm_ops_probe_kernels.hip in the audit counters; WebRtcAecmBatch_GetCheckCounters adds it in.  Does not synchronise.
+hipError_t ReadOpsProbeCheckCounters(uint64_t counters[2], bool reset);
+
 }  // namespace aecm
 #endif  // AECM_AMD_KERNELS_H_

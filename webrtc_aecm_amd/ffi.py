@@ -52,6 +52,7 @@ BATCH_SYMBOLS = [
     "WebRtcAecmBatch_SetCleanPipelining", "WebRtcAecmBatch_DescribeLaunchDetailEx",
     "WebRtcAecmBatch_SetRaggedCleanPipelining", "WebRtcAecmBatch_DescribeRaggedLaunchEx2",
     "WebRtcAecmBatch_block_trace_size_bytes", "WebRtcAecmBatch_SetBlockTrace", "WebRtcAecmBatch_DescribeTracedLaunch",
+    "WebRtcAecmBatch_DebugOps", "WebRtcAecmBatch_DebugOpsCount", "WebRtcAecmBatch_DebugOpName",
 ]
 # include/aecm_batch.h: AecmBlockTrace -- the 32-byte record a block writes while a trace is attached (AecmBatch.set_block_trace)
 BLOCK_TRACE_DTYPE = np.dtype([
@@ -260,6 +261,10 @@ def load():
     lib.WebRtcAecmBatch_GetCheckCounters.argtypes = [C.c_int32, vp, C.c_int32]
     lib.WebRtcAecmBatch_SelfTest.argtypes = [C.c_int32, C.c_int32, vp]
     lib.WebRtcAecmBatch_DebugFft128.argtypes = [C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32]
+    lib.WebRtcAecmBatch_DebugOps.argtypes = [C.c_int32, C.c_int32, C.c_int32, vp, vp, vp, vp, vp, C.c_int32]
+    lib.WebRtcAecmBatch_DebugOpsCount.argtypes = []
+    lib.WebRtcAecmBatch_DebugOpName.argtypes = [C.c_int32]
+    lib.WebRtcAecmBatch_DebugOpName.restype = C.c_char_p
     lib.WebRtcAecmBatch_DeviceInfo.argtypes = [C.c_int32, C.c_char_p, C.c_size_t, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.WebRtcAecmBatch_DevicePciBusId.argtypes = [C.c_int32, C.c_char_p, C.c_size_t]
     _lib = lib
@@ -995,6 +1000,32 @@ def debug_fft128(re, im, variant: int, kernel_variant: int = KERNEL_FAST, device
     if rc != 0:
         raise AecmError(rc, "WebRtcAecmBatch_DebugFft128")
     return data[:, :128].copy(), data[:, 128:].copy(), scales
+
+
+def debug_ops_names():
+    """The names of the ops probe's entries, in id order (webrtc_aecm_amd/csrc/aecm_ops_table.inc, as the library was built with it)."""
+    lib = load()
+    return [lib.WebRtcAecmBatch_DebugOpName(k).decode() for k in range(lib.WebRtcAecmBatch_DebugOpsCount())]
+
+
+def debug_ops(op, a, b=None, c=None, form: int = 0, device: int = 0):
+    """One primitive of aecm_ops.h / plain-integer helper of aecm_wave.h on the device, alone (include/aecm_batch.h:
+    WebRtcAecmBatch_DebugOps).  op: an id or a name of debug_ops_names(); a, b, c: int32 arrays of one length (b, c where the
+    op takes them); form 0 = one tuple per lane, 1 = one tuple per wave with wave-uniform operands.  Returns (out, nonuniform)."""
+    lib = load()
+    if isinstance(op, str):
+        op = debug_ops_names().index(op)
+    a = np.ascontiguousarray(a, dtype=np.int32).ravel()
+    ops = [a] + [None if x is None else np.ascontiguousarray(x, dtype=np.int32).ravel() for x in (b, c)]
+    if any(x is not None and x.size != a.size for x in ops):
+        raise ValueError("debug_ops: operand arrays of different lengths")
+    out = np.zeros(a.size, dtype=np.int32)
+    nonuniform = np.zeros(a.size, dtype=np.int32)
+    rc = lib.WebRtcAecmBatch_DebugOps(device, op, form, *[None if x is None else x.ctypes.data for x in ops], out.ctypes.data,
+                                      nonuniform.ctypes.data, a.size)
+    if rc != 0:
+        raise AecmError(rc, "WebRtcAecmBatch_DebugOps")
+    return out, nonuniform
 
 
 def describe_launch_for(num_streams: int, compute_units: int, num_blocks: int, clean: bool = False):
