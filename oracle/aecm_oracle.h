@@ -76,6 +76,12 @@ int aecm_oracle_process_stream(AecmOracle *o, const int16_t *far_s, const int16_
  * WebRtcAecmBatch_GetDigest; see include/aecm_batch.h). */
 void aecm_oracle_digest(const AecmOracle *o, uint32_t digest[ORC_DIGEST_WORDS]);
 
+/* The state as the product's image (webrtc_aecm_amd/csrc/aecm_state.h: vec = 12 fields x 64 lanes, scal = 64 words, hist =
+ * 100 rows x 64 bins) and back: a stream can start from any given state.  Import narrows every word to its member's reference
+ * type; export is its inverse and writes 0 into the words and bits no member owns.  The statistics restart at 0. */
+void aecm_oracle_import_image(AecmOracle *o, const uint32_t *vec, const int32_t *scal, const uint16_t *hist);
+void aecm_oracle_export_image(const AecmOracle *o, uint32_t *vec, int32_t *scal, uint16_t *hist);
+
 void aecm_oracle_get_stats(const AecmOracle *o, uint64_t stats[ORC_STATS]);
 
 /* Exposed for unit tests of the primitives. */

@@ -81,6 +81,10 @@ def oracle_lib():
         lib.aecm_oracle_process_block.argtypes = [C.c_void_p, _i16p, _i16p, C.c_void_p, _i16p]
         lib.aecm_oracle_process_stream.argtypes = [C.c_void_p, _i16p, _i16p, _i16p, C.c_size_t]
         lib.aecm_oracle_digest.argtypes = [C.c_void_p, _u32p]
+        _i32p = np.ctypeslib.ndpointer(dtype=np.int32, flags="C_CONTIGUOUS")
+        _u16p = np.ctypeslib.ndpointer(dtype=np.uint16, flags="C_CONTIGUOUS")
+        lib.aecm_oracle_import_image.argtypes = [C.c_void_p, _u32p, _i32p, _u16p]
+        lib.aecm_oracle_export_image.argtypes = [C.c_void_p, _u32p, _i32p, _u16p]
         lib.aecm_oracle_get_stats.argtypes = [C.c_void_p, np.ctypeslib.ndpointer(dtype=np.uint64, flags="C_CONTIGUOUS")]
         lib.aecm_oracle_sqrt_floor.argtypes = [C.c_int32]
         lib.aecm_oracle_sqrt_floor.restype = C.c_int32
@@ -157,6 +161,30 @@ class OracleStream:
         d = np.zeros(DIGEST_WORDS, dtype=np.uint32)
         self.lib.aecm_oracle_digest(self.h, d)
         return d
+
+    def import_image(self, vec, scal, hist):
+        """Start from a state given as the product's image (webrtc_aecm_amd/csrc/aecm_state.h): vec uint32[12 * 64],
+        scal int32[64], hist uint16[100 * 64]."""
+        vec = np.ascontiguousarray(vec, dtype=np.uint32).reshape(-1)
+        scal = np.ascontiguousarray(scal, dtype=np.int32).reshape(-1)
+        hist = np.ascontiguousarray(hist, dtype=np.uint16).reshape(-1)
+        assert vec.size == 12 * 64 and scal.size == 64 and hist.size == 100 * 64
+        self.lib.aecm_oracle_import_image(self.h, vec, scal, hist)
+        return self
+
+    def export_image(self):
+        """(vec, scal, hist) of the current state; words and bits that no member owns are 0."""
+        vec, scal, hist = np.zeros(12 * 64, np.uint32), np.zeros(64, np.int32), np.zeros(100 * 64, np.uint16)
+        self.lib.aecm_oracle_export_image(self.h, vec, scal, hist)
+        return vec, scal, hist
+
+    def process_blocks(self, far, near, clean=None):
+        """process() with an optional clean near-end input."""
+        if clean is None:
+            return self.process(far, near)
+        far, near = np.ascontiguousarray(far, dtype=np.int16), np.ascontiguousarray(near, dtype=np.int16)
+        return np.concatenate([self.process_block_clean(far[k:k + BLOCK], near[k:k + BLOCK], clean[k:k + BLOCK])
+                               for k in range(0, far.size, BLOCK)]) if far.size else near.copy()
 
     def stats(self):
         """Branch statistics since init (oracle/aecm_oracle.h: ORC_STAT_*) as a dict of block counts."""

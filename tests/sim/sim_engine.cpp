@@ -4,6 +4,7 @@
 // be exercised by the CPU-only tests.  The shipped library links aecm_engine.cpp (HIP) instead.
 #include <string.h>
 
+#include <atomic>
 #include <vector>
 
 #include "wave_sim.h"
@@ -21,6 +22,14 @@ struct SimStore {
     std::vector<uint16_t> hist;
 };
 SimStore *Store(const StatePtrs &st) { return reinterpret_cast<SimStore *>(st.vec); }
+// Every state a launch of this engine leaves is put to the import gate (ValidateStateImage): the gate may refuse none of them.
+std::atomic<long long> g_gate_checked{0}, g_gate_refused{0};
+// sim_engine_inject_next: an image that replaces stream 0's state at this thread's next launch (a session has no import door of
+// its own: the product's is the session batch's); g_last: the store that launch worked on, for sim_engine_last_image.
+thread_local const uint32_t *g_inject_vec = nullptr;
+thread_local const int32_t *g_inject_scal = nullptr;
+thread_local const uint16_t *g_inject_hist = nullptr;
+thread_local SimStore *g_last = nullptr;
 }  // namespace
 
 BatchEngine *BatchEngine::Create(int num_streams, int) {
@@ -76,9 +85,18 @@ bool BatchEngine::Control(int fixed_delay, int nlp, int first, int count) {
 bool BatchEngine::ProcessBlocksHost(const IoView &io, int num_blocks) {
     SimStore *s = Store(st_);
     StatePtrs st{s->vec.data(), s->scal.data(), s->hist.data(), nullptr};
+    if (g_inject_vec) {
+        memcpy(s->vec.data(), g_inject_vec, kVecWordsPerStream * sizeof(uint32_t));
+        memcpy(s->scal.data(), g_inject_scal, kNumScal * sizeof(int32_t));
+        memcpy(s->hist.data(), g_inject_hist, kHistWordsPerStream * sizeof(uint16_t));
+        g_inject_vec = nullptr;
+    }
+    g_last = s;
     for (int i = 0; i < num_streams_; ++i) {
         if (io.near_clean) BlockEngine<SimWave, true>::run_stream(st, io, i, num_blocks);
         else BlockEngine<SimWave, false>::run_stream(st, io, i, num_blocks);
+        ++g_gate_checked;
+        if (ValidateStateImage(&s->vec[(size_t)i * kVecWordsPerStream], &s->scal[(size_t)i * kNumScal], fs_) != nullptr) ++g_gate_refused;
     }
     return true;
 }
@@ -148,6 +166,26 @@ extern "C" int32_t sim_recordings(int n_streams, int n_samples, int fs, int fram
     e->ProcessRecordings(far, near, clean, out, n_samples, frame, n_samples / frame, (int16_t)ms, true, &rc);
     delete e;
     return rc;
+}
+
+// counts[0] = states the engine's launches have left since the last reset, counts[1] = how many of them the import gate refuses.
+extern "C" void sim_engine_gate_counts(long long *counts, int reset) {
+    counts[0] = aecm::g_gate_checked;
+    counts[1] = aecm::g_gate_refused;
+    if (reset) aecm::g_gate_checked = 0, aecm::g_gate_refused = 0;
+}
+
+// The caller's image (it must stay alive until then) becomes stream 0's state at the calling thread's next launch ...
+extern "C" void sim_engine_inject_next(const uint32_t *vec, const int32_t *scal, const uint16_t *hist) {
+    aecm::g_inject_vec = vec, aecm::g_inject_scal = scal, aecm::g_inject_hist = hist;
+}
+// ... and stream 0's state as the calling thread's last launch left it (0 when there was none, or the injection is still pending).
+extern "C" int sim_engine_last_image(uint32_t *vec, int32_t *scal, uint16_t *hist) {
+    if (!aecm::g_last || aecm::g_inject_vec) return 0;
+    memcpy(vec, aecm::g_last->vec.data(), aecm::kVecWordsPerStream * sizeof(uint32_t));
+    memcpy(scal, aecm::g_last->scal.data(), aecm::kNumScal * sizeof(int32_t));
+    memcpy(hist, aecm::g_last->hist.data(), aecm::kHistWordsPerStream * sizeof(uint16_t));
+    return 1;
 }
 
 // C doors onto the product's Session class for the CPU tests (same shapes as the public ABI).

@@ -100,6 +100,20 @@ int sim_fft128(int16_t *re, int16_t *im, int variant) {
     return scale;
 }
 
+// The whole state image (aecm_state.h): vec kNumVec * 64 words, scal 64 words, hist kHistory * 64 uint16.
+void sim_get_image(void *h, uint32_t *vec, int32_t *scal, uint16_t *hist) {
+    SimStream *s = (SimStream *)h;
+    memcpy(vec, s->img.vec.data(), s->img.vec.size() * 4);
+    memcpy(scal, s->img.scal.data(), s->img.scal.size() * 4);
+    memcpy(hist, s->hist.data(), s->hist.size() * 2);
+}
+void sim_set_image(void *h, const uint32_t *vec, const int32_t *scal, const uint16_t *hist) {
+    SimStream *s = (SimStream *)h;
+    memcpy(s->img.vec.data(), vec, s->img.vec.size() * 4);
+    memcpy(s->img.scal.data(), scal, s->img.scal.size() * 4);
+    memcpy(s->hist.data(), hist, s->hist.size() * 2);
+}
+
 void sim_digest(void *h, uint32_t *digest) {
     SimStream *s = (SimStream *)h;
     ComputeDigest(s->img.vec.data(), s->img.scal.data(), s->hist.data(), digest);

@@ -163,7 +163,8 @@ int64_t FirstDifference(const uint8_t *a, const uint8_t *b) {
     return -1;
 }
 
-// A snapshot every rule accepts: a session as WebRtcAecm_Init leaves its wrapper, a core state of zeros at the rate fs.
+// A snapshot every rule accepts: a session as WebRtcAecm_Init leaves its wrapper, a core state of zeros at the rate fs with the
+// suppression-gain parameters of echoMode 3 (the gate admits set_config's five tuples only).
 void ValidBlob(uint8_t *p, int fs, const int32_t *flow_words) {
     memset(p, 0, kBlobBytes);
     const uint32_t header[8] = {kSessionMagic, kSessionVersion, (uint32_t)fs, 0u, (uint32_t)kFlowWords, (uint32_t)kFlowFarRing, (uint32_t)kSessionOutTail,
@@ -173,6 +174,11 @@ void ValidBlob(uint8_t *p, int fs, const int32_t *flow_words) {
     memcpy(p + 32, core, sizeof core);
     const int32_t mult = fs / 8000;
     memcpy(p + 64 + kVecWordsPerStream * 4 + S_MULT * 4, &mult, 4);
+    SupGainParams sg;
+    SupGainParamsOfMode(3, &sg);
+    const int32_t sg_words[4] = {sg.a, sg.d, sg.dab, sg.dbd};
+    static_assert(S_SG_D == S_SG_A + 1 && S_SG_DAB == S_SG_A + 2 && S_SG_DBD == S_SG_A + 3, "the four words are neighbours");
+    memcpy(p + 64 + kVecWordsPerStream * 4 + S_SG_A * 4, sg_words, sizeof sg_words);
     int32_t words[kFlowWords];
     FlowInit(words);
     memcpy(p + 16192, flow_words ? flow_words : words, sizeof words);

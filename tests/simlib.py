@@ -62,6 +62,8 @@ def lib():
         l.sim_get_echo_path.argtypes = [C.c_void_p, _i16p]
         l.sim_process.argtypes = [C.c_void_p, _i16p, _i16p, C.c_void_p, _i16p, C.c_int]
         l.sim_digest.argtypes = [C.c_void_p, _u32p]
+        l.sim_get_image.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        l.sim_set_image.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.sim_roles_launch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.sim_fft128.argtypes = [_i16p, _i16p, C.c_int]
         l.sim_constants.argtypes = [_u32p, _u32p, _u32p]
@@ -75,12 +77,36 @@ def lib():
         l.simsession_set_config.argtypes = [C.c_void_p, C.c_int16, C.c_int16]
         l.simsession_init_echo_path.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
         l.simsession_get_echo_path.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+        l.sim_engine_inject_next.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        l.sim_engine_last_image.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         l.sim_flow_fuzz.restype = C.c_int64
         l.sim_flow_fuzz.argtypes = [C.c_uint64, C.c_int, C.c_int, C.c_int, C.c_uint32, C.POINTER(C.c_int64)]
         l.sim_flow_tolerance_check.restype = C.c_int
         l.sim_div_magic_check.restype = C.c_int
         _lib = l
     return _lib
+
+
+def engine_gate_counts(reset=False):
+    """(states the simulated engine's launches have left since the last reset -- every launch of every SimSession and of
+    sim_recordings --, how many of them the import gate refuses)."""
+    counts = (C.c_longlong * 2)()
+    lib().sim_engine_gate_counts(counts, 1 if reset else 0)
+    return int(counts[0]), int(counts[1])
+
+
+def engine_inject_next(vec, scal, hist):
+    """The image becomes the state of the stream that this thread's next simulated launch runs (a SimSession's core state: call it
+    right before the session's call).  The three arrays must be contiguous, of the image's types, and stay alive until then."""
+    for a, t, n in ((vec, np.uint32, 12 * 64), (scal, np.int32, 64), (hist, np.uint16, 100 * 64)):
+        assert a.dtype == t and a.size == n and a.flags.c_contiguous
+    lib().sim_engine_inject_next(vec.ctypes.data, scal.ctypes.data, hist.ctypes.data)
+
+
+def engine_last_image():
+    """(vec, scal, hist) as this thread's last simulated launch left them; None when an injection is still pending."""
+    vec, scal, hist = np.zeros(12 * 64, np.uint32), np.zeros(64, np.int32), np.zeros(100 * 64, np.uint16)
+    return (vec, scal, hist) if lib().sim_engine_last_image(vec.ctypes.data, scal.ctypes.data, hist.ctypes.data) else None
 
 
 def flow_fuzz(seed, fs, n_ticks, scenario, start_pos=0):
@@ -121,6 +147,17 @@ class SimStream:
         d = np.zeros(24, dtype=np.uint32)
         self.lib.sim_digest(self.h, d)
         return d
+
+    def image(self):
+        """(vec uint32[12 * 64], scal int32[64], hist uint16[100 * 64]): the whole state (webrtc_aecm_amd/csrc/aecm_state.h)."""
+        vec, scal, hist = np.zeros(12 * 64, np.uint32), np.zeros(64, np.int32), np.zeros(100 * 64, np.uint16)
+        self.lib.sim_get_image(self.h, vec.ctypes.data, scal.ctypes.data, hist.ctypes.data)
+        return vec, scal, hist
+
+    def set_image(self, vec, scal, hist):
+        vec, scal, hist = (np.ascontiguousarray(a, dtype=t).reshape(-1) for a, t in ((vec, np.uint32), (scal, np.int32), (hist, np.uint16)))
+        assert vec.size == 12 * 64 and scal.size == 64 and hist.size == 100 * 64
+        self.lib.sim_set_image(self.h, vec.ctypes.data, scal.ctypes.data, hist.ctypes.data)
 
     def init_echo_path(self, path):
         self.lib.sim_set_echo_path(self.h, np.ascontiguousarray(path, dtype=np.int16))

@@ -44,22 +44,15 @@ inline int BitRev6(int t) {
 
 bool ApplyConfig(int32_t *scal, int cng_mode, int echo_mode) {
     if (cng_mode != 0 && cng_mode != 1) return false;
-    if (echo_mode < 0 || echo_mode > 4) return false;
-    // SUPGAIN_DEFAULT / ERROR_PARAM_A / _B / _D (reference aecm/aecm_defines.h:62-68), scaled per echoMode
-    int g = 256, a = 3072, b = 1536, d = 256;
-    if (echo_mode < 3) {
-        const int s = 3 - echo_mode;
-        g >>= s; a >>= s; b >>= s; d >>= s;
-    } else if (echo_mode == 4) {
-        g <<= 1; a <<= 1; b <<= 1; d <<= 1;
-    }
+    SupGainParams p;                  // aecm_state_check.h: the five tuples the import gate admits are these
+    if (!SupGainParamsOfMode(echo_mode, &p)) return false;
     scal[S_CNG] = cng_mode;
-    scal[S_SUPGAIN] = g;
-    scal[S_SUPGAIN_OLD] = g;
-    scal[S_SG_A] = a;
-    scal[S_SG_D] = d;
-    scal[S_SG_DAB] = a - b;
-    scal[S_SG_DBD] = b - d;
+    scal[S_SUPGAIN] = p.gain;
+    scal[S_SUPGAIN_OLD] = p.gain;
+    scal[S_SG_A] = p.a;
+    scal[S_SG_D] = p.d;
+    scal[S_SG_DAB] = p.dab;
+    scal[S_SG_DBD] = p.dbd;
     return true;
 }
 
@@ -70,12 +63,7 @@ void ApplyControl(int32_t *scal, int fixed_delay, int nlp_flag) {
 
 const char *ValidateStateImage(const uint32_t *vec, const int32_t *scal, int fs) {
     // the rules themselves: aecm_state_check.h (shared with the device-side validation of the bulk import)
-    for (int f = 0; f < kNumScalUsed; ++f)
-        if (const int d = ScalarFieldDefect(f, scal[f], fs)) return StateDefectName(d);
-    for (int t = 0; t < kLanes; ++t)
-        if (const int d = LaneWordsDefect(t, vec[V_NEARFILT * kLanes + t], vec[V_NOISE * kLanes + t], vec[V_M01 * kLanes + t]))
-            return StateDefectName(d);
-    return nullptr;
+    return StateDefectName(StateImageDefect(vec, scal, fs));
 }
 
 void SetEchoPath(uint32_t *vec, int32_t *scal, const int16_t path[kBins]) {

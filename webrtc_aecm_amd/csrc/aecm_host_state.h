@@ -39,7 +39,8 @@ void GetEchoPath(const uint32_t *vec, const int32_t *scal, int16_t path[kBins]);
 // Is this (vec, scal) image one the kernels may run on?  Everything the block kernel uses as an index, a lane number or
 // a shift count, and every value range its cheaper-instruction shortcuts rely on (aecm_ops.h: as_i16 / as_nonneg /
 // mul24 / checked_shift31 claims that hold for every state the algorithm itself can reach): int16 fields inside int16,
-// supGain >= 0, Q domains <= 14, counters and flags in their ranges.  fs: the rate the image claims (mult * 8000).
+// supGain >= 0, the four supGainErrParam words one of set_config's tuples, Q domains <= 14, binary-spectrum thresholds >= 0, counters
+// and flags in their ranges (the rules: aecm_state_check.h).  fs: the rate the image claims (mult * 8000).
 // Used by WebRtcAecmBatch_ImportState; returns the name of the first offending field, or nullptr when the image is sane.
 const char *ValidateStateImage(const uint32_t *vec, const int32_t *scal, int fs);
 

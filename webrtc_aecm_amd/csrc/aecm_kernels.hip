@@ -117,7 +117,8 @@ __global__ __launch_bounds__(256) void aecm_gather_states_kernel(StatePtrs st, i
 }
 
 // result[0] = index of the first blob that may not be run on (atomicMin; the caller presets 0xffffffff), result[1] |= 1 when a
-// blob of another sampling rate than fs_batch is among them.  64 threads per blob: thread t checks scalar field t and lane t.
+// blob of another sampling rate than fs_batch is among them.  64 threads per blob: thread t checks scalar field t and lane t,
+// thread 0 the rule over the four supGainErrParam words as well.
 __global__ __launch_bounds__(64) void aecm_validate_states_kernel(const uint32_t *blobs, int fs_batch, uint32_t *result) {
     const uint32_t *blob = blobs + (int64_t)blockIdx.x * kBlobWords;
     SnapshotHeader h;
@@ -126,7 +127,8 @@ __global__ __launch_bounds__(64) void aecm_validate_states_kernel(const uint32_t
     const uint32_t *vec = blob + kBlobHeaderWords, *scal = vec + kBlobVecWords;
     int defect = SnapshotHeaderOk(h) ? 0 : 1;
     if (!defect) defect = ScalarFieldDefect(t, (int32_t)scal[t], (int)h.fs);
-    if (!defect) defect = LaneWordsDefect(t, vec[V_NEARFILT * kLanes + t], vec[V_NOISE * kLanes + t], vec[V_M01 * kLanes + t]);
+    if (!defect && t == 0) defect = SupGainErrParamsDefect((int32_t)scal[S_SG_A], (int32_t)scal[S_SG_D], (int32_t)scal[S_SG_DAB], (int32_t)scal[S_SG_DBD]);
+    if (!defect) defect = LaneWordsDefect(t, vec[V_NEARFILT * kLanes + t], vec[V_NOISE * kLanes + t], vec[V_MEAN * kLanes + t], vec[V_M01 * kLanes + t]);
     if (__ballot(defect != 0) != 0 && t == 0) atomicMin(result, blockIdx.x);
     if (t == 0 && !defect && (int)h.fs != fs_batch) atomicOr(result + 1, 1u);
 }

@@ -181,8 +181,8 @@ AECM_FLOW_HD uint32_t SessionBlobWord(const void *blob, size_t byte_offset, int 
 }
 
 // May this snapshot be imported into an object of rate fs_object?  Every rule of SessionBatch::ImportSession, as the work of
-// kLanes workers: worker tid checks the headers, scalar field tid and lane tid of the core state, worker 0 the wrapper words as
-// well.  The snapshot may be run on when every worker returns 0.  any_rate: ImportSessionAnyRate's rule for the rate.
+// kLanes workers: worker tid checks the headers, scalar field tid and lane tid of the core state, worker 0 the wrapper words and
+// the core state's rules over several fields as well.  The snapshot may be run on when every worker returns 0.  any_rate: ImportSessionAnyRate's rule for the rate.
 enum SessionBlobDefectCode : int {
     kSessionDefectNone = 0, kSessionDefectHeader = 1, kSessionDefectRate = 2, kSessionDefectCoreHeader = 3,
     kSessionDefectFlow = 0x100,          // + FlowStateDefect's 1-based field
@@ -209,8 +209,12 @@ AECM_FLOW_HD int SessionBlobDefect(const void *blob, int fs_object, bool any_rat
     if (!SnapshotHeaderOk(core) || core.fs != h.fs) return kSessionDefectCoreHeader;
     const size_t vec_at = at.state + kStateHeaderBytes, scal_at = vec_at + kVecWordsPerStream * 4;
     if (const int d = ScalarFieldDefect(tid, (int32_t)SessionBlobWord(blob, scal_at, tid), (int)core.fs)) return kSessionDefectCore + d;
+    if (tid == 0)
+        if (const int d = SupGainErrParamsDefect((int32_t)SessionBlobWord(blob, scal_at, S_SG_A), (int32_t)SessionBlobWord(blob, scal_at, S_SG_D),
+                                                 (int32_t)SessionBlobWord(blob, scal_at, S_SG_DAB), (int32_t)SessionBlobWord(blob, scal_at, S_SG_DBD)))
+            return kSessionDefectCore + d;
     if (const int d = LaneWordsDefect(tid, SessionBlobWord(blob, vec_at, V_NEARFILT * kLanes + tid), SessionBlobWord(blob, vec_at, V_NOISE * kLanes + tid),
-                                      SessionBlobWord(blob, vec_at, V_M01 * kLanes + tid)))
+                                      SessionBlobWord(blob, vec_at, V_MEAN * kLanes + tid), SessionBlobWord(blob, vec_at, V_M01 * kLanes + tid)))
         return kSessionDefectCore + d;
     return 0;
 }

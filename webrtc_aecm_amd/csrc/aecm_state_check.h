@@ -1,11 +1,14 @@
 // Is a stream's state image (aecm_state.h) one the kernels may run on?  ONE statement of the rules, for the host
 // (ValidateStateImage, aecm_host_state.cpp: WebRtcAecmBatch_ImportState of a single blob) and for the device (the validation
-// pass of the bulk import, aecm_kernels.hip, where thread t of a workgroup checks scalar field t and lane t of the lane words).
+// pass of the bulk import, aecm_kernels.hip, where thread t of a workgroup checks scalar field t and lane t of the lane words,
+// and thread 0 the rules that relate several fields).
 //
-// Checked: everything the block kernel uses as an index, a lane number or a shift count, and every value range its
-// cheaper-instruction shortcuts rely on (aecm_ops.h: as_i16 / as_nonneg / mul24 / checked_shift31 claims that hold for every
-// state the algorithm itself can reach): int16 members inside int16, supGain >= 0, Q domains <= 14, counters and flags in
-// their ranges.  A blob no run of the algorithm can produce is refused, not run.
+// What the gate promises, and what tests/test_state_injection.py holds it to: every admitted state runs with every claim of
+// aecm_ops.h holding (as_i16 / as_nonneg / mul24 / checked_shift31) and equals the oracle, block for block and word for word.
+// That takes: everything the block kernel uses as an index, a lane number or a shift count inside its range, int16 members inside
+// int16, supGain >= 0 and the four supGainErrParam words one of set_config's five tuples (the argument for supGain >= 0 rests on
+// them), Q domains <= 14, the binary-spectrum thresholds >= 0, counters and flags in their ranges.  A blob no run of the algorithm
+// can produce is refused, not run.
 #ifndef AECM_AMD_STATE_CHECK_H_
 #define AECM_AMD_STATE_CHECK_H_
 
@@ -24,7 +27,7 @@ namespace aecm {
 enum StateDefect : int {
     kDefectNone = 0, kDefectMult, kDefectHistPos, kDefectLastDelay, kDefectFixedDelay, kDefectStartup, kDefectQDomain, kDefectCng,
     kDefectFlag, kDefectNoiseCtr64, kDefectInt16Member, kDefectSupGain, kDefectSeed, kDefectDelayProbability, kDefectNoise64,
-    kDefectFarQDomains, kDefectNoise, kDefectMeanBitCounts, kNumStateDefects
+    kDefectFarQDomains, kDefectNoise, kDefectMeanBitCounts, kDefectSupGainErrParams, kDefectMeanSpectrum, kNumStateDefects
 };
 
 AECM_CHECK_HD const char *StateDefectName(int d) {
@@ -46,6 +49,8 @@ AECM_CHECK_HD const char *StateDefectName(int d) {
         case kDefectFarQDomains: return "far_q_domains";
         case kDefectNoise: return "noiseEst";
         case kDefectMeanBitCounts: return "mean_bit_counts";
+        case kDefectSupGainErrParams: return "supGainErrParam";
+        case kDefectMeanSpectrum: return "mean_spectrum";
         default: return nullptr;
     }
 }
@@ -80,12 +85,59 @@ AECM_CHECK_HD int ScalarFieldDefect(int f, int32_t v, int fs) {
     }
 }
 
-// Lane t of the lane-vector words V_NEARFILT, V_NOISE, V_M01.
-AECM_CHECK_HD int LaneWordsDefect(int t, uint32_t near_filt_word, uint32_t noise_word, uint32_t m01_word) {
+// The suppression-gain configuration of an echoMode (0..4): SUPGAIN_DEFAULT and SUPGAIN_ERROR_PARAM_A / _B / _D (reference
+// aecm/aecm_defines.h:62-68) as WebRtcAecm_set_config scales them (echo_control_mobile.cc:424-476): supGain = supGainOld = gain,
+// supGainErrParamA = a, supGainErrParamD = d, supGainErrParamDiffAB = a - b, supGainErrParamDiffBD = b - d.
+struct SupGainParams {
+    int gain, a, d, dab, dbd;
+};
+AECM_CHECK_HD bool SupGainParamsOfMode(int echo_mode, SupGainParams *p) {
+    if (echo_mode < 0 || echo_mode > 4) return false;
+    int g = 256, a = 3072, b = 1536, d = 256;
+    if (echo_mode < 3) {
+        const int s = 3 - echo_mode;
+        g >>= s; a >>= s; b >>= s; d >>= s;
+    } else if (echo_mode == 4) {
+        g <<= 1; a <<= 1; b <<= 1; d <<= 1;
+    }
+    *p = SupGainParams{g, a, d, a - b, b - d};
+    return true;
+}
+
+// A rule over several fields: S_SG_A, S_SG_D, S_SG_DAB, S_SG_DBD are written by set_config alone and only as one of its five
+// tuples (echo_control_mobile.cc:424-476; InitCore leaves the tuple of echoMode 3, aecm_core.cc:451-454).  S_SUPGAIN >= 0 --
+// as_nonneg in the block loop -- holds because CalcSuppressionGain's targets are non-negative (aecm_core.cc:1000-1052:
+// A - DiffAB * dE / 200 >= A / 2 for dE < 200, D + DiffBD * (400 - dE) / 200 >= D), which is true of these tuples and of no others in general.
+AECM_CHECK_HD int SupGainErrParamsDefect(int32_t a, int32_t d, int32_t dab, int32_t dbd) {
+    for (int mode = 0; mode <= 4; ++mode) {
+        SupGainParams p;
+        SupGainParamsOfMode(mode, &p);
+        if (a == p.a && d == p.d && dab == p.dab && dbd == p.dbd) return 0;
+    }
+    return kDefectSupGainErrParams;
+}
+
+// Lane t of the lane-vector words V_NEARFILT, V_NOISE, V_MEAN, V_M01.
+AECM_CHECK_HD int LaneWordsDefect(int t, uint32_t near_filt_word, uint32_t noise_word, uint32_t mean_word, uint32_t m01_word) {
     if (((near_filt_word >> 22) & 31u) > 14u || (t < kSecondPass && (near_filt_word >> 27) > 14u)) return kDefectFarQDomains;
     if ((int32_t)noise_word < 0) return kDefectNoise;
+    // A threshold of the binary spectra (mean_far_spectrum / mean_near_spectrum) starts at 0 (delay_estimator_wrapper.cc:208-225,
+    // 338-355) and only ever moves a fraction of the way towards a spectrum value spectrum << (15 - q) < 2^31 (BinarySpectrumFix,
+    // :92-125; WebRtc_MeanEstimatorFix, delay_estimator.cc:690): it is never negative, and new_value - mean cannot overflow --
+    // which the reference leaves undefined and the kernel's and the oracle's wrapping arithmetic resolve differently.
+    if ((int32_t)mean_word < 0) return kDefectMeanSpectrum;
     // no slot t + 64 for t >= 36: that half stays 0
     if ((m01_word & 0xffffu) > (32u << 9) || (m01_word >> 16) > (t < kSecondPass ? (32u << 9) : 0u)) return kDefectMeanBitCounts;
+    return 0;
+}
+
+// The whole image, in the order every caller reports: scalar fields by index, the rules over several fields, lanes by index.
+AECM_CHECK_HD int StateImageDefect(const uint32_t *vec, const int32_t *scal, int fs) {
+    for (int f = 0; f < kNumScalUsed; ++f)
+        if (const int d = ScalarFieldDefect(f, scal[f], fs)) return d;
+    if (const int d = SupGainErrParamsDefect(scal[S_SG_A], scal[S_SG_D], scal[S_SG_DAB], scal[S_SG_DBD])) return d;
+    for (int t = 0; t < kLanes; ++t)
+        if (const int d = LaneWordsDefect(t, vec[V_NEARFILT * kLanes + t], vec[V_NOISE * kLanes + t], vec[V_MEAN * kLanes + t], vec[V_M01 * kLanes + t])) return d;
     return 0;
 }
 
