@@ -102,7 +102,7 @@ struct CallsSide : DeviceSide {
                     for (int j = 0; j < kFlowFrame; ++j) far_frames[(q.frm_pos + (uint32_t)j) & (kFlowFarFrameRing - 1)] = frames[f][j];
                 }
             }
-            // append (TickCallsBlockIo::ready, or the branch of a call without blocks)
+            // append (TickBlockIo::ready, or the branch of a call without blocks)
             for (int j = 0; j < n; ++j) {
                 if (j < p.far[0].count) far_ring[(p.far[0].pos + (uint32_t)j) & mask] = fin[j];
                 near_ring[(npos + (uint32_t)j) & mask] = nin[j];

@@ -23,9 +23,7 @@
 // section 9).  A translation unit of its own so that it compiles next to the tick kernels' unit (aecm_kernels.hip) and its
 // flags can differ from theirs.
 #define AECM_TABLE_ATTR __device__
-#if defined(AECM_CHECKED)
-#define g_aecm_check_fail g_aecm_check_fail_blocks      // device symbols are per translation unit (no relocatable device code)
-#endif
+#define AECM_CHECK_UNIT blocks      // (aecm_kernel_common.h: the unit's pair of audit counters)
 #include <type_traits>
 
 #include "aecm_kernel_common.h"
@@ -33,28 +31,8 @@
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail_blocks[2];
-#endif
 // This unit's share of the audit counters (see ReadCheckCounters in aecm_kernels.hip).
-hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset) {
-#if defined(AECM_CHECKED)
-    unsigned long long host[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail_blocks), sizeof host);
-    if (e != hipSuccess) return e;
-    counters[0] = host[0];
-    counters[1] = host[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail_blocks), zero, sizeof zero);
-    }
-    return e;
-#else
-    (void)counters;
-    (void)reset;
-    return hipErrorNotSupported;
-#endif
-}
+AECM_DEFINE_CHECK_COUNTERS(ReadBlockKernelCheckCounters)
 
 // (The occupancy these kernels are built for -- AECM_WAVES_PER_EU, AECM_ROTATION_WAVES_PER_EU -- and the queue's claim / wait /
 // publish steps live in aecm_block_queue.h, which the traced kernels' unit, aecm_trace_kernels.hip, includes too.)

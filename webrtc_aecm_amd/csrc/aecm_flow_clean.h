@@ -23,7 +23,7 @@
 namespace aecm {
 
 constexpr int kFlowNoClean = 16;                    // = SessionBatch::kNoClean = AECM_SESSION_NO_CLEAN
-constexpr int kFlowSplitGroup = 4;                  // sessions per workgroup of the tick kernels (aecm_kernels.hip: kTickFlowWaves)
+constexpr int kFlowSplitGroup = 4;                  // sessions per workgroup of the tick kernels (aecm_tick_unit.h: kTickFlowWaves)
 
 // Where the list of the sessions without a clean input starts behind clean_count entries of the other: the next multiple of
 // kFlowSplitGroup, so that no workgroup of the tick kernel serves sessions of both kinds.

@@ -1,6 +1,18 @@
-// Device-side pieces shared by the translation units that hold kernels (aecm_block_kernels.hip, aecm_kernels.hip).
+// Device-side pieces shared by the translation units that hold wave-level kernels: the block kernels and their traced twins
+// (aecm_block_kernels.hip, aecm_trace_kernels.hip; through aecm_block_queue.h as well), the ops probe (aecm_ops_probe_kernels.hip),
+// aecm_kernels.hip and the tick units (aecm_tick_calls_kernels.hip, aecm_tick_packets_kernels.hip, aecm_tick_split_kernels.hip).
 #ifndef AECM_AMD_KERNEL_COMMON_H_
 #define AECM_AMD_KERNEL_COMMON_H_
+
+// The audit counters of the -DAECM_CHECKED build (aecm_ops.h counts into g_aecm_check_fail).  Device symbols are per translation
+// unit (no relocatable device code), so every unit keeps a pair of its own: a unit names itself ONCE, ahead of this header,
+//   #define AECM_CHECK_UNIT tick_calls
+// and its pair is g_aecm_check_fail_tick_calls.  (aecm_kernels.hip names nothing: its pair is g_aecm_check_fail itself.)
+#if defined(AECM_CHECKED) && defined(AECM_CHECK_UNIT)
+#define AECM_CHECK_CAT_(a, b) a##b
+#define AECM_CHECK_CAT(a, b) AECM_CHECK_CAT_(a, b)
+#define g_aecm_check_fail AECM_CHECK_CAT(g_aecm_check_fail_, AECM_CHECK_UNIT)
+#endif
 
 #include "aecm_kernels.h"
 #include "aecm_tables.h"
@@ -33,6 +45,29 @@ __device__ __forceinline__ void FillLdsTables(const uint32_t *consts) {
     }
     __syncthreads();
 }
+
+// AECM_DEFINE_CHECK_COUNTERS(Reader), once per unit, inside namespace aecm: the unit's pair of audit counters and the host
+// function `hipError_t Reader(uint64_t counters[2], bool reset)` (declared in aecm_kernels.h) that reads it, and zeroes it on
+// request.  It does not synchronise; hipErrorNotSupported in the shipped build.
+#if defined(AECM_CHECKED)
+#define AECM_DEFINE_CHECK_COUNTERS(Reader)                                                           \
+    __device__ unsigned long long g_aecm_check_fail[2];                                              \
+    hipError_t Reader(uint64_t counters[2], bool reset) {                                            \
+        unsigned long long host[2] = {0, 0};                                                         \
+        hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail), sizeof host);        \
+        if (e != hipSuccess) return e;                                                               \
+        counters[0] = host[0];                                                                       \
+        counters[1] = host[1];                                                                       \
+        if (reset) {                                                                                 \
+            const unsigned long long zero[2] = {0, 0};                                               \
+            e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail), zero, sizeof zero);                 \
+        }                                                                                            \
+        return e;                                                                                    \
+    }
+#else
+#define AECM_DEFINE_CHECK_COUNTERS(Reader) \
+    hipError_t Reader(uint64_t *, bool) { return hipErrorNotSupported; }
+#endif
 
 }  // namespace aecm
 

@@ -8,30 +8,24 @@
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail[2];
-#endif
-// Audit counters of the -DAECM_CHECKED build (aecm_ops.h); hipErrorNotSupported in the shipped build.
+AECM_DEFINE_CHECK_COUNTERS(ReadThisUnitCheckCounters)      // (used below only)
+// Audit counters of the -DAECM_CHECKED build (aecm_ops.h): this unit's pair, the block kernels' and the traced block kernels',
+// behind everything the device still has to do; hipErrorNotSupported in the shipped build.
 hipError_t ReadCheckCounters(uint64_t counters[2], bool reset) {
 #if defined(AECM_CHECKED)
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return e;
-    unsigned long long host[2] = {0, 0};
-    e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail), sizeof host);
-    if (e != hipSuccess) return e;
-    uint64_t blocks[2] = {0, 0};
-    e = ReadBlockKernelCheckCounters(blocks, reset);       // the block kernels' unit keeps its own pair
-    if (e != hipSuccess) return e;
-    uint64_t traced[2] = {0, 0};
-    e = ReadTraceKernelCheckCounters(traced, reset);       // and so does the traced block kernels'
-    if (e != hipSuccess) return e;
-    counters[0] = host[0] + blocks[0] + traced[0];
-    counters[1] = host[1] + blocks[1] + traced[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail), zero, sizeof zero);
+    uint64_t sum[2] = {0, 0};
+    for (const auto read : {ReadThisUnitCheckCounters, ReadBlockKernelCheckCounters, ReadTraceKernelCheckCounters}) {
+        uint64_t share[2] = {0, 0};
+        e = read(share, reset);
+        if (e != hipSuccess) return e;
+        sum[0] += share[0];
+        sum[1] += share[1];
     }
-    return e;
+    counters[0] = sum[0];
+    counters[1] = sum[1];
+    return hipSuccess;
 #else
     (void)counters;
     (void)reset;
@@ -209,28 +203,7 @@ hipError_t LaunchAssembleOutput(const int16_t *blocks, int64_t blocks_stride, co
 }
 
 // ---- device-resident session machinery (aecm_flow_plan.h) ---------------------------------------------
-template <bool kHasClean, class Append>
-struct TickFlowBlockIo {
-    using E = BlockEngine<Gfx950Wave<true, true, true>, kHasClean>;
-    using Regs = typename E::Regs;
-    const int16_t *far_src;          // the far ring itself (direct ticks) or the framed far stream
-    const int16_t *nr, *cr;          // near / clean rings of this session
-    int16_t *out_row;                // output stream ring
-    int far_mask, mask;
-    unsigned far_pos, near_pos, out_pos;      // positions of the tick's first block in far_src / the near rings / the output ring
-    const Append &append;            // the tick's samples -> rings
-    __device__ __forceinline__ int far(const Regs &r, int b) const { return far_src[(far_pos + b * kBlock + r.lane) & far_mask]; }
-    __device__ __forceinline__ int near(const Regs &r, int b) const { return nr[(near_pos + b * kBlock + r.lane) & mask]; }
-    __device__ __forceinline__ int clean(const Regs &r, int b) const { return cr[(near_pos + b * kBlock + r.lane) & mask]; }
-    __device__ __forceinline__ void out(const Regs &r, int b, int v) const { out_row[(out_pos + b * kBlock + r.brev) & mask] = (int16_t)v; }
-    // Called by the engine after it has issued its state loads: the tick's samples go into the rings HERE (8-byte stores
-    // that, placed ahead of those loads, would make the compiler fetch the scalar half of the state with vector loads: for
-    // all it knows they could alias it), then this wave's fetches below must see this wave's stores.
-    __device__ __forceinline__ void ready() const {
-        append();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
-};
+#include "aecm_tick_unit.h"      // TickBlockIo, the build's choices for the tick kernels, AECM_TICK_LIVE_SESSION
 
 // One lane per session: the tick's session machinery for 64 sessions per wavefront.
 __global__ __launch_bounds__(256)
@@ -250,98 +223,32 @@ void aecm_flow_plan_kernel(TickFlowIo fio, int n, unsigned near_pos, int n_strea
     for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
 }
 
-// The same for a tick in which sessions may sit out (kFlowIdle) or may have done so before (aecm_flow_plan.h: F_NEAR_LAG).
-// An idle lane adds the tick to its session's lag and touches nothing else.  A live lane brings its session back in step
-// first (FlowResync: the pending near-end samples, fewer than one block, move behind the object's position -- rare, and at
-// most 63 samples per ring) and then plans the tick as above.  With a live list to fill (sp.live), the lane also writes its
-// session's id to its slot of the list: wave ballot + mbcnt within the wavefront, LDS across the workgroup's four
-// wavefronts, the host's prefix count (sp.block_base) across workgroups -- ascending ids, no atomics.
+// The same for a tick in which sessions may sit out (kFlowIdle) or may have done so before: idle lanes count their session's lag,
+// returning ones are brought back in step, and with a live list to fill (sp.live) a calling lane writes its session's id to its
+// slot of it.  The text is shared with the other planning kernels (aecm_flow_plan_list.inc, aecm_flow_plan_lane.inc).
 static_assert(kFlowPlanBlock == 256, "the planning kernels run 256 lanes per workgroup");
 __global__ __launch_bounds__(256)
 void aecm_flow_plan_sparse_kernel(TickFlowIo fio, TickSparseIo sp, int n, unsigned near_pos, int n_streams) {
     __shared__ uint32_t wave_counts[kFlowPlanBlock / 64];
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    const bool in_range = s < n_streams;
-    const int flags = !in_range ? kFlowIdle : fio.flags_per_session ? (int)fio.flags_per_session[s] : fio.flags;
-    const bool live = (flags & kFlowIdle) == 0;
-    if (sp.live) {                                                  // (uniform: a kernel argument)
-        const uint64_t ballot = __ballot(live);
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        if (lane == 0) wave_counts[wave] = (uint32_t)__builtin_popcountll(ballot);
-        __syncthreads();
-        const uint32_t slot = FlowLiveSlot(sp.block_base[blockIdx.x], wave_counts, wave, ballot, lane);
-        if (live && slot < (uint32_t)n_streams) sp.live[slot] = (uint32_t)s;      // (the list holds n_streams entries)
-    }
-    if (!in_range) return;
-    int32_t *lag = fio.state + (size_t)F_NEAR_LAG * n_streams + s;
-    if (!live) {
-        *lag = FlowIdleTick(FlowIdleTick(*lag, sp.deferred_lag), n);
-        return;
-    }
-    FlowRegs r;
-    for (int k = 0; k < kFlowFieldsUsed; ++k) r.v[k] = fio.state[(size_t)k * n_streams + s];
-    r.v[F_NEAR_LAG] = FlowIdleTick(r.v[F_NEAR_LAG], sp.deferred_lag);
-    if (r.v[F_NEAR_LAG] != 0) {
-        FlowNearMove m;
-        FlowResync(r, near_pos, m);
-        const uint32_t mask = (uint32_t)sp.ring_len - 1u;
-        FlowMoveNear(sp.near_ring + (size_t)s * sp.ring_len, mask, m);
-        if (sp.clean_ring) FlowMoveNear(sp.clean_ring + (size_t)s * sp.ring_len, mask, m);
-    }
-    const int ms = fio.ms_per_session ? (int)fio.ms_per_session[s] : fio.ms;
-    FlowPlan p;
-    FlowTick(r, fio.fs, n, ms, flags, near_pos, p);
-    for (int k = 0; k < kFlowFieldsUsed; ++k) fio.state[(size_t)k * n_streams + s] = r.v[k];
-    int32_t w[kFlowPlanWords];
-    FlowPackPlan(p, w);
-    int4 *dst = reinterpret_cast<int4 *>(fio.plans + (size_t)s * kFlowPlanWords);
-    for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+#define AECM_FLOW_PLAN_LIST_GUARD if (sp.live)
+#include "aecm_flow_plan_list.inc"
+#define AECM_FLOW_PLAN_IDLE_SAMPLES n
+#define AECM_FLOW_PLAN_TICK(p) FlowTick(r, fio.fs, n, ms, flags, near_pos, p)
+#include "aecm_flow_plan_lane.inc"
 }
 
 // The planning launch of a tick of an object of mixed rates / call sizes (aecm_flow_plan.h: FlowRouteTickMixed): the object holds
 // sessions of both rates, or a session makes a half call (kFlowHalfCall) in this tick.  Everything the sparse planning kernel
-// above does -- its text once more, so that THAT kernel stays, instruction for instruction, the kernel it was (the reason
-// aecm_tick_flow_body.inc gives for the tick kernels) -- except that the lane takes its session's rate from the core state
-// (scal = StatePtrs::scal, S_MULT: what the block engine itself goes by) instead of the object's, and plans with
-// FlowTickMixed: a half call is one call pair of 80 samples that leaves the session 80 samples behind.
+// above does, except that the lane takes its session's rate from the core state (scal = StatePtrs::scal, S_MULT: what the block
+// engine itself goes by) instead of the object's, and plans with FlowTickMixed: a half call is one call pair of 80 samples that
+// leaves the session 80 samples behind.
 __device__ __forceinline__ void FlowPlanMixedBody(const TickFlowIo &fio, const TickSparseIo &sp, const int32_t *scal, int n, unsigned near_pos,
                                                    int n_streams, uint32_t *wave_counts) {
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    const bool in_range = s < n_streams;
-    const int flags = !in_range ? kFlowIdle : fio.flags_per_session ? (int)fio.flags_per_session[s] : fio.flags;
-    const bool live = (flags & kFlowIdle) == 0;
-    if (sp.live) {                                                  // (uniform: a kernel argument)
-        const uint64_t ballot = __ballot(live);
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        if (lane == 0) wave_counts[wave] = (uint32_t)__builtin_popcountll(ballot);
-        __syncthreads();
-        const uint32_t slot = FlowLiveSlot(sp.block_base[blockIdx.x], wave_counts, wave, ballot, lane);
-        if (live && slot < (uint32_t)n_streams) sp.live[slot] = (uint32_t)s;      // (the list holds n_streams entries)
-    }
-    if (!in_range) return;
-    int32_t *lag = fio.state + (size_t)F_NEAR_LAG * n_streams + s;
-    if (!live) {
-        *lag = FlowIdleTick(FlowIdleTick(*lag, sp.deferred_lag), n);
-        return;
-    }
-    FlowRegs r;
-    for (int k = 0; k < kFlowFieldsUsed; ++k) r.v[k] = fio.state[(size_t)k * n_streams + s];
-    r.v[F_NEAR_LAG] = FlowIdleTick(r.v[F_NEAR_LAG], sp.deferred_lag);
-    if (r.v[F_NEAR_LAG] != 0) {
-        FlowNearMove m;
-        FlowResync(r, near_pos, m);
-        const uint32_t mask = (uint32_t)sp.ring_len - 1u;
-        FlowMoveNear(sp.near_ring + (size_t)s * sp.ring_len, mask, m);
-        if (sp.clean_ring) FlowMoveNear(sp.clean_ring + (size_t)s * sp.ring_len, mask, m);
-    }
-    const int ms = fio.ms_per_session ? (int)fio.ms_per_session[s] : fio.ms;
-    FlowPlan p;
-    FlowTickMixed(r, scal[(size_t)s * kNumScal + S_MULT] == 2 ? 16000 : 8000, n, ms, flags, near_pos, p);
-    for (int k = 0; k < kFlowFieldsUsed; ++k) fio.state[(size_t)k * n_streams + s] = r.v[k];
-    int32_t w[kFlowPlanWords];
-    FlowPackPlan(p, w);
-    int4 *dst = reinterpret_cast<int4 *>(fio.plans + (size_t)s * kFlowPlanWords);
-    for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+#define AECM_FLOW_PLAN_LIST_GUARD if (sp.live)
+#include "aecm_flow_plan_list.inc"
+#define AECM_FLOW_PLAN_IDLE_SAMPLES n
+#define AECM_FLOW_PLAN_TICK(p) FlowTickMixed(r, scal[(size_t)s * kNumScal + S_MULT] == 2 ? 16000 : 8000, n, ms, flags, near_pos, p)
+#include "aecm_flow_plan_lane.inc"
 }
 __global__ __launch_bounds__(256)
 void aecm_flow_plan_mixed_kernel(TickFlowIo fio, TickSparseIo sp, const int32_t *__restrict__ scal, int n, unsigned near_pos, int n_streams) {
@@ -349,33 +256,7 @@ void aecm_flow_plan_mixed_kernel(TickFlowIo fio, TickSparseIo sp, const int32_t 
     FlowPlanMixedBody(fio, sp, scal, n, near_pos, n_streams, wave_counts);
 }
 
-// Sessions per workgroup of the tick kernel.  A workgroup's waves are placed together, n / 4 per SIMD: with the 7 waves
-// per SIMD the kernel is built for (below), 8-wave workgroups can only ever fill 6 of the 7 slots, 4-wave workgroups all
-// of them -- at the price of one 20 KB table fill (from L2) per 4 sessions instead of per 8.  Measured, 65 536 sessions,
-// ms per tick: 8 sessions 0.2356, 4 sessions 0.2251, 2 sessions 0.3153.  (Round 2, at 8 waves per SIMD, 8 per
-// workgroup was the better size: profiles/r02_experiments.md.)
-#ifndef AECM_TICK_FLOW_WAVES
-#define AECM_TICK_FLOW_WAVES 4
-#endif
-#ifndef AECM_TICK_EARLY_STATE_LOAD
-#define AECM_TICK_EARLY_STATE_LOAD 1      // 65 536 sessions: 0.2218 -> 0.2194 ms per tick.  (Timing probes without the two fences of the
-                                          // tick -- samples into the rings before the blocks fetch them, block outputs before the
-                                          // output frames read them -- moved nothing: 0.2199 / 0.2193 / 0.2199 / 0.2190 ms.)
-#endif
-#ifndef AECM_TICK_SPLIT_PLAN_WORDS
-#define AECM_TICK_SPLIT_PLAN_WORDS 1
-#endif
-#ifndef AECM_TICK_FLOW_WAVES_PER_EU
-#if defined(AECM_CHECKED)
-#define AECM_TICK_FLOW_WAVES_PER_EU 4
-#else
-// 7, not 8: the scalar budget of 8 waves per SIMD (78) costs this kernel hundreds of scalar spills; at 94 it has 52.  With the
-// uniform regions left unstructurized (build.py): 8 waves 0.272 ms per tick of 65 536 sessions, 7 waves 0.234, 6 waves 0.237
-// (default pipeline: 0.241 at 8 waves, its best).
-#define AECM_TICK_FLOW_WAVES_PER_EU 7
-#endif
-#endif
-constexpr int kTickFlowWaves = AECM_TICK_FLOW_WAVES;
+// (aecm_tick_unit.h: four sessions per workgroup, 7 waves per SIMD, and the measurements behind both.)
 template <bool kHasClean>
 __global__ __launch_bounds__(64 * kTickFlowWaves) __attribute__((amdgpu_waves_per_eu(AECM_TICK_FLOW_WAVES_PER_EU, 8)))
 void aecm_tick_flow_kernel(StatePtrs st, TickIo io, TickFlowIo fio, int n_streams) {
@@ -384,16 +265,13 @@ void aecm_tick_flow_kernel(StatePtrs st, TickIo io, TickFlowIo fio, int n_stream
 #include "aecm_tick_flow_body.inc"
 }
 // The tick of the sessions that call, in an object where others sit the tick out (AECM_SESSION_IDLE): wavefront w of the grid
-// serves session live[w], w < live_count (the list aecm_flow_plan_sparse_kernel wrote: ascending ids).  The id is wave-uniform
-// and in a scalar register -- readfirstlane -- before anything is addressed by it, ahead of the early state loads: every row
-// offset of the body stays scalar, and the scalar half of the state is still fetched by scalar loads.  A wavefront past the
-// list's end serves nobody but still takes part in the table fill's barrier (s = n_streams makes it leave behind it).
+// serves session live[w], w < live_count (the list aecm_flow_plan_sparse_kernel wrote; AECM_TICK_LIVE_SESSION, aecm_tick_unit.h,
+// ahead of the early state loads).
 template <bool kHasClean>
 __global__ __launch_bounds__(64 * kTickFlowWaves) __attribute__((amdgpu_waves_per_eu(AECM_TICK_FLOW_WAVES_PER_EU, 8)))
 void aecm_tick_flow_sparse_kernel(StatePtrs st, TickIo io, TickFlowIo fio, int n_streams, const uint32_t *__restrict__ live, int live_count) {
     const int64_t wave_id = (int64_t)blockIdx.x * kTickFlowWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)live[wave_id < live_count ? wave_id : 0]);
-    const int64_t s = wave_id < live_count && id < (uint32_t)n_streams ? (int64_t)id : (int64_t)n_streams;
+    AECM_TICK_LIVE_SESSION(live, live_count, wave_id)
     const int lane = threadIdx.x & 63;
 #include "aecm_tick_flow_body.inc"
 }

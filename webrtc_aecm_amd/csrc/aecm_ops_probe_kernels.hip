@@ -16,9 +16,7 @@
 // A unit of its own, built with the block kernels' flags (build.py: SOURCE_FLAGS): the primitives are compiled the way they ship,
 // and no other unit's instruction stream moves.
 #define AECM_TABLE_ATTR __device__
-#if defined(AECM_CHECKED)
-#define g_aecm_check_fail g_aecm_check_fail_ops_probe      // device symbols are per translation unit (no relocatable device code)
-#endif
+#define AECM_CHECK_UNIT ops_probe      // (aecm_kernel_common.h: the unit's pair of audit counters)
 #include "aecm_kernel_common.h"
 
 #define AECM_OPS_ENGINE BlockEngine<Gfx950Wave<true>, false>
@@ -36,28 +34,8 @@
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail_ops_probe[2];
-#endif
 // This unit's share of the audit counters (see ReadCheckCounters in aecm_kernels.hip); WebRtcAecmBatch_GetCheckCounters adds it in.
-hipError_t ReadOpsProbeCheckCounters(uint64_t counters[2], bool reset) {
-#if defined(AECM_CHECKED)
-    unsigned long long host[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail_ops_probe), sizeof host);
-    if (e != hipSuccess) return e;
-    counters[0] = host[0];
-    counters[1] = host[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail_ops_probe), zero, sizeof zero);
-    }
-    return e;
-#else
-    (void)counters;
-    (void)reset;
-    return hipErrorNotSupported;
-#endif
-}
+AECM_DEFINE_CHECK_COUNTERS(ReadOpsProbeCheckCounters)
 
 // ---- the table, as the host sees it --------------------------------------------------------------
 namespace {

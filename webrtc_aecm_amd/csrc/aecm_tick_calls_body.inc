@@ -1,14 +1,14 @@
 // The body of the loop-form tick kernels -- aecm_tick_calls_kernel (aecm_tick_calls_kernels.hip) and aecm_tick_packets_kernel
 // (aecm_tick_packets_kernels.hip) -- as TEXT, included between the braces of each (the way of aecm_tick_flow_body.inc, and for its
 // reason: the K-call kernels stay, token for token and so instruction for instruction, what they were;
-// tests/golden/tick_calls_fingerprints.json).  In scope: st, io, fio, n_streams, live, live_count, calls, kHasClean.  The two kernels
+// tests/golden/tick_calls_fingerprints.json).  In scope: st, io, fio, n_streams, live, live_count, calls, kHasClean, and
+// what aecm_tick_unit.h defines (TickBlockIo, kTickCallsWaves, AECM_TICK_LIVE_SESSION).  The two kernels
 // differ in ONE thing, where a call's sample count n -- which is also the step from one call's rows to the next -- comes from:
 //   AECM_TICK_CALLS_SIZE_OF_LAUNCH   `const int n = io.n;` for the K-call tick (every session makes calls of the launch's n), else empty
 //   AECM_TICK_CALLS_SIZE_OF_PLAN     `const int n = p.n_frames * kFlowFrame;` for the packet tick (the SESSION's call size, wave-uniform,
 //                                    the same in all of its K plans: rows packed, near positions contiguous), else empty
     const int64_t wave_id = (int64_t)blockIdx.x * kTickCallsWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)live[wave_id < live_count ? wave_id : 0]);
-    const int64_t s = wave_id < live_count && id < (uint32_t)n_streams ? (int64_t)id : (int64_t)n_streams;
+    AECM_TICK_LIVE_SESSION(live, live_count, wave_id)
     const int lane_id = threadIdx.x & 63;
     using E = BlockEngine<Gfx950Wave<true, true, true>, kHasClean>;
     typename E::Regs r;
@@ -107,10 +107,10 @@
             }
         }
         // 4. the blocks, on the registers the calls before left (the fence between the stores above and the blocks' fetches:
-        //    TickCallsBlockIo::ready)
+        //    TickBlockIo::ready, aecm_tick_unit.h)
         const int nb = p.n_blocks;
         if (nb > 0) {
-            using Io = TickCallsBlockIo<kHasClean, decltype(append)>;
+            using Io = TickBlockIo<kHasClean, decltype(append)>;
             Io bio{p.direct ? fr : ff, nr, cr, orow, p.direct ? mask : kFlowFarFrameRing - 1, mask,
                    p.direct ? p.blk_pos0 + p.far_delta : p.blk_pos0, p.near_base + p.blk_pos0, p.blk_pos0, append};
             E::run_blocks_loaded(r, st, bio, s, nb);

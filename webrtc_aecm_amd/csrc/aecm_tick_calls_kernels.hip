@@ -9,37 +9,15 @@
 // A unit of its own: the tick kernels of aecm_kernels.hip stay, instruction for instruction, what they were.  Compiled with
 // that unit's flags (build.py: SOURCE_FLAGS).
 #define AECM_TABLE_ATTR __device__
-#if defined(AECM_CHECKED)
-#define g_aecm_check_fail g_aecm_check_fail_tick_calls      // device symbols are per translation unit (no relocatable device code)
-#endif
+#define AECM_CHECK_UNIT tick_calls      // (aecm_kernel_common.h: the unit's pair of audit counters)
 #include "aecm_kernel_common.h"
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail_tick_calls[2];
-#endif
 // This unit's share of the audit counters of the -DAECM_CHECKED build (aecm_ops.h); hipErrorNotSupported in the shipped build.
-hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset) {
-#if defined(AECM_CHECKED)
-    unsigned long long host[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail_tick_calls), sizeof host);
-    if (e != hipSuccess) return e;
-    counters[0] = host[0];
-    counters[1] = host[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail_tick_calls), zero, sizeof zero);
-    }
-    return e;
-#else
-    (void)counters;
-    (void)reset;
-    return hipErrorNotSupported;
-#endif
-}
+AECM_DEFINE_CHECK_COUNTERS(ReadTickCallsCheckCounters)
 
-#include "aecm_tick_calls_io.h"
+#include "aecm_tick_unit.h"
 
 // Wavefront w of the grid serves session live[w], w < live_count (ascending ids; the id wave-uniform and in a scalar register
 // before anything is addressed by it).  The state loads are issued once, ahead of the table fill -- and ahead of every fence

@@ -1,5 +1,5 @@
-// The body of the tick kernels (aecm_kernels.hip: aecm_tick_flow_kernel, aecm_tick_flow_sparse_kernel), included into each
-// after it has named its session: s (int64_t, wave-uniform, in a scalar register; >= n_streams: the wavefront serves nobody
+// The body of the tick kernels (aecm_kernels.hip: aecm_tick_flow_kernel, aecm_tick_flow_sparse_kernel; aecm_tick_split_kernels.hip:
+// aecm_tick_split_kernel, aecm_tick_split_list_kernel), included into each behind aecm_tick_unit.h and after it has named its session: s (int64_t, wave-uniform, in a scalar register; >= n_streams: the wavefront serves nobody
 // and leaves behind the table fill's barrier) and lane.  One text for both, so the two cannot drift apart -- and a text
 // rather than a function, so that the dense kernel stays, instruction for instruction, the kernel it was before there was
 // a sparse one.  The other forms were tried:
@@ -117,10 +117,10 @@
             if (lane < kFlowFrame - 64) ff[(q.frm_pos + 64 + lane) & (kFlowFarFrameRing - 1)] = v1[f];
         }
     }
-    // 4. the blocks (the fence between the stores above and the blocks' fetches is TickFlowBlockIo::ready)
+    // 4. the blocks (the fence between the stores above and the blocks' fetches is TickBlockIo::ready, aecm_tick_unit.h)
     const int nb = p.n_blocks;
     if (nb > 0) {
-        using Io = TickFlowBlockIo<kHasClean, decltype(append)>;
+        using Io = TickBlockIo<kHasClean, decltype(append)>;
         Io bio{p.direct ? fr : ff, nr, cr, orow, p.direct ? mask : kFlowFarFrameRing - 1, mask,
                p.direct ? p.blk_pos0 + p.far_delta : p.blk_pos0, p.near_base + p.blk_pos0, p.blk_pos0, append};
 #if AECM_TICK_EARLY_STATE_LOAD

@@ -11,37 +11,15 @@
 // written.  A unit of its own: the kernels of aecm_tick_calls_kernels.hip stay, instruction for instruction, what they were
 // (tests/golden/tick_calls_fingerprints.json).  Compiled with that unit's flags (build.py: SOURCE_FLAGS).
 #define AECM_TABLE_ATTR __device__
-#if defined(AECM_CHECKED)
-#define g_aecm_check_fail g_aecm_check_fail_tick_packets      // device symbols are per translation unit (no relocatable device code)
-#endif
+#define AECM_CHECK_UNIT tick_packets      // (aecm_kernel_common.h: the unit's pair of audit counters)
 #include "aecm_kernel_common.h"
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail_tick_packets[2];
-#endif
 // This unit's share of the audit counters of the -DAECM_CHECKED build (aecm_ops.h); hipErrorNotSupported in the shipped build.
-hipError_t ReadTickPacketsCheckCounters(uint64_t counters[2], bool reset) {
-#if defined(AECM_CHECKED)
-    unsigned long long host[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail_tick_packets), sizeof host);
-    if (e != hipSuccess) return e;
-    counters[0] = host[0];
-    counters[1] = host[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail_tick_packets), zero, sizeof zero);
-    }
-    return e;
-#else
-    (void)counters;
-    (void)reset;
-    return hipErrorNotSupported;
-#endif
-}
+AECM_DEFINE_CHECK_COUNTERS(ReadTickPacketsCheckCounters)
 
-#include "aecm_tick_calls_io.h"
+#include "aecm_tick_unit.h"
 
 // Wavefront w of the grid serves session live[w], w < live_count: the K-call tick kernel, but every session with the call size its
 // own plans name (the planning kernel gave every one of a session's K plans the same n_frames).

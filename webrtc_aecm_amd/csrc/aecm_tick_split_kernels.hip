@@ -9,85 +9,25 @@
 // never touched.  A unit of its own: the tick kernels of aecm_kernels.hip stay, instruction for instruction, what they were.
 // Compiled with that unit's flags (build.py: SOURCE_FLAGS).
 #define AECM_TABLE_ATTR __device__
-#if defined(AECM_CHECKED)
-#define g_aecm_check_fail g_aecm_check_fail_tick_split      // device symbols are per translation unit (no relocatable device code)
-#endif
+#define AECM_CHECK_UNIT tick_split      // (aecm_kernel_common.h: the unit's pair of audit counters)
 #include "aecm_kernel_common.h"
 
 #include "aecm_flow_clean.h"      // (behind the HIP headers: aecm_flow_plan.h takes __forceinline__ from them)
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail_tick_split[2];
-#endif
 // This unit's share of the audit counters of the -DAECM_CHECKED build (aecm_ops.h); hipErrorNotSupported in the shipped build.
-hipError_t ReadTickSplitCheckCounters(uint64_t counters[2], bool reset) {
-#if defined(AECM_CHECKED)
-    unsigned long long host[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail_tick_split), sizeof host);
-    if (e != hipSuccess) return e;
-    counters[0] = host[0];
-    counters[1] = host[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail_tick_split), zero, sizeof zero);
-    }
-    return e;
-#else
-    (void)counters;
-    (void)reset;
-    return hipErrorNotSupported;
-#endif
-}
+AECM_DEFINE_CHECK_COUNTERS(ReadTickSplitCheckCounters)
 
-// What aecm_tick_flow_body.inc expects of the unit that includes it, as aecm_kernels.hip has it: the blocks' view of the session's
-// rings, and the build's choices for the tick kernels (the same defaults; LaunchTickSplit checks the workgroup size against
-// TickWorkgroupWaves() of that unit).
-template <bool kHasClean, class Append>
-struct TickFlowBlockIo {
-    using E = BlockEngine<Gfx950Wave<true, true, true>, kHasClean>;
-    using Regs = typename E::Regs;
-    const int16_t *far_src;          // the far ring itself (direct ticks) or the framed far stream
-    const int16_t *nr, *cr;          // near / clean rings of this session
-    int16_t *out_row;                // output stream ring
-    int far_mask, mask;
-    unsigned far_pos, near_pos, out_pos;      // positions of the tick's first block in far_src / the near rings / the output ring
-    const Append &append;            // the tick's samples -> rings
-    __device__ __forceinline__ int far(const Regs &r, int b) const { return far_src[(far_pos + b * kBlock + r.lane) & far_mask]; }
-    __device__ __forceinline__ int near(const Regs &r, int b) const { return nr[(near_pos + b * kBlock + r.lane) & mask]; }
-    __device__ __forceinline__ int clean(const Regs &r, int b) const { return cr[(near_pos + b * kBlock + r.lane) & mask]; }
-    __device__ __forceinline__ void out(const Regs &r, int b, int v) const { out_row[(out_pos + b * kBlock + r.brev) & mask] = (int16_t)v; }
-    // (aecm_kernels.hip: the tick's samples go into the rings behind the engine's state loads, then this wave's fetches see them)
-    __device__ __forceinline__ void ready() const {
-        append();
-        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-    }
-};
-#ifndef AECM_TICK_FLOW_WAVES
-#define AECM_TICK_FLOW_WAVES 4
-#endif
-#ifndef AECM_TICK_EARLY_STATE_LOAD
-#define AECM_TICK_EARLY_STATE_LOAD 1
-#endif
-#ifndef AECM_TICK_SPLIT_PLAN_WORDS
-#define AECM_TICK_SPLIT_PLAN_WORDS 1
-#endif
-#ifndef AECM_TICK_FLOW_WAVES_PER_EU
-#if defined(AECM_CHECKED)
-#define AECM_TICK_FLOW_WAVES_PER_EU 4
-#else
-#define AECM_TICK_FLOW_WAVES_PER_EU 7      // (aecm_kernels.hip: the scalar budget of 8 waves per SIMD costs the body hundreds of scalar spills)
-#endif
-#endif
-constexpr int kTickFlowWaves = AECM_TICK_FLOW_WAVES;
+// What aecm_tick_flow_body.inc expects of the unit that includes it: the blocks' view of the session's rings and the build's choices
+// for the tick kernels, those of aecm_kernels.hip (LaunchTickSplit checks the workgroup size against TickWorkgroupWaves() of that unit).
+#include "aecm_tick_unit.h"
 static_assert(kTickFlowWaves == kFlowSplitGroup, "the second list starts at a workgroup boundary of the tick kernel");
 
 // Workgroups [0, clean_groups) serve live[0 .. clean_count), the others live[4 clean_groups .. + plain_count): the branch is on
 // blockIdx.x against a kernel argument -- uniform over the workgroup, so the barrier of the table fill inside either copy of the body
-// is taken by all of a workgroup's wavefronts or by none.  As in aecm_tick_flow_sparse_kernel the session's id is wave-uniform and in
-// a scalar register before anything is addressed by it, and a wavefront past its list's end serves nobody but still takes the
-// barrier (s = n_streams makes it leave behind it).  The body is the one text of the other tick kernels, once per kind, each in a
+// is taken by all of a workgroup's wavefronts or by none.  A wavefront finds its session as in aecm_tick_flow_sparse_kernel
+// (AECM_TICK_LIVE_SESSION, aecm_tick_unit.h).  The body is the one text of the other tick kernels, once per kind, each in a
 // scope of its own.
 __global__ __launch_bounds__(64 * kTickFlowWaves) __attribute__((amdgpu_waves_per_eu(AECM_TICK_FLOW_WAVES_PER_EU, 8)))
 void aecm_tick_split_kernel(StatePtrs st, TickIo io, TickFlowIo fio, int n_streams, const uint32_t *__restrict__ live, int clean_count, int clean_groups,
@@ -97,15 +37,13 @@ void aecm_tick_split_kernel(StatePtrs st, TickIo io, TickFlowIo fio, int n_strea
     if ((int)blockIdx.x < clean_groups) {
         constexpr bool kHasClean = true;
         const int64_t wave_id = (int64_t)blockIdx.x * kTickFlowWaves + wave;
-        const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)live[wave_id < clean_count ? wave_id : 0]);
-        const int64_t s = wave_id < clean_count && id < (uint32_t)n_streams ? (int64_t)id : (int64_t)n_streams;
+        AECM_TICK_LIVE_SESSION(live, clean_count, wave_id)
 #include "aecm_tick_flow_body.inc"
     } else {
         constexpr bool kHasClean = false;
         const uint32_t *__restrict__ plain = live + (int64_t)clean_groups * kTickFlowWaves;
         const int64_t wave_id = ((int64_t)blockIdx.x - clean_groups) * kTickFlowWaves + wave;
-        const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)plain[wave_id < plain_count ? wave_id : 0]);
-        const int64_t s = wave_id < plain_count && id < (uint32_t)n_streams ? (int64_t)id : (int64_t)n_streams;
+        AECM_TICK_LIVE_SESSION(plain, plain_count, wave_id)
 #include "aecm_tick_flow_body.inc"
     }
 }
@@ -119,8 +57,7 @@ template <bool kHasClean>
 __global__ __launch_bounds__(64 * kTickFlowWaves) __attribute__((amdgpu_waves_per_eu(AECM_TICK_FLOW_WAVES_PER_EU, 8)))
 void aecm_tick_split_list_kernel(StatePtrs st, TickIo io, TickFlowIo fio, int n_streams, const uint32_t *__restrict__ live, int live_count) {
     const int64_t wave_id = (int64_t)blockIdx.x * kTickFlowWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t id = (uint32_t)__builtin_amdgcn_readfirstlane((int)live[wave_id < live_count ? wave_id : 0]);
-    const int64_t s = wave_id < live_count && id < (uint32_t)n_streams ? (int64_t)id : (int64_t)n_streams;
+    AECM_TICK_LIVE_SESSION(live, live_count, wave_id)
     const int lane = threadIdx.x & 63;
 #include "aecm_tick_flow_body.inc"
 }

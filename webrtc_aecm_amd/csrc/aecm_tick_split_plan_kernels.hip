@@ -10,11 +10,11 @@
 
 namespace aecm {
 
-// One lane per session.  The text of aecm_flow_plan_sparse_kernel (kMixed: of aecm_flow_plan_mixed_kernel -- the lane takes its
-// session's rate from the core state and plans with FlowTickMixed), with two live lists in place of one: a calling lane's id goes to
-// the list of its kind (kFlowNoClean in its flag byte: the sessions whose Process gets no clean pointer), each list ascending, the
-// second starting at split.plain_start.  A session without a clean input keeps a clean ring row all the same; nothing reads it, so
-// the resync may move it along with the near ring like everybody's.
+// One lane per session: the planning lane of the sparse tick (kMixed: of the mixed tick -- the lane takes its session's rate from
+// the core state and plans with FlowTickMixed; aecm_flow_plan_lane.inc), behind first lines of its own, for two live lists in place
+// of one: a calling lane's id goes to the list of its kind (kFlowNoClean in its flag byte: the sessions whose Process gets no clean
+// pointer), each list ascending, the second starting at split.plain_start.  A session without a clean input keeps a clean ring row
+// all the same; nothing reads it, so the resync may move it along with the near ring like everybody's.
 static_assert(kFlowPlanBlock == 256, "the planning kernels run 256 lanes per workgroup");
 template <bool kMixed>
 __global__ __launch_bounds__(256)
@@ -38,31 +38,11 @@ void aecm_flow_plan_split_kernel(TickFlowIo fio, TickSparseIo sp, TickSplitIo sp
         const uint32_t end = no_clean ? split.plain_start + (uint32_t)split.plain_count : (uint32_t)split.clean_count;
         if (live && slot < end && slot < FlowSplitListEntries((uint32_t)n_streams)) sp.live[slot] = (uint32_t)s;
     }
-    if (!in_range) return;
-    int32_t *lag = fio.state + (size_t)F_NEAR_LAG * n_streams + s;
-    if (!live) {
-        *lag = FlowIdleTick(FlowIdleTick(*lag, sp.deferred_lag), n);
-        return;
-    }
-    FlowRegs r;
-    for (int k = 0; k < kFlowFieldsUsed; ++k) r.v[k] = fio.state[(size_t)k * n_streams + s];
-    r.v[F_NEAR_LAG] = FlowIdleTick(r.v[F_NEAR_LAG], sp.deferred_lag);
-    if (r.v[F_NEAR_LAG] != 0) {
-        FlowNearMove m;
-        FlowResync(r, near_pos, m);
-        const uint32_t mask = (uint32_t)sp.ring_len - 1u;
-        FlowMoveNear(sp.near_ring + (size_t)s * sp.ring_len, mask, m);
-        if (sp.clean_ring) FlowMoveNear(sp.clean_ring + (size_t)s * sp.ring_len, mask, m);
-    }
-    const int ms = fio.ms_per_session ? (int)fio.ms_per_session[s] : fio.ms;
-    FlowPlan p;
-    if (kMixed) FlowTickMixed(r, scal[(size_t)s * kNumScal + S_MULT] == 2 ? 16000 : 8000, n, ms, flags, near_pos, p);
-    else FlowTick(r, fio.fs, n, ms, flags, near_pos, p);
-    for (int k = 0; k < kFlowFieldsUsed; ++k) fio.state[(size_t)k * n_streams + s] = r.v[k];
-    int32_t w[kFlowPlanWords];
-    FlowPackPlan(p, w);
-    int4 *dst = reinterpret_cast<int4 *>(fio.plans + (size_t)s * kFlowPlanWords);
-    for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+#define AECM_FLOW_PLAN_IDLE_SAMPLES n
+#define AECM_FLOW_PLAN_TICK(p)                                                                                      \
+    if (kMixed) FlowTickMixed(r, scal[(size_t)s * kNumScal + S_MULT] == 2 ? 16000 : 8000, n, ms, flags, near_pos, p); \
+    else FlowTick(r, fio.fs, n, ms, flags, near_pos, p)
+#include "aecm_flow_plan_lane.inc"
 }
 
 hipError_t LaunchPlanSplit(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,

@@ -19,36 +19,14 @@
 // vector store like the audio rows', never part of the sc1 state hand-over between the chunks of a stream: nobody reads a record
 // inside a launch, and QueuePublish's s_waitcnt vmcnt(0) covers them like every other store of the chunk.
 #define AECM_TABLE_ATTR __device__
-#if defined(AECM_CHECKED)
-#define g_aecm_check_fail g_aecm_check_fail_trace      // device symbols are per translation unit (no relocatable device code)
-#endif
+#define AECM_CHECK_UNIT trace      // (aecm_kernel_common.h: the unit's pair of audit counters)
 #include "aecm_kernel_common.h"
 #include "aecm_block_queue.h"
 
 namespace aecm {
 
-#if defined(AECM_CHECKED)
-__device__ unsigned long long g_aecm_check_fail_trace[2];
-#endif
 // This unit's share of the audit counters (see ReadCheckCounters in aecm_kernels.hip).
-hipError_t ReadTraceKernelCheckCounters(uint64_t counters[2], bool reset) {
-#if defined(AECM_CHECKED)
-    unsigned long long host[2] = {0, 0};
-    hipError_t e = hipMemcpyFromSymbol(host, HIP_SYMBOL(g_aecm_check_fail_trace), sizeof host);
-    if (e != hipSuccess) return e;
-    counters[0] = host[0];
-    counters[1] = host[1];
-    if (reset) {
-        const unsigned long long zero[2] = {0, 0};
-        e = hipMemcpyToSymbol(HIP_SYMBOL(g_aecm_check_fail_trace), zero, sizeof zero);
-    }
-    return e;
-#else
-    (void)counters;
-    (void)reset;
-    return hipErrorNotSupported;
-#endif
-}
+AECM_DEFINE_CHECK_COUNTERS(ReadTraceKernelCheckCounters)
 
 template <bool kFast, bool kHasClean, bool kPhasePrio = true>
 __global__ __launch_bounds__(64 * kWavesPerWorkgroup)
