@@ -456,6 +456,57 @@ int32_t WebRtcAecmSessions_GetSessionCleanMode(AecmSessions *s, int32_t session,
  * fused launch; on > 0: always one launch per list.  Results do not change. */
 int32_t WebRtcAecmSessions_SplitCleanTwoLaunches(AecmSessions *s, int32_t on);
 
+/* ---- Session trace: where every call stands, per tick, without stopping the clock ------------------------------
+ * Opt-in, per object.  While a trace buffer is attached, every session that calls in a tick of ONE call pair per session also writes
+ * one 64-byte record: has its canceller left start-up, which delay does the wrapper steer by, how full is its far-end jitter buffer,
+ * and -- in `core` -- what the block trace shows of the core state after the tick's last block (echo delay estimate, far-end activity,
+ * suppression gain ...).  Every wrapper field is the value WebRtcAecmSessions_ExportSession would show directly after that tick, taken
+ * from the wrapper words of the snapshot (the named member of the reference's AecMobile, echo_control_mobile.cc:42-79; the 16-bit
+ * fields are the low halves of their words); `core` is AecmBlockTrace of the core blob of that same snapshot.  Little endian.
+ * Audio, codes, state and snapshots are identical with and without a trace; with none attached every launch is the launch it is
+ * without this feature, with the same kernels. */
+typedef struct AecmSessionTrace {      /* 64 bytes */
+    uint32_t tick;                     /*  0  number of this tick, counted from 0 at attachment                            */
+    int16_t  blocks;                   /*  4  blocks the core ran for this session in this tick: the advance of the snapshot's
+                                        *     block position over the tick, divided by 64 (0 in the start-up phase)         */
+    int16_t  samp_khz;                 /*  6  8 or 16: the session's own rate                                              */
+    int16_t  ms_in_snd_card_buf;       /*  8  msInSndCardBuf (after the reference's + 10)                                  */
+    int16_t  known_delay;              /* 10  knownDelay                                                                   */
+    int16_t  filt_delay;               /* 12  filtDelay                                                                    */
+    int16_t  buf_size_start;           /* 14  bufSizeStart                                                                 */
+    int16_t  ec_startup;               /* 16  ECstartup: 1 while the session is in its start-up phase                      */
+    int16_t  check_buff_size;          /* 18  checkBuffSize                                                                */
+    int16_t  delay_change;             /* 20  delayChange                                                                  */
+    int16_t  last_delay_diff;          /* 22  lastDelayDiff                                                                */
+    int32_t  far_buffered;             /* 24  samples in the far-end jitter buffer, 0 .. 4000                              */
+    int32_t  time_for_delay_change;    /* 28  timeForDelayChange                                                           */
+    AecmBlockTrace core;               /* 32  the core state after the tick's last block, exactly AecmBlockTrace           */
+} AecmSessionTrace;
+size_t WebRtcAecmSessions_session_trace_size_bytes(void);      /* 64 */
+/* Attaches trace_dev (device memory, or a registered host alias: WebRtcAecmBatch_RegisterHostBuffer; NULL detaches).  Strides are in
+ * records: tick number j since attachment writes session s's record at
+ *     trace_dev + 64 * (s * session_stride + (j % ring_ticks) * tick_stride).
+ * ring_ticks == 1 keeps "the latest record per session", a larger ring keeps history: a session-major buffer [S][R] is (R, 1, R), a
+ * tick-major one [R][S] is (1, S, R).  The caller owns the buffer and its size, as for out_dev.  Attaching (again) starts the count at 0.
+ *  - A session that runs no block in a tick (start-up phase) still gets its record, with the core state it holds.
+ *  - A session that carries AECM_SESSION_IDLE gets no record: its slot keeps its bytes, and the `tick` field of what it holds tells a
+ *    consumer how old that is.  A tick in which nobody calls writes nothing and still counts.
+ *  - Traced: every tick of ONE call pair per session -- Tick, TickPerSession, TickFlags, TickAsync, their Host forms, Process /
+ *    ProcessHost, and TickCalls* / TickPackets* with calls == 1 -- with every flag (AECM_SESSION_SPLIT_CALLS: one record for the tick,
+ *    taken after the second call), with per-session msInSndCardBuf, with sessions of both rates, with and without a clean input.
+ *    WebRtcAecmSessions_BufferFarend* writes no record.
+ *  - While a trace is attached, TickCalls* / TickPackets* with calls > 1 return AECM_UNSUPPORTED_FUNCTION_ERROR and change nothing:
+ *    not the sessions, not the position, not the tick count.  (Those ticks keep the core state in registers across their calls; a
+ *    record per call from that loop is the follow-up.)
+ *  - A refused tick of any kind does not advance the count.
+ *  - With TickAsync the records are visible where out is: behind done_hip_event or WebRtcAecmSessions_Synchronize.
+ *  - SetSessionTrace is ordered behind the ticks already enqueued: they write where they were told to when they were enqueued.
+ * Returns 0, or AECM_BAD_PARAMETER_ERROR with nothing changed (an attached trace stays attached) for a NULL object, a pointer that is
+ * not 4-byte aligned, a stride <= 0 or ring_ticks <= 0. */
+int32_t WebRtcAecmSessions_SetSessionTrace(AecmSessions *s, void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks);
+/* *ticks = the ticks accepted since the trace was attached (0 while none is attached).  Needs no device. */
+int32_t WebRtcAecmSessions_GetSessionTraceTicks(AecmSessions *s, int64_t *ticks);
+
 /* Zero-copy host audio.  A caller-owned host buffer is pinned and mapped into the device's address space once
  * (hipHostRegister); *device_alias is then a device pointer that every *_dev argument of this header accepts
  * (WebRtcAecmBatch_ProcessBlocks, WebRtcAecmSessions_Tick / TickAsync ...): the kernels read the samples and write the

@@ -1,6 +1,7 @@
 // extern "C" surface of libaecm_mi355x.so: the reference's session ABI (include/echo_control_mobile.h)
 // and the batch extension (include/aecm_batch.h).  Plain pointers and sizes only.
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <string.h>
 
 #include <new>
@@ -879,6 +880,24 @@ int32_t WebRtcAecmSessions_GetSessionCleanMode(AecmSessions *s, int32_t session,
 int32_t WebRtcAecmSessions_SplitCleanTwoLaunches(AecmSessions *s, int32_t on) {
     if (!s) return -1;
     s->batch->SplitCleanTwoLaunches(on);
+    return 0;
+}
+
+// The session trace: the record is aecm_session_trace.h's eight words and the block trace's eight.
+static_assert(sizeof(AecmSessionTrace) == aecm::kSessionTraceWords * sizeof(uint32_t) && offsetof(AecmSessionTrace, core) == aecm::kSessionTraceHeaderWords * sizeof(uint32_t) &&
+                  offsetof(AecmSessionTrace, far_buffered) == 24 && offsetof(AecmSessionTrace, time_for_delay_change) == 28,
+              "the session trace record is sixteen words, the wrapper half first");
+size_t WebRtcAecmSessions_session_trace_size_bytes(void) { return sizeof(AecmSessionTrace); }
+
+int32_t WebRtcAecmSessions_SetSessionTrace(AecmSessions *s, void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks) {
+    if (!s) return AECM_BAD_PARAMETER_ERROR;
+    return s->batch->SetSessionTrace(trace_dev, session_stride, tick_stride, ring_ticks);
+}
+
+int32_t WebRtcAecmSessions_GetSessionTraceTicks(AecmSessions *s, int64_t *ticks) {
+    if (!s) return AECM_BAD_PARAMETER_ERROR;
+    if (!ticks) return AECM_NULL_POINTER_ERROR;
+    *ticks = s->batch->session_trace_ticks();
     return 0;
 }
 

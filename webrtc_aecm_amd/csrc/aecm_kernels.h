@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "aecm_flow_plan.h"
+#include "aecm_session_trace.h"
 #include "aecm_state.h"
 
 namespace aecm {
@@ -238,6 +239,19 @@ hipError_t LaunchTickSplit(const StatePtrs &st, const TickIo &io, const TickFlow
 // The planning launch alone (aecm_tick_split_plan_kernels.hip; LaunchTickSplit calls it).
 hipError_t LaunchPlanSplit(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,
                            bool mixed_plan, hipStream_t stream);
+// The planning launch of LaunchTickFlow (sp == nullptr) / LaunchTickFlowSparse alone (aecm_kernels.hip; both call it).
+hipError_t LaunchPlanFlow(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo *sp, int n_streams, bool mixed_plan,
+                          hipStream_t stream);
+// The three tick launches of one call pair per session with a session trace attached (aecm_tick_trace_kernels.hip;
+// include/aecm_batch.h: AecmSessionTrace): the planning launches are the ones above, unchanged; the tick launch is the traced twin of
+// the untraced one, and every session it serves also writes its 64-byte record to
+// tv.records + kSessionTraceWords * (s * tv.session_stride + tv.tick_slot_offset) (aecm_session_trace.h: SessionTraceView; tv.records
+// must not be null).  The other arguments and the results are those of the launches above.  There is no traced K-call / packet tick.
+hipError_t LaunchTickFlowTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const SessionTraceView &tv, int n_streams, hipStream_t stream);
+hipError_t LaunchTickFlowSparseTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const SessionTraceView &tv,
+                                      int n_streams, int live_count, hipStream_t stream, bool mixed_plan = false);
+hipError_t LaunchTickSplitTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split,
+                                 const SessionTraceView &tv, int n_streams, bool mixed_plan, bool two_launches, hipStream_t stream);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront
@@ -267,6 +281,8 @@ hipError_t ReadCheckCounters(uint64_t counters[2], bool reset);
 hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_trace_kernels.hip (the traced block kernels); ReadCheckCounters adds it in as well.  Does not synchronise.
 hipError_t ReadTraceKernelCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_tick_trace_kernels.hip (the traced tick kernels); ReadCheckCounters adds it in as well.  Does not synchronise.
+hipError_t ReadTickTraceCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_calls_kernels.hip, for callers that audit K-call ticks (ReadCheckCounters does not add it in).  Does not synchronise.
 hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_packets_kernels.hip, likewise.

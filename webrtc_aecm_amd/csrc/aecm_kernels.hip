@@ -9,14 +9,14 @@
 namespace aecm {
 
 AECM_DEFINE_CHECK_COUNTERS(ReadThisUnitCheckCounters)      // (used below only)
-// Audit counters of the -DAECM_CHECKED build (aecm_ops.h): this unit's pair, the block kernels' and the traced block kernels',
-// behind everything the device still has to do; hipErrorNotSupported in the shipped build.
+// Audit counters of the -DAECM_CHECKED build (aecm_ops.h): this unit's pair, the block kernels', the traced block kernels' and the
+// traced tick kernels', behind everything the device still has to do; hipErrorNotSupported in the shipped build.
 hipError_t ReadCheckCounters(uint64_t counters[2], bool reset) {
 #if defined(AECM_CHECKED)
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return e;
     uint64_t sum[2] = {0, 0};
-    for (const auto read : {ReadThisUnitCheckCounters, ReadBlockKernelCheckCounters, ReadTraceKernelCheckCounters}) {
+    for (const auto read : {ReadThisUnitCheckCounters, ReadBlockKernelCheckCounters, ReadTraceKernelCheckCounters, ReadTickTraceCheckCounters}) {
         uint64_t share[2] = {0, 0};
         e = read(share, reset);
         if (e != hipSuccess) return e;
@@ -282,9 +282,21 @@ int TickWorkgroupsPerCu() {       // by the wave slots the kernel is built for, 
     return by_waves < by_lds ? by_waves : by_lds;
 }
 
+// The planning launch of a tick of one call pair alone (the launchers below call it, and their traced twins in
+// aecm_tick_trace_kernels.hip): sp == nullptr: the dense planning kernel; else the sparse one or, with mixed_plan, the mixed one.
+hipError_t LaunchPlanFlow(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo *sp, int n_streams, bool mixed_plan,
+                          hipStream_t stream) {
+    if (n_streams <= 0) return hipSuccess;
+    const dim3 grid((n_streams + 255) / 256), block(256);
+    if (!sp) hipLaunchKernelGGL(aecm_flow_plan_kernel, grid, block, 0, stream, fio, io.n, (unsigned)io.near_pos, n_streams);
+    else if (mixed_plan) hipLaunchKernelGGL(aecm_flow_plan_mixed_kernel, grid, block, 0, stream, fio, *sp, st.scal, io.n, (unsigned)io.near_pos, n_streams);
+    else hipLaunchKernelGGL(aecm_flow_plan_sparse_kernel, grid, block, 0, stream, fio, *sp, io.n, (unsigned)io.near_pos, n_streams);
+    return hipGetLastError();
+}
+
 hipError_t LaunchTickFlow(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, int n_streams, hipStream_t stream) {
     if (n_streams <= 0) return hipSuccess;
-    hipLaunchKernelGGL(aecm_flow_plan_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, fio, io.n, (unsigned)io.near_pos, n_streams);
+    (void)LaunchPlanFlow(st, io, fio, nullptr, n_streams, false, stream);
     const dim3 grid((n_streams + kTickFlowWaves - 1) / kTickFlowWaves), block(64 * kTickFlowWaves);
     const size_t lds = sizeof(LdsTables);
     if (io.clean_in) hipLaunchKernelGGL((aecm_tick_flow_kernel<true>), grid, block, lds, stream, st, io, fio, n_streams);
@@ -297,10 +309,7 @@ hipError_t LaunchTickFlowSparse(const StatePtrs &st, const TickIo &io, const Tic
     if (n_streams <= 0) return hipSuccess;
     if (live_count < 0 || live_count > n_streams || (sp.live && !sp.block_base)) return hipErrorInvalidValue;
     // the planning launch runs over ALL sessions (the idle ones count their lag); the tick launch over the live ones only
-    if (mixed_plan)
-        hipLaunchKernelGGL(aecm_flow_plan_mixed_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, fio, sp, st.scal, io.n, (unsigned)io.near_pos, n_streams);
-    else
-        hipLaunchKernelGGL(aecm_flow_plan_sparse_kernel, dim3((n_streams + 255) / 256), dim3(256), 0, stream, fio, sp, io.n, (unsigned)io.near_pos, n_streams);
+    (void)LaunchPlanFlow(st, io, fio, &sp, n_streams, mixed_plan, stream);
     const dim3 block(64 * kTickFlowWaves);
     const size_t lds = sizeof(LdsTables);
     if (!sp.live) {                        // nobody idles in this tick (some had, before): everybody is live, the dense tick kernel

@@ -139,6 +139,23 @@ bool SessionBatch::SplitTickTwoLaunches(int calling) const {
     return calling > kSplitFusedRounds * resident;
 }
 
+// Host state only: every tick launch takes its view as a kernel argument, so the ticks already enqueued keep theirs.
+int32_t SessionBatch::SetSessionTrace(void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks) {
+    if (!trace_dev) {
+        trace_records_ = nullptr;
+        tick_.AttachTrace(false);
+        return 0;
+    }
+    // the kernels store the records as 32-bit words: a pointer that is not a multiple of 4 would fault on the GPU
+    if ((reinterpret_cast<uintptr_t>(trace_dev) & 3) || session_stride <= 0 || tick_stride <= 0 || ring_ticks <= 0) return AECM_BAD_PARAMETER_ERROR;
+    trace_records_ = static_cast<uint32_t *>(trace_dev);
+    trace_session_stride_ = session_stride;
+    trace_tick_stride_ = tick_stride;
+    trace_ring_ticks_ = ring_ticks;
+    tick_.AttachTrace(true);
+    return 0;
+}
+
 int32_t SessionBatch::CheckSession(int session) const {
     if (tick_.fs == 0) return AECM_UNINITIALIZED_ERROR;
     if (poisoned_) return AECM_UNSPECIFIED_ERROR;
@@ -401,6 +418,9 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
                    flags_per_session ? flags_dev_[slot] : nullptr, ms, flags & (kNoFarend | kSplitCalls), tick_.fs};      // (fs: the object's; mixed planning goes by the session's)
     // nothing of this tick has been enqueued (device pointers: no staging copies): a refused event leaves no poison
     if (!WaitForCallerEvent(wait_event)) return AECM_BAD_PARAMETER_ERROR;
+    // the records of this tick, by its number: the count before Commit moves it (a trace is attached: calls == 1, CheckArgs)
+    const bool traced = tick_.trace_attached;
+    const SessionTraceView tv{trace_records_, trace_session_stride_, (tick_.trace_ticks % trace_ring_ticks_) * trace_tick_stride_, (uint32_t)tick_.trace_ticks};
     // ---- commit: the tick is certain to be enqueued.  Behind the accepted wait, before the first launch: the position has moved
     // even when a launch fails (the object is then poisoned).
     tick_.Commit(plan);
@@ -410,13 +430,15 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     bool ok = false;
     switch (plan.family) {
     case kTickFamily_dense:
-        ok = AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
+        ok = traced ? AECM_HIP_OK(LaunchTickFlowTraced(engine_->state_ptrs(), tio, fio, tv, S, st)) : AECM_HIP_OK(LaunchTickFlow(engine_->state_ptrs(), tio, fio, S, st));
         break;
     case kTickFamily_sparse:
     case kTickFamily_mixed: {
         // (a sparse plan for a tick everybody makes -- the lags are brought up to date --: the dense tick kernel, no live list)
         const TickSparseIo dense_tick{near_ring_, clean_ring_, kRing, nullptr, nullptr, route.deferred_lag};
-        ok = AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, route.sparse_tick ? sp : dense_tick, S, plan.live, st, plan.mixed_plan));
+        const TickSparseIo &lists = route.sparse_tick ? sp : dense_tick;
+        ok = traced ? AECM_HIP_OK(LaunchTickFlowSparseTraced(engine_->state_ptrs(), tio, fio, lists, tv, S, plan.live, st, plan.mixed_plan))
+                    : AECM_HIP_OK(LaunchTickFlowSparse(engine_->state_ptrs(), tio, fio, lists, S, plan.live, st, plan.mixed_plan));
         break;
     }
     case kTickFamily_calls:
@@ -432,7 +454,8 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         TickSparseIo lists = sp;
         lists.live = split_live_dev_;
         const TickSplitIo split{bases_dev_[slot] + tick_.live_bases.size(), plan.clean_count, plan.plain_count, FlowPlainListStart((uint32_t)plan.clean_count)};
-        ok = AECM_HIP_OK(LaunchTickSplit(engine_->state_ptrs(), tio, fio, lists, split, S, plan.mixed_plan, SplitTickTwoLaunches(plan.live), st));
+        ok = traced ? AECM_HIP_OK(LaunchTickSplitTraced(engine_->state_ptrs(), tio, fio, lists, split, tv, S, plan.mixed_plan, SplitTickTwoLaunches(plan.live), st))
+                    : AECM_HIP_OK(LaunchTickSplit(engine_->state_ptrs(), tio, fio, lists, split, S, plan.mixed_plan, SplitTickTwoLaunches(plan.live), st));
         break;
     }
     default: break;      // (kTickFamily_nothing has returned above)

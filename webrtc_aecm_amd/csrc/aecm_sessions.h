@@ -115,6 +115,13 @@ public:
     // Diagnostics (tools/bench_sessions.py): every tick through the live list and the sparse tick kernel, idle sessions or
     // not -- what the indirection itself costs.
     void ForceSparseTicks(bool on) { tick_.force_sparse = on; }
+    // The session trace (include/aecm_batch.h: AecmSessionTrace has the contract).  While one is attached every tick of one call
+    // pair runs the traced twin of its tick launch (aecm_tick_trace_kernels.hip) behind the same planning launch, and tick j since
+    // attachment has session s write its record at trace_dev + 64 * (s * session_stride + (j % ring_ticks) * tick_stride); ticks of
+    // several calls are refused (TickObject::CheckArgs), the count moves in TickObject::Commit.  The view travels as a kernel
+    // argument, so attaching and detaching are ordered behind the ticks already enqueued.  nullptr detaches.
+    int32_t SetSessionTrace(void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks);
+    int64_t session_trace_ticks() const { return tick_.trace_ticks; }
 
     // Snapshot of ONE live session (checkpoint; migration into another object, on another GPU): everything the reference
     // keeps per instance -- AecMobile's wrapper members and jitter buffer (echo_control_mobile.cc:42-79), the core's frame
@@ -160,6 +167,10 @@ private:
     // the near position, the lags, the clean history -- and the planner of a tick: aecm_tick_plan.h.  Only TickObject's own
     // methods write it.
     TickObject tick_;
+    // what SetSessionTrace attached (tick_.trace_attached says whether; tick_.trace_ticks is the count): the base, the strides, the ring
+    uint32_t *trace_records_ = nullptr;
+    int64_t trace_session_stride_ = 0, trace_tick_stride_ = 0;
+    int32_t trace_ring_ticks_ = 1;
     int split_two_launches_ = -1;
     bool SplitTickTwoLaunches(int calling) const;
     uint32_t *split_live_dev_ = nullptr;       // [FlowSplitListEntries(S)] the two lists of a split tick; allocated by the first one

@@ -70,6 +70,11 @@ struct TickObject {
     int64_t near_pos = 0;                    // near-end samples ticked so far = ring position of the next tick's first one
     FlowObjectLag lag;                       // aecm_flow_plan.h: FlowRouteTick
     FlowCleanHistory history;                // what every session's Process calls carried (kNoClean)
+    // The session trace (include/aecm_batch.h: WebRtcAecmSessions_SetSessionTrace): whether one is attached -- the caller's switch,
+    // like force_sparse, which no Init touches -- and the ticks accepted since it was (AttachTrace zeroes the count; only Commit moves it).
+    bool trace_attached = false;
+    int64_t trace_ticks = 0;
+    void AttachTrace(bool on) { trace_attached = on; trace_ticks = 0; }
     // scratch of Plan, read by whoever launches that plan: FlowLiveBlockBases of the tick's flags [ceil(S / kFlowPlanBlock)], and
     // FlowScanFlagsClean of a split tick's [2][the same]
     mutable std::vector<uint32_t> live_bases, split_bases;
@@ -120,6 +125,9 @@ struct TickObject {
         if (!fast_variant) return kTickUnsupported;
         // K calls per row of a session of the other rate is a layout of its own: the packed rows of a packet tick
         if (calls > 1 && other_rates > 0 && !packets) return kTickUnsupported;
+        // a session trace has one record per tick of ONE call pair: the K-call and packet ticks keep the core state in registers
+        // across their calls and have no traced twins
+        if (calls > 1 && trace_attached) return kTickUnsupported;
         return 0;
     }
 
@@ -171,11 +179,12 @@ struct TickObject {
     // The bases the planning launch of `p` reads: both lists' of a split tick, one behind the other, else the live list's.
     const std::vector<uint32_t> &Bases(const TickPlan &p) const { return p.split_tick ? split_bases : live_bases; }
 
-    // The planned tick is certain to be made: the only place that moves near_pos, lag and the clean history.  (A tick nobody
-    // makes gives no session a Process call: the history stays.)
+    // The planned tick is certain to be made: the only place that moves near_pos, lag, the clean history and the session trace's
+    // tick count.  (A tick nobody makes gives no session a Process call: the history stays; it writes no record and still counts.)
     void Commit(const TickPlan &p) {
         near_pos += p.span;
         lag = p.lag_after;
+        if (trace_attached) ++trace_ticks;
         if (p.route.launch) history.Commit(p.flags_per_session, p.had_clean, p.clean_tick);
     }
     // Check, plan and -- accepted -- commit in one, for a caller with nothing between the steps (the simulators under tests/sim/:

@@ -76,7 +76,14 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_TickCalls", "WebRtcAecmSessions_TickCallsHost", "WebRtcAecmSessions_TickCallsAsync",
     "WebRtcAecmSessions_TickPackets", "WebRtcAecmSessions_TickPacketsHost", "WebRtcAecmSessions_TickPacketsAsync",
     "WebRtcAecmSessions_GetSessionCleanMode", "WebRtcAecmSessions_SplitCleanTwoLaunches",
+    "WebRtcAecmSessions_session_trace_size_bytes", "WebRtcAecmSessions_SetSessionTrace", "WebRtcAecmSessions_GetSessionTraceTicks",
 ]
+# include/aecm_batch.h: AecmSessionTrace -- the 64-byte record a session writes per tick while a trace is attached
+# (AecmSessions.set_session_trace); `core` is the block trace's record of the core state after the tick's last block
+SESSION_TRACE_DTYPE = np.dtype([
+    ("tick", "<u4"), ("blocks", "<i2"), ("samp_khz", "<i2"), ("ms_in_snd_card_buf", "<i2"), ("known_delay", "<i2"),
+    ("filt_delay", "<i2"), ("buf_size_start", "<i2"), ("ec_startup", "<i2"), ("check_buff_size", "<i2"), ("delay_change", "<i2"),
+    ("last_delay_diff", "<i2"), ("far_buffered", "<i4"), ("time_for_delay_change", "<i4"), ("core", BLOCK_TRACE_DTYPE)])
 SESSION_NO_FAREND = 1
 SESSION_SPLIT_CALLS = 2
 SESSION_IDLE = 4
@@ -217,6 +224,11 @@ def load():
     lib.WebRtcAecmSessions_ForceSparseTicks.argtypes = [vp, C.c_int32]
     lib.WebRtcAecmSessions_GetSessionCleanMode.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.WebRtcAecmSessions_SplitCleanTwoLaunches.argtypes = [vp, C.c_int32]
+    if hasattr(lib, "WebRtcAecmSessions_SetSessionTrace"):      # (a library of an older tree, loaded for an A/B run, has none)
+        lib.WebRtcAecmSessions_session_trace_size_bytes.restype = C.c_size_t
+        lib.WebRtcAecmSessions_session_trace_size_bytes.argtypes = []
+        lib.WebRtcAecmSessions_SetSessionTrace.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32]
+        lib.WebRtcAecmSessions_GetSessionTraceTicks.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.WebRtcAecmSessions_InitRates.argtypes = [vp, C.c_int32, vp]
     lib.WebRtcAecmSessions_InitSessionRate.argtypes = [vp, C.c_int32, C.c_int32]
     lib.WebRtcAecmSessions_GetSessionRate.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
@@ -932,6 +944,23 @@ class AecmSessions:
         False: always the fused launch, None: by the size of the tick (the default of a new object)."""
         return self.lib.WebRtcAecmSessions_SplitCleanTwoLaunches(self.h, -1 if on is None else 1 if on else 0)
 
+    def set_session_trace(self, ptr, session_stride, tick_stride, ring_ticks) -> int:
+        """Attach a session trace (include/aecm_batch.h: WebRtcAecmSessions_SetSessionTrace): ptr = device memory for
+        SESSION_TRACE_DTYPE records; tick j since attachment writes session s's record at record index
+        s * session_stride + (j % ring_ticks) * tick_stride.  Returns the code."""
+        return self.lib.WebRtcAecmSessions_SetSessionTrace(self.h, ptr, session_stride, tick_stride, ring_ticks)
+
+    def clear_session_trace(self) -> int:
+        return self.lib.WebRtcAecmSessions_SetSessionTrace(self.h, None, 0, 0, 0)
+
+    def session_trace_ticks(self) -> int:
+        """Ticks accepted since the trace was attached (0 while none is)."""
+        ticks = C.c_int64(-1)
+        rc = self.lib.WebRtcAecmSessions_GetSessionTraceTicks(self.h, C.byref(ticks))
+        if rc != 0:
+            raise RuntimeError(f"WebRtcAecmSessions_GetSessionTraceTicks: {rc}")
+        return ticks.value
+
     def force_sparse_ticks(self, on: bool = True) -> int:
         """Diagnostics: every tick through the live list and the sparse tick kernel (WebRtcAecmSessions_ForceSparseTicks)."""
         return self.lib.WebRtcAecmSessions_ForceSparseTicks(self.h, 1 if on else 0)
@@ -1064,6 +1093,10 @@ def describe_launch_detail(num_streams: int, num_blocks: int, compute_units: int
 
 def block_trace_size_bytes() -> int:
     return load().WebRtcAecmBatch_block_trace_size_bytes()
+
+
+def session_trace_size_bytes() -> int:
+    return load().WebRtcAecmSessions_session_trace_size_bytes()
 
 
 def describe_traced_launch(num_streams: int, num_blocks: int, compute_units: int = 0, clean: bool = False, policy=None) -> dict:
