@@ -497,7 +497,7 @@ size_t WebRtcAecmSessions_session_trace_size_bytes(void);      /* 64 */
  *    WebRtcAecmSessions_BufferFarend* writes no record.
  *  - While a trace is attached, TickCalls* / TickPackets* with calls > 1 return AECM_UNSUPPORTED_FUNCTION_ERROR and change nothing:
  *    not the sessions, not the position, not the tick count.  (Those ticks keep the core state in registers across their calls; a
- *    record per call from that loop is the follow-up.)
+ *    record per call from that loop is the call trace's, below: WebRtcAecmSessions_SetCallTrace.)
  *  - A refused tick of any kind does not advance the count.
  *  - With TickAsync the records are visible where out is: behind done_hip_event or WebRtcAecmSessions_Synchronize.
  *  - SetSessionTrace is ordered behind the ticks already enqueued: they write where they were told to when they were enqueued.
@@ -506,6 +506,39 @@ size_t WebRtcAecmSessions_session_trace_size_bytes(void);      /* 64 */
 int32_t WebRtcAecmSessions_SetSessionTrace(AecmSessions *s, void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks);
 /* *ticks = the ticks accepted since the trace was attached (0 while none is attached).  Needs no device. */
 int32_t WebRtcAecmSessions_GetSessionTraceTicks(AecmSessions *s, int64_t *ticks);
+
+/* ---- Call trace: one AecmSessionTrace record per session and CALL PAIR, K-call and packet ticks too ------------------------------
+ * The session trace above refuses the ticks a packet server runs on (TickCalls* / TickPackets* with calls > 1).  The call trace is a
+ * second, separate opt-in with the same record and a switch of its own: while it is attached the object counts CALL SLOTS -- an
+ * accepted tick with argument calls = K advances the count by K, an ordinary tick or Process by 1 -- and every session that calls
+ * writes one 64-byte AecmSessionTrace record per call slot.  The struct is unchanged; its `tick` field holds the slot number j + c for
+ * call c of a tick that started at count j, and the record lies at
+ *     trace_dev + 64 * (s * session_stride + ((j + c) % ring_calls) * call_stride).
+ * The contract: the buffer after a K-call or packet tick is byte for byte the buffer that K ordinary ticks under SetSessionTrace
+ * leave with the same geometry on the same rows (for a half-call session of a packet tick: K AECM_SESSION_HALF_CALL ticks on re-laid
+ * rows, as TickPackets defines its equivalence).  So every wrapper field is what ExportSession would show directly after that call
+ * pair, `blocks` is the blocks the core ran in that call, and `core` is AecmBlockTrace of the core state after that call's last
+ * block -- or of the state the session holds, for a call that ran none.
+ *  - ring_calls == 1 keeps the latest call's record.  With ring_calls < K the buffer is what writing the K records in order gives.
+ *  - A session that carries AECM_SESSION_IDLE gets no records: its slots keep their bytes, and the count still advances by K.  A tick
+ *    nobody makes writes nothing and still counts.
+ *  - Traced: TickCalls*, TickPackets* (Device, Host and Async forms) with any calls they accept, and everything the session trace
+ *    traces -- AECM_SESSION_NO_FAREND, per-session msInSndCardBuf, both rates, with and without a clean input.  With calls == 1 a
+ *    tick is the session trace's tick with the slot number as its number (AECM_SESSION_SPLIT_CALLS / AECM_SESSION_HALF_CALL: one
+ *    record for the slot).  WebRtcAecmSessions_BufferFarend* writes no record and does not count.
+ *  - Everything TickCalls* / TickPackets* refuse without a trace is refused with one (a calling AECM_SESSION_NO_CLEAN session with
+ *    calls > 1 and a clean plane; the safe kernel variant; ...), and a refused tick changes nothing: not the sessions, not the
+ *    position, not the count.
+ *  - Records are visible where out is; SetCallTrace is ordered behind the ticks already enqueued, without a synchronisation.
+ *  - At most one of the two traces is attached: SetCallTrace while a session trace is attached, and SetSessionTrace while a call
+ *    trace is, return AECM_BAD_PARAMETER_ERROR and leave the attached one attached.  NULL detaches only its own kind.
+ *    GetSessionTraceTicks keeps answering for the session trace only (0 while a call trace is attached).
+ * An object that never calls SetCallTrace launches the kernels and gives the refusals it always did.
+ * Returns 0, or AECM_BAD_PARAMETER_ERROR with nothing changed for a NULL object, a pointer that is not 4-byte aligned, a
+ * stride <= 0, ring_calls <= 0, or a session trace that is attached.  Attaching (again) starts the count at 0. */
+int32_t WebRtcAecmSessions_SetCallTrace(AecmSessions *s, void *trace_dev, int64_t session_stride, int64_t call_stride, int32_t ring_calls);
+/* *calls = the call slots counted since the call trace was attached (0 while none is attached).  Needs no device. */
+int32_t WebRtcAecmSessions_GetCallTraceCalls(AecmSessions *s, int64_t *calls);
 
 /* Zero-copy host audio.  A caller-owned host buffer is pinned and mapped into the device's address space once
  * (hipHostRegister); *device_alias is then a device pointer that every *_dev argument of this header accepts

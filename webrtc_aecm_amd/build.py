@@ -24,7 +24,7 @@ CLI = LIB_DIR / "aecm_run"
 KERNEL_SOURCES = ["aecm_block_kernels.hip", "aecm_kernels.hip", "aecm_session_snapshot_kernels.hip", "aecm_tick_calls_kernels.hip",
                   "aecm_tick_calls_plan_kernels.hip", "aecm_tick_packets_kernels.hip", "aecm_tick_packets_plan_kernels.hip",
                   "aecm_tick_split_kernels.hip", "aecm_tick_split_plan_kernels.hip", "aecm_tick_trace_kernels.hip", "aecm_trace_kernels.hip",
-                  "aecm_ops_probe_kernels.hip"]
+                  "aecm_call_trace_kernels.hip", "aecm_call_trace_plan_kernels.hip", "aecm_ops_probe_kernels.hip"]
 HOST_SOURCES = ["aecm_engine.cpp", "aecm_session.cpp", "aecm_schedule.cpp", "aecm_sessions.cpp", "aecm_capi.cpp", "aecm_host_state.cpp"]
 SOURCES = KERNEL_SOURCES + HOST_SOURCES
 # Per-source flags.  The kernels branch on wave-uniform conditions only; leaving those regions unstructurized is worth +6 %
@@ -43,6 +43,9 @@ SOURCE_FLAGS = {"aecm_block_kernels.hip": UNIFORM_BRANCH_FLAGS + KEEP_BRANCHES_F
                 "aecm_tick_split_kernels.hip": UNIFORM_BRANCH_FLAGS,      # (the split tick, AECM_SESSION_NO_CLEAN: likewise)
                 # the traced twins of the tick kernels (session trace): the tick units' flags, so that a trace observes the code that ships
                 "aecm_tick_trace_kernels.hip": UNIFORM_BRANCH_FLAGS,
+                # the traced twins of the K-call and packet tick kernels (call trace): likewise (their planning twins,
+                # aecm_call_trace_plan_kernels.hip -- one lane per session, as aecm_tick_calls_plan_kernels.hip -- take no flags of their own)
+                "aecm_call_trace_kernels.hip": UNIFORM_BRANCH_FLAGS,
                 # the traced twins of the block kernels (block trace): the block kernels' flags, so that a trace observes the code that ships
                 "aecm_trace_kernels.hip": UNIFORM_BRANCH_FLAGS + KEEP_BRANCHES_FLAGS,
                 # the ops probe (diagnostics: each primitive of aecm_ops.h alone): the block kernels' flags, so that it probes them as they ship

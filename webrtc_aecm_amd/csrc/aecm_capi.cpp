@@ -901,6 +901,19 @@ int32_t WebRtcAecmSessions_GetSessionTraceTicks(AecmSessions *s, int64_t *ticks)
     return 0;
 }
 
+// The call trace: the same record per call slot.
+int32_t WebRtcAecmSessions_SetCallTrace(AecmSessions *s, void *trace_dev, int64_t session_stride, int64_t call_stride, int32_t ring_calls) {
+    if (!s) return AECM_BAD_PARAMETER_ERROR;
+    return s->batch->SetCallTrace(trace_dev, session_stride, call_stride, ring_calls);
+}
+
+int32_t WebRtcAecmSessions_GetCallTraceCalls(AecmSessions *s, int64_t *calls) {
+    if (!s) return AECM_BAD_PARAMETER_ERROR;
+    if (!calls) return AECM_NULL_POINTER_ERROR;
+    *calls = s->batch->call_trace_calls();
+    return 0;
+}
+
 int32_t WebRtcAecmSessions_SetKernelVariant(AecmSessions *s, int32_t variant) {
     if (!s) return -1;
     if (variant != AECM_KERNEL_SAFE && variant != AECM_KERNEL_FAST) return AECM_BAD_PARAMETER_ERROR;

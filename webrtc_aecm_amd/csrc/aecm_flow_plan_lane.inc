@@ -18,6 +18,13 @@
 //                                 fio.plans[s][kFlowPlanWords]
 //   AECM_FLOW_PLAN_CALLS(emit)    plans `calls` (in scope) call pairs, handing every one to emit(c, plan) (FlowTickCalls,
 //                                 FlowTickPackets); the plans go to fio.plans[s][calls][kFlowPlanWords]
+// and, with AECM_FLOW_PLAN_CALLS only, an optional statement at the end of emit, with c, p and -- directly behind call c's FlowTick
+// -- r in scope (nothing where the includer defines none: every kernel without it keeps its tokens):
+//   AECM_FLOW_PLAN_CALL_RECORD    the call trace's planning kernels (aecm_call_trace_plan_kernels.hip) store the wrapper half of
+//                                 call c's record here
+#if !defined(AECM_FLOW_PLAN_CALL_RECORD)
+#define AECM_FLOW_PLAN_CALL_RECORD
+#endif
     if (!in_range) return;
     int32_t *lag = fio.state + (size_t)F_NEAR_LAG * n_streams + s;
     if (!live) {
@@ -50,8 +57,10 @@
         int32_t w[kFlowPlanWords];
         FlowPackPlan(p, w);
         for (int q = 0; q < kFlowPlanWords / 4; ++q) dst[c * (kFlowPlanWords / 4) + q] = make_int4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
+        AECM_FLOW_PLAN_CALL_RECORD
     }));
     for (int k = 0; k < kFlowFieldsUsed; ++k) fio.state[(size_t)k * n_streams + s] = r.v[k];
 #undef AECM_FLOW_PLAN_CALLS
 #endif
+#undef AECM_FLOW_PLAN_CALL_RECORD
 #undef AECM_FLOW_PLAN_IDLE_SAMPLES

@@ -246,12 +246,30 @@ hipError_t LaunchPlanFlow(const StatePtrs &st, const TickIo &io, const TickFlowI
 // include/aecm_batch.h: AecmSessionTrace): the planning launches are the ones above, unchanged; the tick launch is the traced twin of
 // the untraced one, and every session it serves also writes its 64-byte record to
 // tv.records + kSessionTraceWords * (s * tv.session_stride + tv.tick_slot_offset) (aecm_session_trace.h: SessionTraceView; tv.records
-// must not be null).  The other arguments and the results are those of the launches above.  There is no traced K-call / packet tick.
+// must not be null).  The other arguments and the results are those of the launches above.  (The traced K-call / packet ticks are the
+// call trace's, below.)
 hipError_t LaunchTickFlowTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const SessionTraceView &tv, int n_streams, hipStream_t stream);
 hipError_t LaunchTickFlowSparseTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const SessionTraceView &tv,
                                       int n_streams, int live_count, hipStream_t stream, bool mixed_plan = false);
 hipError_t LaunchTickSplitTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split,
                                  const SessionTraceView &tv, int n_streams, bool mixed_plan, bool two_launches, hipStream_t stream);
+// The K-call and the packet tick with a call trace attached (aecm_call_trace_plan_kernels.hip, aecm_call_trace_kernels.hip;
+// include/aecm_batch.h: WebRtcAecmSessions_SetCallTrace): LaunchTickCalls / LaunchTickPackets by twins of both of their kernels, and
+// every session that calls also gets one record per call (aecm_session_trace.h: CallTraceView has the placement; cv.records must
+// not be null) --
+//   aecm_plan_calls_traced_kernel / aecm_plan_packets_traced_kernel             the planning lane stores words 0..7 of call c's
+//                                   record as it plans call c, from its own registers
+//   aecm_calls_traced_tick_kernel / aecm_packets_traced_tick_kernel             lanes 0..7 store words 8..15 behind call c's blocks
+// The other arguments and the results are those of the untraced launches.
+hipError_t LaunchTickCallsTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const CallTraceView &cv, int n_streams,
+                                 int live_count, int calls, hipStream_t stream);
+hipError_t LaunchTickPacketsTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const CallTraceView &cv, int n_streams,
+                                   int live_count, int calls, hipStream_t stream);
+// The planning launches alone (aecm_call_trace_plan_kernels.hip; the two above call them).
+hipError_t LaunchPlanCallsTraced(const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const CallTraceView &cv, int n_streams, int calls,
+                                 hipStream_t stream);
+hipError_t LaunchPlanPacketsTraced(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const CallTraceView &cv, int n_streams,
+                                   int calls, hipStream_t stream);
 int TickWorkgroupWaves();        // sessions per workgroup of the tick kernel
 int TickWorkgroupsPerCu();       // workgroups of it a CU holds at once
 // Far-end bursts: WebRtcAecm_BufferFarend calls WITHOUT a Process (reference echo_control_mobile.cc:215-234), one wavefront
@@ -283,6 +301,8 @@ hipError_t ReadBlockKernelCheckCounters(uint64_t counters[2], bool reset);
 hipError_t ReadTraceKernelCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_trace_kernels.hip (the traced tick kernels); ReadCheckCounters adds it in as well.  Does not synchronise.
 hipError_t ReadTickTraceCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_call_trace_kernels.hip (the traced K-call and packet tick kernels); ReadCheckCounters adds it in as well.  Does not synchronise.
+hipError_t ReadCallTraceCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_calls_kernels.hip, for callers that audit K-call ticks (ReadCheckCounters does not add it in).  Does not synchronise.
 hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_packets_kernels.hip, likewise.

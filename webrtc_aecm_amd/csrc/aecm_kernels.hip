@@ -9,14 +9,16 @@
 namespace aecm {
 
 AECM_DEFINE_CHECK_COUNTERS(ReadThisUnitCheckCounters)      // (used below only)
-// Audit counters of the -DAECM_CHECKED build (aecm_ops.h): this unit's pair, the block kernels', the traced block kernels' and the
-// traced tick kernels', behind everything the device still has to do; hipErrorNotSupported in the shipped build.
+// Audit counters of the -DAECM_CHECKED build (aecm_ops.h): this unit's pair, the block kernels', the traced block kernels', the
+// traced tick kernels' and the traced K-call / packet tick kernels', behind everything the device still has to do;
+// hipErrorNotSupported in the shipped build.
 hipError_t ReadCheckCounters(uint64_t counters[2], bool reset) {
 #if defined(AECM_CHECKED)
     hipError_t e = hipDeviceSynchronize();
     if (e != hipSuccess) return e;
     uint64_t sum[2] = {0, 0};
-    for (const auto read : {ReadThisUnitCheckCounters, ReadBlockKernelCheckCounters, ReadTraceKernelCheckCounters, ReadTickTraceCheckCounters}) {
+    for (const auto read : {ReadThisUnitCheckCounters, ReadBlockKernelCheckCounters, ReadTraceKernelCheckCounters, ReadTickTraceCheckCounters,
+                            ReadCallTraceCheckCounters}) {
         uint64_t share[2] = {0, 0};
         e = read(share, reset);
         if (e != hipSuccess) return e;

@@ -141,18 +141,34 @@ bool SessionBatch::SplitTickTwoLaunches(int calling) const {
 
 // Host state only: every tick launch takes its view as a kernel argument, so the ticks already enqueued keep theirs.
 int32_t SessionBatch::SetSessionTrace(void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks) {
-    if (!trace_dev) {
+    if (!trace_dev) {      // (detaches its own kind only: a call trace stays)
         trace_records_ = nullptr;
         tick_.AttachTrace(false);
         return 0;
     }
     // the kernels store the records as 32-bit words: a pointer that is not a multiple of 4 would fault on the GPU
     if ((reinterpret_cast<uintptr_t>(trace_dev) & 3) || session_stride <= 0 || tick_stride <= 0 || ring_ticks <= 0) return AECM_BAD_PARAMETER_ERROR;
+    if (!tick_.AttachTrace(true)) return AECM_BAD_PARAMETER_ERROR;       // at most one of the two traces: a call trace is attached
     trace_records_ = static_cast<uint32_t *>(trace_dev);
     trace_session_stride_ = session_stride;
     trace_tick_stride_ = tick_stride;
     trace_ring_ticks_ = ring_ticks;
-    tick_.AttachTrace(true);
+    return 0;
+}
+
+// Host state only, as SetSessionTrace.
+int32_t SessionBatch::SetCallTrace(void *trace_dev, int64_t session_stride, int64_t call_stride, int32_t ring_calls) {
+    if (!trace_dev) {      // (detaches its own kind only: a session trace stays)
+        call_trace_records_ = nullptr;
+        tick_.AttachCallTrace(false);
+        return 0;
+    }
+    if ((reinterpret_cast<uintptr_t>(trace_dev) & 3) || session_stride <= 0 || call_stride <= 0 || ring_calls <= 0) return AECM_BAD_PARAMETER_ERROR;
+    if (!tick_.AttachCallTrace(true)) return AECM_BAD_PARAMETER_ERROR;   // at most one of the two traces: a session trace is attached
+    call_trace_records_ = static_cast<uint32_t *>(trace_dev);
+    call_trace_session_stride_ = session_stride;
+    call_trace_call_stride_ = call_stride;
+    call_trace_ring_calls_ = ring_calls;
     return 0;
 }
 
@@ -418,9 +434,15 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
                    flags_per_session ? flags_dev_[slot] : nullptr, ms, flags & (kNoFarend | kSplitCalls), tick_.fs};      // (fs: the object's; mixed planning goes by the session's)
     // nothing of this tick has been enqueued (device pointers: no staging copies): a refused event leaves no poison
     if (!WaitForCallerEvent(wait_event)) return AECM_BAD_PARAMETER_ERROR;
-    // the records of this tick, by its number: the count before Commit moves it (a trace is attached: calls == 1, CheckArgs)
-    const bool traced = tick_.trace_attached;
-    const SessionTraceView tv{trace_records_, trace_session_stride_, (tick_.trace_ticks % trace_ring_ticks_) * trace_tick_stride_, (uint32_t)tick_.trace_ticks};
+    // the records of this tick, by its number: the count before Commit moves it (a session trace is attached: calls == 1, CheckArgs).
+    // With a call trace the numbers are call slots: the first slot of this tick for the K-call and packet families (cv); a tick of
+    // one call pair is the session trace's tick with its slot as the tick number (tv).
+    const bool call_traced = tick_.call_trace_attached, traced = tick_.trace_attached || call_traced;
+    const int64_t first_call = tick_.call_trace_calls, first_slot = first_call % call_trace_ring_calls_;
+    const CallTraceView cv{call_trace_records_, call_trace_session_stride_, call_trace_call_stride_, call_trace_ring_calls_, (int32_t)first_slot, (uint32_t)first_call};
+    const SessionTraceView tv = call_traced ? SessionTraceView{call_trace_records_, call_trace_session_stride_, first_slot * call_trace_call_stride_, (uint32_t)first_call}
+                                            : SessionTraceView{trace_records_, trace_session_stride_, (tick_.trace_ticks % trace_ring_ticks_) * trace_tick_stride_,
+                                                               (uint32_t)tick_.trace_ticks};
     // ---- commit: the tick is certain to be enqueued.  Behind the accepted wait, before the first launch: the position has moved
     // even when a launch fails (the object is then poisoned).
     tick_.Commit(plan);
@@ -443,12 +465,14 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
     }
     case kTickFamily_calls:
         fio.plans = calls_plans_;
-        ok = AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, plan.live, calls, st));
+        ok = call_traced ? AECM_HIP_OK(LaunchTickCallsTraced(engine_->state_ptrs(), tio, fio, sp, cv, S, plan.live, calls, st))
+                         : AECM_HIP_OK(LaunchTickCalls(engine_->state_ptrs(), tio, fio, sp, S, plan.live, calls, st));
         break;
     case kTickFamily_packets:      // the packed layout and its kernels
         fio.plans = calls_plans_;
         fio.flags = flags & kNoFarend;
-        ok = AECM_HIP_OK(LaunchTickPackets(engine_->state_ptrs(), tio, fio, sp, S, plan.live, calls, st));
+        ok = call_traced ? AECM_HIP_OK(LaunchTickPacketsTraced(engine_->state_ptrs(), tio, fio, sp, cv, S, plan.live, calls, st))
+                         : AECM_HIP_OK(LaunchTickPackets(engine_->state_ptrs(), tio, fio, sp, S, plan.live, calls, st));
         break;
     case kTickFamily_split: {
         TickSparseIo lists = sp;

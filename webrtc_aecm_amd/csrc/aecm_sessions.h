@@ -122,6 +122,13 @@ public:
     // argument, so attaching and detaching are ordered behind the ticks already enqueued.  nullptr detaches.
     int32_t SetSessionTrace(void *trace_dev, int64_t session_stride, int64_t tick_stride, int32_t ring_ticks);
     int64_t session_trace_ticks() const { return tick_.trace_ticks; }
+    // The call trace (include/aecm_batch.h: WebRtcAecmSessions_SetCallTrace has the contract): the same record per CALL SLOT.  While
+    // one is attached the object counts call slots (TickObject::Commit: a tick of K call pairs moves the count by K), a tick of one
+    // call pair runs the session trace's twins with the slot number as its tick, and a K-call or packet tick runs the traced twins
+    // of both of its launches (aecm_call_trace_plan_kernels.hip, aecm_call_trace_kernels.hip).  At most one of the two traces is
+    // attached: either call refuses while the other kind is.  The view travels as a kernel argument, as the session trace's.
+    int32_t SetCallTrace(void *trace_dev, int64_t session_stride, int64_t call_stride, int32_t ring_calls);
+    int64_t call_trace_calls() const { return tick_.call_trace_calls; }
 
     // Snapshot of ONE live session (checkpoint; migration into another object, on another GPU): everything the reference
     // keeps per instance -- AecMobile's wrapper members and jitter buffer (echo_control_mobile.cc:42-79), the core's frame
@@ -171,6 +178,10 @@ private:
     uint32_t *trace_records_ = nullptr;
     int64_t trace_session_stride_ = 0, trace_tick_stride_ = 0;
     int32_t trace_ring_ticks_ = 1;
+    // what SetCallTrace attached (tick_.call_trace_attached says whether; tick_.call_trace_calls is the count)
+    uint32_t *call_trace_records_ = nullptr;
+    int64_t call_trace_session_stride_ = 0, call_trace_call_stride_ = 0;
+    int32_t call_trace_ring_calls_ = 1;
     int split_two_launches_ = -1;
     bool SplitTickTwoLaunches(int calling) const;
     uint32_t *split_live_dev_ = nullptr;       // [FlowSplitListEntries(S)] the two lists of a split tick; allocated by the first one

@@ -7,6 +7,13 @@
 //   AECM_TICK_CALLS_SIZE_OF_LAUNCH   `const int n = io.n;` for the K-call tick (every session makes calls of the launch's n), else empty
 //   AECM_TICK_CALLS_SIZE_OF_PLAN     `const int n = p.n_frames * kFlowFrame;` for the packet tick (the SESSION's call size, wave-uniform,
 //                                    the same in all of its K plans: rows packed, near positions contiguous), else empty
+// One optional hook, nothing where the includer defines none (every kernel without it keeps its tokens):
+//   AECM_TICK_CALLS_AFTER_BLOCKS     a statement behind step 4 of every call, with c, p and r -- the core state behind call c's last
+//                                    block, or as loaded for a call that ran none -- in scope: the call trace's tick kernels
+//                                    (aecm_call_trace_kernels.hip) store the core half of call c's record here
+#if !defined(AECM_TICK_CALLS_AFTER_BLOCKS)
+#define AECM_TICK_CALLS_AFTER_BLOCKS
+#endif
     const int64_t wave_id = (int64_t)blockIdx.x * kTickCallsWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     AECM_TICK_LIVE_SESSION(live, live_count, wave_id)
     const int lane_id = threadIdx.x & 63;
@@ -118,6 +125,7 @@
         } else {
             append();                    // a call of the start-up phase: no blocks, but the rings take its samples
         }
+        AECM_TICK_CALLS_AFTER_BLOCKS
         // the block outputs before the output frames read them; the call's appended samples, framed samples and replay
         // rows before call c + 1 reads them
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -139,3 +147,4 @@
         }
     }
     if (ran) E::store_state(r, vec, scal);
+#undef AECM_TICK_CALLS_AFTER_BLOCKS

@@ -43,6 +43,7 @@ struct TickPlan {
     int32_t code = 0;                  // 0, kTickBadParameter or kTickUnsupported; refused: only `code` means anything
     int32_t live = 0;                  // sessions that call
     int32_t span = 0;                  // the samples of the tick in every row: n * calls
+    int32_t calls = 1;                 // the tick's argument: the call slots a call trace counts for it
     uint8_t any = 0;                   // the OR of the calling sessions' flag bytes
     bool half_calls = false;           // some session that calls makes a half call
     bool k_calls = false;              // calls > 1
@@ -70,11 +71,27 @@ struct TickObject {
     int64_t near_pos = 0;                    // near-end samples ticked so far = ring position of the next tick's first one
     FlowObjectLag lag;                       // aecm_flow_plan.h: FlowRouteTick
     FlowCleanHistory history;                // what every session's Process calls carried (kNoClean)
-    // The session trace (include/aecm_batch.h: WebRtcAecmSessions_SetSessionTrace): whether one is attached -- the caller's switch,
-    // like force_sparse, which no Init touches -- and the ticks accepted since it was (AttachTrace zeroes the count; only Commit moves it).
-    bool trace_attached = false;
-    int64_t trace_ticks = 0;
-    void AttachTrace(bool on) { trace_attached = on; trace_ticks = 0; }
+    // The session trace (include/aecm_batch.h: WebRtcAecmSessions_SetSessionTrace), the per-TICK mode: whether one is attached -- the
+    // caller's switch, like force_sparse, which no Init touches -- and the ticks accepted since it was (AttachTrace zeroes the count;
+    // only Commit moves it).
+    // The call trace (WebRtcAecmSessions_SetCallTrace), the per-CALL mode: a switch of its own, under which ticks of several calls
+    // are accepted and the count is of call slots: an accepted tick of `calls` call pairs moves it by `calls` (Commit).
+    // At most one of the two is on: switching one on while the other is on is refused (false) and changes nothing; switching off
+    // touches only its own kind.
+    bool trace_attached = false, call_trace_attached = false;
+    int64_t trace_ticks = 0, call_trace_calls = 0;
+    bool AttachTrace(bool on) {
+        if (on && call_trace_attached) return false;
+        trace_attached = on;
+        trace_ticks = 0;
+        return true;
+    }
+    bool AttachCallTrace(bool on) {
+        if (on && trace_attached) return false;
+        call_trace_attached = on;
+        call_trace_calls = 0;
+        return true;
+    }
     // scratch of Plan, read by whoever launches that plan: FlowLiveBlockBases of the tick's flags [ceil(S / kFlowPlanBlock)], and
     // FlowScanFlagsClean of a split tick's [2][the same]
     mutable std::vector<uint32_t> live_bases, split_bases;
@@ -125,8 +142,8 @@ struct TickObject {
         if (!fast_variant) return kTickUnsupported;
         // K calls per row of a session of the other rate is a layout of its own: the packed rows of a packet tick
         if (calls > 1 && other_rates > 0 && !packets) return kTickUnsupported;
-        // a session trace has one record per tick of ONE call pair: the K-call and packet ticks keep the core state in registers
-        // across their calls and have no traced twins
+        // a session trace has one record per tick of ONE call pair (the per-tick mode); a record per call of a K-call or packet tick
+        // is the call trace's, the per-call mode, which this refusal does not touch
         if (calls > 1 && trace_attached) return kTickUnsupported;
         return 0;
     }
@@ -136,6 +153,7 @@ struct TickObject {
         TickPlan p;
         const int32_t S = n_sessions;
         p.span = a.n * a.calls;
+        p.calls = a.calls;
         p.k_calls = a.calls > 1;
         // Who calls (kIdle: neither call; the other bits of an idle session's byte mean nothing).  One pass over the flags: the
         // live count, and per planning workgroup the live sessions before it (what the device needs for the live list).
@@ -179,12 +197,14 @@ struct TickObject {
     // The bases the planning launch of `p` reads: both lists' of a split tick, one behind the other, else the live list's.
     const std::vector<uint32_t> &Bases(const TickPlan &p) const { return p.split_tick ? split_bases : live_bases; }
 
-    // The planned tick is certain to be made: the only place that moves near_pos, lag, the clean history and the session trace's
-    // tick count.  (A tick nobody makes gives no session a Process call: the history stays; it writes no record and still counts.)
+    // The planned tick is certain to be made: the only place that moves near_pos, lag, the clean history, the session trace's
+    // tick count and the call trace's count of call slots.  (A tick nobody makes gives no session a Process call: the history stays;
+    // it writes no record and still counts.)
     void Commit(const TickPlan &p) {
         near_pos += p.span;
         lag = p.lag_after;
         if (trace_attached) ++trace_ticks;
+        if (call_trace_attached) call_trace_calls += p.calls;
         if (p.route.launch) history.Commit(p.flags_per_session, p.had_clean, p.clean_tick);
     }
     // Check, plan and -- accepted -- commit in one, for a caller with nothing between the steps (the simulators under tests/sim/:

@@ -1,6 +1,7 @@
 // What the wave-per-session tick units share -- aecm_kernels.hip (the dense and the sparse tick), aecm_tick_calls_kernels.hip (the
 // K-call tick), aecm_tick_packets_kernels.hip (the packet tick), aecm_tick_split_kernels.hip (the split tick),
-// aecm_tick_trace_kernels.hip (the traced twins of the dense, sparse and split ticks): where the blocks of a
+// aecm_tick_trace_kernels.hip (the traced twins of the dense, sparse and split ticks), aecm_call_trace_kernels.hip (the traced
+// twins of the K-call and the packet tick): where the blocks of a
 // tick or of one call fetch and deliver, how the kernels are built, and how a wavefront finds its session in a live list.  Included
 // behind aecm_kernel_common.h, inside namespace aecm.  The kernels' common texts are aecm_tick_flow_body.inc and
 // aecm_tick_calls_body.inc.

@@ -77,6 +77,7 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_TickPackets", "WebRtcAecmSessions_TickPacketsHost", "WebRtcAecmSessions_TickPacketsAsync",
     "WebRtcAecmSessions_GetSessionCleanMode", "WebRtcAecmSessions_SplitCleanTwoLaunches",
     "WebRtcAecmSessions_session_trace_size_bytes", "WebRtcAecmSessions_SetSessionTrace", "WebRtcAecmSessions_GetSessionTraceTicks",
+    "WebRtcAecmSessions_SetCallTrace", "WebRtcAecmSessions_GetCallTraceCalls",
 ]
 # include/aecm_batch.h: AecmSessionTrace -- the 64-byte record a session writes per tick while a trace is attached
 # (AecmSessions.set_session_trace); `core` is the block trace's record of the core state after the tick's last block
@@ -229,6 +230,9 @@ def load():
         lib.WebRtcAecmSessions_session_trace_size_bytes.argtypes = []
         lib.WebRtcAecmSessions_SetSessionTrace.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32]
         lib.WebRtcAecmSessions_GetSessionTraceTicks.argtypes = [vp, C.POINTER(C.c_int64)]
+    if hasattr(lib, "WebRtcAecmSessions_SetCallTrace"):         # (likewise)
+        lib.WebRtcAecmSessions_SetCallTrace.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int32]
+        lib.WebRtcAecmSessions_GetCallTraceCalls.argtypes = [vp, C.POINTER(C.c_int64)]
     lib.WebRtcAecmSessions_InitRates.argtypes = [vp, C.c_int32, vp]
     lib.WebRtcAecmSessions_InitSessionRate.argtypes = [vp, C.c_int32, C.c_int32]
     lib.WebRtcAecmSessions_GetSessionRate.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
@@ -960,6 +964,23 @@ class AecmSessions:
         if rc != 0:
             raise RuntimeError(f"WebRtcAecmSessions_GetSessionTraceTicks: {rc}")
         return ticks.value
+
+    def set_call_trace(self, ptr, session_stride, call_stride, ring_calls) -> int:
+        """Attach a call trace (include/aecm_batch.h: WebRtcAecmSessions_SetCallTrace): ptr = device memory for SESSION_TRACE_DTYPE
+        records, one per session and call pair -- K-call and packet ticks too; call slot j since attachment writes session s's
+        record at record index s * session_stride + (j % ring_calls) * call_stride.  Returns the code."""
+        return self.lib.WebRtcAecmSessions_SetCallTrace(self.h, ptr, session_stride, call_stride, ring_calls)
+
+    def clear_call_trace(self) -> int:
+        return self.lib.WebRtcAecmSessions_SetCallTrace(self.h, None, 0, 0, 0)
+
+    def call_trace_calls(self) -> int:
+        """Call slots counted since the call trace was attached (0 while none is)."""
+        calls = C.c_int64(-1)
+        rc = self.lib.WebRtcAecmSessions_GetCallTraceCalls(self.h, C.byref(calls))
+        if rc != 0:
+            raise RuntimeError(f"WebRtcAecmSessions_GetCallTraceCalls: {rc}")
+        return calls.value
 
     def force_sparse_ticks(self, on: bool = True) -> int:
         """Diagnostics: every tick through the live list and the sparse tick kernel (WebRtcAecmSessions_ForceSparseTicks)."""
