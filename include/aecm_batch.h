@@ -297,7 +297,12 @@ enum {
      *     (WebRtcAecmSessions_SplitCleanTwoLaunches).
      *   - TickFlagsHost stages the whole near_clean plane as always; the flagged sessions' rows are never read by a kernel.
      *   - calls > 1 (TickCalls*, TickPackets*) with a calling session that carries the flag and near_clean != NULL:
-     *     AECM_UNSUPPORTED_FUNCTION_ERROR, nothing changed.  K-call ticks of mixed kinds are not supported yet.
+     *     AECM_UNSUPPORTED_FUNCTION_ERROR, nothing changed -- unless the object's switch WebRtcAecmSessions_SetSplitCallTicks is on
+     *     (below; off in a new object).  With it, the tick is the loop written at TickCalls / TickPackets with the flagged sessions' K
+     *     Process calls getting nearendClean = NULL: none of the K pieces of a flagged session's near_clean row is read, everything
+     *     said above holds for all K calls, and the history rule is applied once per tick (a tick gives a session the same kind for
+     *     all of its calls).  While a call trace is attached (WebRtcAecmSessions_SetCallTrace), K-call ticks of mixed kinds are
+     *     not supported yet: AECM_UNSUPPORTED_FUNCTION_ERROR whatever the switch says.
      *   - Snapshots: layout, version and the export code are unchanged.  The clean tail of a "never" session's snapshot is whatever
      *     its never-read ring row holds; it influences nothing. */
     AECM_SESSION_NO_CLEAN = 16
@@ -455,6 +460,30 @@ int32_t WebRtcAecmSessions_GetSessionCleanMode(AecmSessions *s, int32_t session,
  * object): one fused launch up to four times the sessions the device holds at once, one launch per list beyond; on == 0: always the
  * fused launch; on > 0: always one launch per list.  Results do not change. */
 int32_t WebRtcAecmSessions_SplitCleanTwoLaunches(AecmSessions *s, int32_t on);
+/* K-call and packet ticks with a clean input PER SESSION: one packet clock, some legs behind a noise suppressor and some not.
+ * Off (the default of a new object): nothing differs from an object without this call -- TickCalls* / TickPackets* with calls > 1,
+ * near_clean != NULL and a calling session that carries AECM_SESSION_NO_CLEAN return AECM_UNSUPPORTED_FUNCTION_ERROR.
+ * On (on != 0): those ticks (sync, Host and Async forms) are accepted.  For every session that calls the result is the loop written
+ * at TickCalls / TickPackets, a flagged session's K WebRtcAecm_Process calls getting nearendClean = NULL and every other session's
+ * clean[s] + c * n_s: bit for bit K ordinary ticks with the same flags on the same (packet ticks: re-laid) rows -- outputs, codes,
+ * echo paths and ExportSession(s) snapshots -- and interchangeable with them at any point of a session's life.
+ *   - The history rule of AECM_SESSION_NO_CLEAN applies unchanged: a tick that would change a calling session's kind is
+ *     AECM_BAD_PARAMETER_ERROR, nothing changed.
+ *   - No calling session flagged: exactly the K-call / packet tick with a clean input, by its launches.  Every calling session
+ *     flagged: the K-call / packet tick without a clean plane; near_clean is not touched and no clean ring is made.
+ *   - Otherwise: one planning launch that plans the K calls of every session and writes both live lists, then one tick launch per
+ *     list, each keeping its sessions' core state in registers across the K call pairs (WebRtcAecmSessions_SplitCleanTwoLaunches
+ *     does not apply: there is no fused form).  Measured on an MI355X against K back-to-back ordinary ticks with the same flags of
+ *     a twin object (profiles/r33_split_calls.txt), K = 2 / 3 / 6, half the sessions flagged: 65 536 sessions 0.89 / 0.84 / 0.79 of
+ *     the K ticks, 4 096 sessions 0.95 / 0.86 / 0.75; a quarter or three quarters flagged 0.91 .. 0.77 and 0.99 .. 0.77 (the least
+ *     for K = 2 in small objects, where the ramp-down and ramp-up between the two tick launches is most of the packet).
+ *   - Everything else TickCalls* / TickPackets* refuse stays refused, in the same order: SPLIT_CALLS, HALF_CALL in TickCalls, two
+ *     rates in TickCalls, the safe kernel variant, an attached session trace.
+ *   - While a call trace is attached (WebRtcAecmSessions_SetCallTrace) such a tick stays AECM_UNSUPPORTED_FUNCTION_ERROR, on or off.
+ * A switch of the object like SplitCleanTwoLaunches and ForceSparseTicks: it keeps its value across Init / InitRates, and it is
+ * host state read when a tick is planned, so it is ordered behind the ticks already enqueued; no synchronisation is needed.
+ * Returns 0; -1 for a NULL object. */
+int32_t WebRtcAecmSessions_SetSplitCallTicks(AecmSessions *s, int32_t on);
 
 /* ---- Session trace: where every call stands, per tick, without stopping the clock ------------------------------
  * Opt-in, per object.  While a trace buffer is attached, every session that calls in a tick of ONE call pair per session also writes
@@ -527,7 +556,8 @@ int32_t WebRtcAecmSessions_GetSessionTraceTicks(AecmSessions *s, int64_t *ticks)
  *    tick is the session trace's tick with the slot number as its number (AECM_SESSION_SPLIT_CALLS / AECM_SESSION_HALF_CALL: one
  *    record for the slot).  WebRtcAecmSessions_BufferFarend* writes no record and does not count.
  *  - Everything TickCalls* / TickPackets* refuse without a trace is refused with one (a calling AECM_SESSION_NO_CLEAN session with
- *    calls > 1 and a clean plane; the safe kernel variant; ...), and a refused tick changes nothing: not the sessions, not the
+ *    calls > 1 and a clean plane -- AECM_UNSUPPORTED_FUNCTION_ERROR also where WebRtcAecmSessions_SetSplitCallTicks is on: such
+ *    ticks are not call-traced; the safe kernel variant; ...), and a refused tick changes nothing: not the sessions, not the
  *    position, not the count.
  *  - Records are visible where out is; SetCallTrace is ordered behind the ticks already enqueued, without a synchronisation.
  *  - At most one of the two traces is attached: SetCallTrace while a session trace is attached, and SetSessionTrace while a call

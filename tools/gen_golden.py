@@ -195,6 +195,23 @@ def main():
         np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, calls=K, rates=mh.RATES, flags=flags, ms=ms, out=out,
                             codes=codes.astype(np.int16), paths=paths)
         print("sesspackets", fs, frame, K, "half packets", int((((flags & 8) != 0) & ((flags & 4) == 0)).sum()), sorted(set(codes.ravel().tolist())))
+    # K-call ticks with a clean near-end input per session (WebRtcAecmSessions_SetSplitCallTicks; tests/split_calls_helpers.py:
+    # golden_pattern): the 11 sessions of the split run, those of NEVER11 on instances whose every Process gets nearendClean = NULL,
+    # the others their clean rows, 48 calls each in ticks of K.  Arrays only: flags, msInSndCardBuf, outputs, codes, paths.
+    import split_calls_helpers as sch
+    import split_helpers as sph
+    for name, (fs, frame, K, seed) in sch.GOLDEN_CASES.items():
+        if only and only not in name:
+            continue
+        flags, ms = sch.golden_pattern(K, seed)
+        far, near, clean = sparse_helpers.signals(seed, sph.S11, sch.GOLDEN_CALLS * frame, fs, with_clean=True)
+        refs = sch.reference_sessions(lambda rate: pyoracle.RefSession(rate, 1, 3), [fs] * sph.S11, sph.NEVER11)
+        out, codes, _ = calls_helpers.run_reference(None, calls_helpers.calls_ops(K, frame, flags, ms),
+                                                    calls_helpers.Feed(far, near, sph.object_clean(clean, sph.NEVER11)), sessions=refs)
+        paths = np.stack([r.get_echo_path()[1] for r in refs])
+        np.savez_compressed(GOLD / f"{name}.npz", seed=seed, fs=fs, frame=frame, calls=K, never=np.array(sph.NEVER11, dtype=np.int32), flags=flags, ms=ms,
+                            out=out, codes=codes.astype(np.int16), paths=paths)
+        print("sesssplitcalls", fs, frame, K, "live calls", int(((flags & 4) == 0).sum()) * K, sorted(set(codes.ravel().tolist())))
     # The block corpus as sessions (tests/corpus_sessions.py): every case of a rate without a clean input as one session, ordinary
     # ticks with call_pattern delays and underruns for the whole case.  Kept: the output tail, a SHA-256 of the whole output, the
     # non-zero codes and the final echo paths.

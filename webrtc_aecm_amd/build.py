@@ -23,7 +23,8 @@ UBSAN_FLAGS = ["-O1", "-g", "-fsanitize=undefined", "-fno-sanitize-recover=undef
 CLI = LIB_DIR / "aecm_run"
 KERNEL_SOURCES = ["aecm_block_kernels.hip", "aecm_kernels.hip", "aecm_session_snapshot_kernels.hip", "aecm_tick_calls_kernels.hip",
                   "aecm_tick_calls_plan_kernels.hip", "aecm_tick_packets_kernels.hip", "aecm_tick_packets_plan_kernels.hip",
-                  "aecm_tick_split_kernels.hip", "aecm_tick_split_plan_kernels.hip", "aecm_tick_trace_kernels.hip", "aecm_trace_kernels.hip",
+                  "aecm_tick_split_kernels.hip", "aecm_tick_split_plan_kernels.hip", "aecm_tick_split_calls_kernels.hip",
+                  "aecm_tick_split_calls_plan_kernels.hip", "aecm_tick_trace_kernels.hip", "aecm_trace_kernels.hip",
                   "aecm_call_trace_kernels.hip", "aecm_call_trace_plan_kernels.hip", "aecm_ops_probe_kernels.hip"]
 HOST_SOURCES = ["aecm_engine.cpp", "aecm_session.cpp", "aecm_schedule.cpp", "aecm_sessions.cpp", "aecm_capi.cpp", "aecm_host_state.cpp"]
 SOURCES = KERNEL_SOURCES + HOST_SOURCES
@@ -41,6 +42,9 @@ SOURCE_FLAGS = {"aecm_block_kernels.hip": UNIFORM_BRANCH_FLAGS + KEEP_BRANCHES_F
 # its planning kernel, aecm_tick_calls_plan_kernels.hip -- one lane per session, every branch divergent -- takes no flags of its own)
                 "aecm_tick_packets_kernels.hip": UNIFORM_BRANCH_FLAGS,    # (the packet tick: the same pair of units, built the same way)
                 "aecm_tick_split_kernels.hip": UNIFORM_BRANCH_FLAGS,      # (the split tick, AECM_SESSION_NO_CLEAN: likewise)
+                # the split K-call / packet tick kernels: likewise (their planning kernels, aecm_tick_split_calls_plan_kernels.hip --
+                # one lane per session, as aecm_tick_calls_plan_kernels.hip -- take no flags of their own)
+                "aecm_tick_split_calls_kernels.hip": UNIFORM_BRANCH_FLAGS,
                 # the traced twins of the tick kernels (session trace): the tick units' flags, so that a trace observes the code that ships
                 "aecm_tick_trace_kernels.hip": UNIFORM_BRANCH_FLAGS,
                 # the traced twins of the K-call and packet tick kernels (call trace): likewise (their planning twins,

@@ -883,6 +883,12 @@ int32_t WebRtcAecmSessions_SplitCleanTwoLaunches(AecmSessions *s, int32_t on) {
     return 0;
 }
 
+int32_t WebRtcAecmSessions_SetSplitCallTicks(AecmSessions *s, int32_t on) {
+    if (!s) return -1;
+    s->batch->SetSplitCallTicks(on != 0);
+    return 0;
+}
+
 // The session trace: the record is aecm_session_trace.h's eight words and the block trace's eight.
 static_assert(sizeof(AecmSessionTrace) == aecm::kSessionTraceWords * sizeof(uint32_t) && offsetof(AecmSessionTrace, core) == aecm::kSessionTraceHeaderWords * sizeof(uint32_t) &&
                   offsetof(AecmSessionTrace, far_buffered) == 24 && offsetof(AecmSessionTrace, time_for_delay_change) == 28,
@@ -982,6 +988,11 @@ int32_t WebRtcAecmBatch_GetCheckCounters(int32_t device_id, uint64_t counters[2]
     if (e != hipSuccess) return AECM_UNSPECIFIED_ERROR;
     counters[0] += probe[0];
     counters[1] += probe[1];
+    uint64_t split_calls[2] = {0, 0};                      // so do the split K-call / packet tick kernels (SetSplitCallTicks)
+    e = aecm::ReadTickSplitCallsCheckCounters(split_calls, reset != 0);
+    if (e != hipSuccess) return AECM_UNSPECIFIED_ERROR;
+    counters[0] += split_calls[0];
+    counters[1] += split_calls[1];
     return 0;
 }
 

@@ -102,11 +102,13 @@ struct FlowCleanHistory {
 
     // May the tick be made?  flags: the per-session bytes or null (then everybody calls with no bit of interest set), any = the OR of
     // the calling sessions' bytes (FlowScanFlags), calls = call pairs per session.  Changes nothing that can be observed (it may bring
-    // `mode` up to date with `pending`).
-    FlowCleanVerdict Check(const uint8_t *flags, uint8_t any, bool has_clean, int32_t calls, FlowCleanTick *tick) const {
+    // `mode` up to date with `pending`).  split_calls: the object takes split ticks of several calls (TickObject::split_call_ticks,
+    // and no call trace attached) -- such a tick gives a session the same kind for all of its calls, so the rule is the one below;
+    // without it a split tick of calls > 1 is unsupported, before its histories are looked at.
+    FlowCleanVerdict Check(const uint8_t *flags, uint8_t any, bool has_clean, int32_t calls, FlowCleanTick *tick, bool split_calls = false) const {
         tick->split = has_clean && flags != nullptr && (any & (uint8_t)kFlowNoClean) != 0;
         tick->checked = tick->split || split_used;
-        if (tick->split && calls > 1) return kCleanUnsupported;
+        if (tick->split && calls > 1 && !split_calls) return kCleanUnsupported;
         if (!tick->checked) return kCleanAccepted;
         Fold();
         const size_t S = mode.size();

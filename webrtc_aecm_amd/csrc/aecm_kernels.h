@@ -239,6 +239,23 @@ hipError_t LaunchTickSplit(const StatePtrs &st, const TickIo &io, const TickFlow
 // The planning launch alone (aecm_tick_split_plan_kernels.hip; LaunchTickSplit calls it).
 hipError_t LaunchPlanSplit(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,
                            bool mixed_plan, hipStream_t stream);
+// A split tick of `calls` call pairs per session (aecm_tick_split_calls_kernels.hip; WebRtcAecmSessions_SetSplitCallTicks): the lists,
+// the counts and the clean plane of LaunchTickSplit, the rows and fio.plans ([S][calls][kFlowPlanWords]) of LaunchTickCalls /
+// LaunchTickPackets.  Three launches whatever `calls` is:
+//   aecm_flow_plan_split_calls_kernel / aecm_flow_plan_split_packets_kernel   the K-call / packet planning lane, filling both lists
+//   aecm_tick_split_calls_kernel<true> / aecm_tick_split_packets_kernel<true>     the loop-form tick body with a clean input over the
+//                                                                                 first list, ceil(clean_count / 4) workgroups
+//   aecm_tick_split_calls_kernel<false> / aecm_tick_split_packets_kernel<false>   the body without over the second list
+// Calls: every session at fio.fs and calls of io.n samples; Packets: every session at its own rate and call size, rows packed.
+hipError_t LaunchTickSplitCalls(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,
+                                int calls, hipStream_t stream);
+hipError_t LaunchTickSplitPackets(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams,
+                                  int calls, hipStream_t stream);
+// The planning launches alone (aecm_tick_split_calls_plan_kernels.hip; the two above call them).
+hipError_t LaunchPlanSplitCalls(const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split, int n_streams, int calls,
+                                hipStream_t stream);
+hipError_t LaunchPlanSplitPackets(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo &sp, const TickSplitIo &split,
+                                  int n_streams, int calls, hipStream_t stream);
 // The planning launch of LaunchTickFlow (sp == nullptr) / LaunchTickFlowSparse alone (aecm_kernels.hip; both call it).
 hipError_t LaunchPlanFlow(const StatePtrs &st, const TickIo &io, const TickFlowIo &fio, const TickSparseIo *sp, int n_streams, bool mixed_plan,
                           hipStream_t stream);
@@ -309,6 +326,8 @@ hipError_t ReadTickCallsCheckCounters(uint64_t counters[2], bool reset);
 hipError_t ReadTickPacketsCheckCounters(uint64_t counters[2], bool reset);
 // The share of aecm_tick_split_kernels.hip, likewise.
 hipError_t ReadTickSplitCheckCounters(uint64_t counters[2], bool reset);
+// The share of aecm_tick_split_calls_kernels.hip; WebRtcAecmBatch_GetCheckCounters adds it in.  Does not synchronise.
+hipError_t ReadTickSplitCallsCheckCounters(uint64_t counters[2], bool reset);
 
 // Device self test of the wave primitives; counters[0..7] are failure counts (all must be 0):
 //  0 shfl_xor, 1 exchange, 2 reduce_max/min/add, 3 shift_up1, 4 bpermute/readlane/writelane, 5 ballot,

@@ -478,6 +478,16 @@ int32_t SessionBatch::Enqueue(const int16_t *far, const int16_t *near, const int
         TickSparseIo lists = sp;
         lists.live = split_live_dev_;
         const TickSplitIo split{bases_dev_[slot] + tick_.live_bases.size(), plan.clean_count, plan.plain_count, FlowPlainListStart((uint32_t)plan.clean_count)};
+        if (plan.k_calls) {
+            // several call pairs per session (SetSplitCallTicks; no trace of either kind: CheckArgs, Plan): the K plans per session
+            // of the K-call tick, or -- half calls, sessions of another rate -- the packed layout of the packet tick; always one
+            // tick launch per list
+            fio.plans = calls_plans_;
+            if (plan.mixed_plan) fio.flags = flags & kNoFarend;
+            ok = plan.mixed_plan ? AECM_HIP_OK(LaunchTickSplitPackets(engine_->state_ptrs(), tio, fio, lists, split, S, calls, st))
+                                 : AECM_HIP_OK(LaunchTickSplitCalls(engine_->state_ptrs(), tio, fio, lists, split, S, calls, st));
+            break;
+        }
         ok = traced ? AECM_HIP_OK(LaunchTickSplitTraced(engine_->state_ptrs(), tio, fio, lists, split, tv, S, plan.mixed_plan, SplitTickTwoLaunches(plan.live), st))
                     : AECM_HIP_OK(LaunchTickSplit(engine_->state_ptrs(), tio, fio, lists, split, S, plan.mixed_plan, SplitTickTwoLaunches(plan.live), st));
         break;

@@ -105,13 +105,20 @@ public:
     //     session's kind is refused (bad parameter) and changes nothing, and so is every later tick or Process of an object that has
     //     accepted a tick with the bit, an object that never uses it is never refused for it.  Nobody flagged among the callers: the
     //     tick without the bit, by its launches; everybody: the launches of the tick without `clean`; else aecm_tick_split_kernels.hip,
-    //     always by the live lists (which of them: aecm_tick_plan.h, TickPlan::family).  Ignored without `clean` and in an idle session's byte; with calls > 1: unsupported function.
+    //     always by the live lists (which of them: aecm_tick_plan.h, TickPlan::family).  Ignored without `clean` and in an idle session's byte; with calls > 1: unsupported function
+    //     unless SetSplitCallTicks is on (and no call trace is attached): then the same rules for all K calls of the tick.
     static constexpr uint8_t kNoFarend = kFlowNoFarend, kSplitCalls = kFlowSplitCalls, kIdle = kFlowIdle, kHalfCall = kFlowHalfCall, kNoClean = kFlowNoClean;
     // 0 no Process call since the session's last initialisation, 1 every one carried a clean input, 2 none did, 3 both
     int32_t GetSessionCleanMode(int session, int32_t *mode) const;
     // The tick launch of a split tick: the fused kernel, or one launch per list -- by the size of the tick (SplitTickTwoLaunches below;
     // mode < 0, the default), or as the caller says (diagnostics, tools/bench_split_clean.py: 0 fused, > 0 two).  Results do not change.
     void SplitCleanTwoLaunches(int mode) { split_two_launches_ = mode < 0 ? -1 : mode > 0 ? 1 : 0; }
+    // K-call and packet ticks (calls > 1) with callers of both kinds: refused (unsupported function) while off, the default; on, they
+    // are planned like every split tick (TickObject::Plan: family split with k_calls, and mixed_plan for the packed layout) and made by
+    // aecm_tick_split_calls_kernels.hip -- always one tick launch per list, SplitCleanTwoLaunches does not apply.  The caller's
+    // switch, like ForceSparseTicks: host state only, so it is ordered behind the ticks already enqueued, and no Init touches it.
+    // With a call trace attached such ticks stay refused whatever the switch says.
+    void SetSplitCallTicks(bool on) { tick_.split_call_ticks = on; }
     // Diagnostics (tools/bench_sessions.py): every tick through the live list and the sparse tick kernel, idle sessions or
     // not -- what the indirection itself costs.
     void ForceSparseTicks(bool on) { tick_.force_sparse = on; }

@@ -68,6 +68,9 @@ struct TickObject {
     std::vector<int32_t> rates;              // [S] every session's own rate
     int32_t other_rates = 0;                 // sessions whose rate is not fs
     bool force_sparse = false;               // diagnostics: every tick by the live list
+    // WebRtcAecmSessions_SetSplitCallTicks: K-call and packet ticks with callers of both kinds are planned (family split with
+    // k_calls; mixed_plan: the packed layout) instead of refused.  The caller's switch, like force_sparse: no Init touches it.
+    bool split_call_ticks = false;
     int64_t near_pos = 0;                    // near-end samples ticked so far = ring position of the next tick's first one
     FlowObjectLag lag;                       // aecm_flow_plan.h: FlowRouteTick
     FlowCleanHistory history;                // what every session's Process calls carried (kNoClean)
@@ -167,7 +170,8 @@ struct TickObject {
         if (p.k_calls && (p.any & (a.packets ? kFlowSplitCalls : kFlowSplitCalls | kFlowHalfCall)) != 0) return refused(kTickBadParameter);
         p.half_calls = a.flags_per_session && (p.any & kFlowHalfCall) != 0;
         // kNoClean: a tick that gives a calling session another kind of Process call than it has had is refused
-        if (const FlowCleanVerdict v = history.Check(a.flags_per_session, p.any, a.has_clean, a.calls, &p.clean_tick))
+        // (callers of both kinds in a tick of several calls: only with the object's switch, and never under a call trace)
+        if (const FlowCleanVerdict v = history.Check(a.flags_per_session, p.any, a.has_clean, a.calls, &p.clean_tick, split_call_ticks && !call_trace_attached))
             return refused(v == kCleanUnsupported ? kTickUnsupported : kTickBadParameter);
         p.flags_per_session = a.flags_per_session;
         p.had_clean = a.has_clean;

@@ -11,8 +11,8 @@
 namespace aecm {
 
 // One lane per session: the planning lane of the sparse tick (kMixed: of the mixed tick -- the lane takes its session's rate from
-// the core state and plans with FlowTickMixed; aecm_flow_plan_lane.inc), behind first lines of its own, for two live lists in place
-// of one: a calling lane's id goes to the list of its kind (kFlowNoClean in its flag byte: the sessions whose Process gets no clean
+// the core state and plans with FlowTickMixed; aecm_flow_plan_lane.inc), behind first lines for two live lists in place of one
+// (aecm_flow_plan_split_list.inc): a calling lane's id goes to the list of its kind (kFlowNoClean in its flag byte: the sessions whose Process gets no clean
 // pointer), each list ascending, the second starting at split.plain_start.  A session without a clean input keeps a clean ring row
 // all the same; nothing reads it, so the resync may move it along with the near ring like everybody's.
 static_assert(kFlowPlanBlock == 256, "the planning kernels run 256 lanes per workgroup");
@@ -20,24 +20,7 @@ template <bool kMixed>
 __global__ __launch_bounds__(256)
 void aecm_flow_plan_split_kernel(TickFlowIo fio, TickSparseIo sp, TickSplitIo split, const int32_t *__restrict__ scal, int n, unsigned near_pos, int n_streams) {
     __shared__ uint32_t wave_counts[2][kFlowPlanBlock / 64];
-    const int s = blockIdx.x * 256 + threadIdx.x;
-    const bool in_range = s < n_streams;
-    const int flags = !in_range ? kFlowIdle : (int)fio.flags_per_session[s];
-    const bool live = (flags & kFlowIdle) == 0, no_clean = (flags & kFlowNoClean) != 0;
-    {
-        const uint64_t ballot_clean = __ballot(live && !no_clean), ballot_plain = __ballot(live && no_clean);
-        const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-        if (lane == 0) {
-            wave_counts[0][wave] = (uint32_t)__builtin_popcountll(ballot_clean);
-            wave_counts[1][wave] = (uint32_t)__builtin_popcountll(ballot_plain);
-        }
-        __syncthreads();
-        const uint32_t slot = FlowSplitSlot(no_clean, sp.block_base[blockIdx.x], split.plain_base[blockIdx.x], split.plain_start, wave_counts, wave,
-                                            ballot_clean, ballot_plain, lane);
-        // (the list holds FlowSplitListEntries(n_streams); either list ends where the host counted it to end)
-        const uint32_t end = no_clean ? split.plain_start + (uint32_t)split.plain_count : (uint32_t)split.clean_count;
-        if (live && slot < end && slot < FlowSplitListEntries((uint32_t)n_streams)) sp.live[slot] = (uint32_t)s;
-    }
+#include "aecm_flow_plan_split_list.inc"
 #define AECM_FLOW_PLAN_IDLE_SAMPLES n
 #define AECM_FLOW_PLAN_TICK(p)                                                                                      \
     if (kMixed) FlowTickMixed(r, scal[(size_t)s * kNumScal + S_MULT] == 2 ? 16000 : 8000, n, ms, flags, near_pos, p); \

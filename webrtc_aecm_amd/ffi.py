@@ -78,6 +78,7 @@ SESSIONS_SYMBOLS = [
     "WebRtcAecmSessions_GetSessionCleanMode", "WebRtcAecmSessions_SplitCleanTwoLaunches",
     "WebRtcAecmSessions_session_trace_size_bytes", "WebRtcAecmSessions_SetSessionTrace", "WebRtcAecmSessions_GetSessionTraceTicks",
     "WebRtcAecmSessions_SetCallTrace", "WebRtcAecmSessions_GetCallTraceCalls",
+    "WebRtcAecmSessions_SetSplitCallTicks",
 ]
 # include/aecm_batch.h: AecmSessionTrace -- the 64-byte record a session writes per tick while a trace is attached
 # (AecmSessions.set_session_trace); `core` is the block trace's record of the core state after the tick's last block
@@ -225,6 +226,8 @@ def load():
     lib.WebRtcAecmSessions_ForceSparseTicks.argtypes = [vp, C.c_int32]
     lib.WebRtcAecmSessions_GetSessionCleanMode.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.WebRtcAecmSessions_SplitCleanTwoLaunches.argtypes = [vp, C.c_int32]
+    if hasattr(lib, "WebRtcAecmSessions_SetSplitCallTicks"):    # (a library of an older tree, loaded for an A/B run, has none)
+        lib.WebRtcAecmSessions_SetSplitCallTicks.argtypes = [vp, C.c_int32]
     if hasattr(lib, "WebRtcAecmSessions_SetSessionTrace"):      # (a library of an older tree, loaded for an A/B run, has none)
         lib.WebRtcAecmSessions_session_trace_size_bytes.restype = C.c_size_t
         lib.WebRtcAecmSessions_session_trace_size_bytes.argtypes = []
@@ -947,6 +950,12 @@ class AecmSessions:
         """Diagnostics: the tick launch of a tick with SESSION_NO_CLEAN sessions and others -- True: always one launch per list,
         False: always the fused launch, None: by the size of the tick (the default of a new object)."""
         return self.lib.WebRtcAecmSessions_SplitCleanTwoLaunches(self.h, -1 if on is None else 1 if on else 0)
+
+    def set_split_call_ticks(self, on: bool = True) -> int:
+        """K-call and packet ticks (calls > 1) with a clean plane and SESSION_NO_CLEAN sessions among the callers: accepted while on,
+        AECM_UNSUPPORTED_FUNCTION_ERROR while off, the default (WebRtcAecmSessions_SetSplitCallTicks).  The object's switch: it
+        survives init()."""
+        return self.lib.WebRtcAecmSessions_SetSplitCallTicks(self.h, 1 if on else 0)
 
     def set_session_trace(self, ptr, session_stride, tick_stride, ring_ticks) -> int:
         """Attach a session trace (include/aecm_batch.h: WebRtcAecmSessions_SetSessionTrace): ptr = device memory for
