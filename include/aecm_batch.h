@@ -447,7 +447,9 @@ int32_t WebRtcAecmSessions_ProcessHost(AecmSessions *s, const int16_t *near_host
                                        int32_t *codes_host);
 int32_t WebRtcAecmSessions_Synchronize(AecmSessions *s);
 /* AECM_KERNEL_FAST (default) / AECM_KERNEL_SAFE for the object's block engine.  The tick kernel is built on the fast
- * primitives only: with the safe variant selected, ticks return AECM_UNSUPPORTED_FUNCTION_ERROR (and change nothing). */
+ * primitives only: with the safe variant selected, ticks return AECM_UNSUPPORTED_FUNCTION_ERROR (and change nothing).
+ * Far-end bursts (WebRtcAecmSessions_BufferFarend*) are accepted under either variant and make the reference's
+ * WebRtcAecm_BufferFarend calls as always. */
 int32_t WebRtcAecmSessions_SetKernelVariant(AecmSessions *s, int32_t variant);
 /* Diagnostics (tools/bench_sessions.py --occupancy): on != 0 sends every tick through the live list and the sparse tick kernel,
  * idle sessions or not, so that the cost of the indirection itself can be measured.  Results do not change. */

@@ -269,6 +269,19 @@ void *tickplan_new(int32_t n_sessions, int32_t fs) {
 void tickplan_free(void *o) { delete static_cast<TickObject *>(o); }
 void tickplan_init_session(void *o, int32_t session, int32_t fs) { static_cast<TickObject *>(o)->InitSession(session, fs); }
 void tickplan_force_sparse(void *o, int32_t on) { static_cast<TickObject *>(o)->force_sparse = on != 0; }
+// The object's other switches that a plan reads: WebRtcAecmSessions_SetSplitCallTicks, and the two traces (which = 0 the session
+// trace, 1 the call trace; returns 0 where the planner refuses the attachment: the other kind is attached).
+void tickplan_split_call_ticks(void *o, int32_t on) { static_cast<TickObject *>(o)->split_call_ticks = on != 0; }
+int32_t tickplan_attach_trace(void *o, int32_t which, int32_t on) {
+    TickObject *t = static_cast<TickObject *>(o);
+    return which ? t->AttachCallTrace(on != 0) : t->AttachTrace(on != 0);
+}
+// counts = {ticks of the session trace, call slots of the call trace}
+void tickplan_trace_counts(void *o, int64_t *counts) {
+    const TickObject *t = static_cast<TickObject *>(o);
+    counts[0] = t->trace_ticks;
+    counts[1] = t->call_trace_calls;
+}
 
 // One tick.  args = {flags, n_samples, calls, stride, packets, has_clean, host_pointers, ms_per_session, has_far, has_near_and_out, poisoned,
 // fast, commit}; out = {family, live, span, sparse_plan, sparse_tick, deferred_lag handed over, mixed_plan, need_slot, zero_out, clean_plane,

@@ -12,6 +12,7 @@ import webrtc_aecm_amd as aecm
 from helpers import (GOLDEN, adversarial_cases, call_pattern, describe_digest_diff, drive_session, far_frames_needed, golden_files,
                      oracle_batch, oracle_run, reconfiguration_events, run_burst_fixture, stream_config, synth_streams)
 from oracle import pyoracle
+from surface_fuzz import LoggedRef as _LoggedRef
 from webrtc_aecm_amd.synth import synth_clean, synth_pair
 
 pytestmark = pytest.mark.gpu
@@ -1228,26 +1229,6 @@ def test_far_end_burst_of_255_calls_overflows_the_jitter_buffer(fs, frame):
     for i in range(30, 60):
         tick(i)
     sb.close()
-
-
-class _LoggedRef:
-    """A reference session that remembers every call it received, so that a second reference session in the same state can be
-    made by replaying them (the reference has no way to copy an instance; migration tests need the copy)."""
-
-    def __init__(self, fs):
-        self.fs = fs
-        self.ref = pyoracle.RefSession(fs, 1, 3)
-        self.log = []
-
-    def call(self, name, *args):
-        self.log.append((name, args))
-        return getattr(self.ref, name)(*args)
-
-    def clone(self):
-        c = _LoggedRef(self.fs)
-        for name, args in self.log:
-            c.call(name, *args)
-        return c
 
 
 @_needs_ref

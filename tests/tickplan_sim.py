@@ -65,6 +65,11 @@ def lib():
         l.tickplan_init_session.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
         l.tickplan_force_sparse.restype = None
         l.tickplan_force_sparse.argtypes = [C.c_void_p, C.c_int32]
+        l.tickplan_split_call_ticks.restype = None
+        l.tickplan_split_call_ticks.argtypes = [C.c_void_p, C.c_int32]
+        l.tickplan_attach_trace.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        l.tickplan_trace_counts.restype = None
+        l.tickplan_trace_counts.argtypes = [C.c_void_p, C.c_void_p]
         l.tickplan_tick.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         l.tickplan_state.restype = None
         l.tickplan_state.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
@@ -97,6 +102,23 @@ class Object:
 
     def init_session(self, session, fs):
         lib().tickplan_init_session(self.h, session, fs)
+
+    def force_sparse(self, on=True):
+        lib().tickplan_force_sparse(self.h, int(on))
+
+    def split_call_ticks(self, on=True):
+        """WebRtcAecmSessions_SetSplitCallTicks."""
+        lib().tickplan_split_call_ticks(self.h, int(on))
+
+    def attach_trace(self, which, on=True):
+        """which: "session" / "call".  False where the planner refuses (the other trace is attached)."""
+        return bool(lib().tickplan_attach_trace(self.h, int(which == "call"), int(on)))
+
+    def trace_counts(self):
+        """(ticks the session trace has counted, call slots the call trace has)."""
+        c = np.zeros(2, dtype=np.int64)
+        lib().tickplan_trace_counts(self.h, c.ctypes.data)
+        return int(c[0]), int(c[1])
 
     def tick(self, flags=None, all_flags=0, n=160, calls=1, stride=None, packets=False, clean=False, host=False, ms_per_session=False, far=True,
              near_out=True, poisoned=False, fast=True, commit=True):

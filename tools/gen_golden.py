@@ -237,6 +237,17 @@ def main():
         out, codes, paths = fc.drive_reference(sch, far, near, lambda rate: pyoracle.RefSession(rate, 1, 3))
         np.savez_compressed(GOLD / f"{name}.npz", **fc.summary(out, codes, paths))
         print("sessflow", family, out.shape, "codes", int((codes != 0).sum()))
+    # The session surface fuzz (tests/surface_fuzz.py): per case the SHA-256 of the program and of what the reference answers to it
+    # (every code, every output row, the echo paths).
+    if not only or only in "session_surface_fuzz":
+        import json
+        import surface_fuzz as sf
+        pins = {}
+        for case in sorted(sf.CASES):
+            prog = sf.generate(case)
+            pins[case] = dict(program=sf.program_sha256(prog), expected=sf.run_reference(case, prog).digest.hexdigest())
+            print("surface fuzz", case, len(prog), "ops")
+        (GOLD / "session_surface_fuzz.json").write_text(json.dumps(pins, indent=1, sort_keys=True) + "\n")
     from helpers import stream_config
     for name, S, nb, fs, seed0 in RAGGED_CASES:
         if only and only not in name:
